@@ -10,17 +10,22 @@ the GPU → write both JPEG files per slice. Nothing is cached between steps.
 Headline = BASELINE config 3 as written (strong scaling, round 5): every step is ONE 465-slice
 cohort sharded contiguously over the N ranks, so the total work per step is fixed as N grows
 ("scaling": "strong", config.global_batch = 465). The weak-scaling figure (N cohort replicas with
-distinct output trees, one full cohort per rank per step) is measured right after and reported under
-config.weak; `--scaling weak` swaps the two. At N = 1 they coincide.
+distinct output trees, one full cohort per rank per step) is measured right after with `--full` and
+reported under config.weak; `--scaling weak` swaps the two. At N = 1 they coincide.
 
 Ranks: `python bench.py --gpus N` starts N rank processes itself (before anything touches a GPU)
 and supervises them; under torchrun (WORLD_SIZE set) each process is one rank. Either way the
 ranks talk through the native communicator the CLI uses (src/dist: RCCL over xGMI, or the
 shared-memory host comm when ranks share a GPU), bootstrapped via the torch rendezvous store.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
     NM03_DEVICE_OVERRIDE=0 python bench.py --gpus 4      # 4 ranks sharing GPU 0 (rehearsal)
+
+A plain run sets up, warms up, times the K steps and prints the result line. `--full` adds every other
+figure of the record (the other scaling mode, wipe-each-pass, single passes, whole CLI invocations);
+`--wipe-passes`, `--single-passes` and `--cli-runs` given explicitly select one of them on their own.
+`--dump-outputs DIR` writes what the last timed step produced as DIR/<name>.npy (dump_outputs()).
 """
 import argparse
 import json
@@ -87,12 +92,21 @@ def parse_args(argv=None):
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                     help="which figure is the headline value (default strong: BASELINE config 3, one cohort "
                          "sharded over the ranks); the other is reported next to it")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other scaling mode's measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else the record can hold: the other scaling "
+                         "mode (config.weak / config.strong), config.wipe_each_pass (200 passes), the single passes "
+                         "(100) and config.cli_wall (10 runs). Off by default: a plain run only times --steps steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last of them produced (per-slice status codes, JPEG "
+                         "file sizes, decoded pixels of a fixed sample of slices) as DIR/<name>.npy")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="--full: skip the other scaling mode's measurement")
     # 200 wipe passes ≈ 0.3-0.7 s timed (20 passes were 43 ms: one 10 ms hiccup or the reaper's final
     # drain moved the figure by 25-40%).
-    ap.add_argument("--wipe-passes", type=int, default=200,
+    ap.add_argument("--wipe-passes", type=int, default=None,
                     help="also time this many passes that each first wipe their output directories (the "
-                         "reference's per-run rm -rf; reported as config.wipe_each_pass; 0 = skip)")
+                         "reference's per-run rm -rf; reported as config.wipe_each_pass; 0 = skip; "
+                         "default 200 with --full, else 0)")
     ap.add_argument("--wipe-mode", choices=("reaper", "inline"), default="reaper",
                     help="wipe passes: rename each output directory aside and delete it on 2 background "
                          "reaper threads (cohort.h OutputReaper; the final drain is inside the clock), or "
@@ -126,9 +140,10 @@ def parse_args(argv=None):
                     help="host I/O threads per rank (0 = the rank's CPU partition and budget share, ≤16)")
     ap.add_argument("--single-pass-cap", type=int, default=0,
                     help="batch cap of the capped single passes (0 = ceil(shard / streams))")
-    ap.add_argument("--single-passes", type=int, default=100,
+    ap.add_argument("--single-passes", type=int, default=None,
                     help="also time this many single strong-scaling passes (one cohort sharded over the "
-                         "ranks, nothing else in flight; config.strong.single_pass_ms; 0 = skip)")
+                         "ranks, nothing else in flight; config.strong.single_pass_ms; 0 = skip; "
+                         "default 100 with --full, else 0)")
     ap.add_argument("--comm", choices=("auto", "rccl", "host"), default=os.environ.get("NM03_COMM", "auto"))
     ap.add_argument("--data-root", default=os.path.join(_scratch(), "nm03_bench_data"))
     ap.add_argument("--out-root", default=os.path.join(_scratch(), "nm03_bench_out"))
@@ -156,10 +171,10 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the launcher, rendezvous, comm, sharding and aggregation: every step "
                          "of a real run except the engine (no GPU); the JSON value is meaningless")
-    ap.add_argument("--cli-runs", type=int, default=10,
+    ap.add_argument("--cli-runs", type=int, default=None,
                     help="also time this many whole invocations of the unmodified img_processing_parallel --gpus N "
                          "on the bench cohort, as the reference measured its binaries (hyperfine, README.md:92-96); "
-                         "reported as config.cli_wall (0 = skip)")
+                         "reported as config.cli_wall (0 = skip; default 10 with --full, else 0)")
     ap.add_argument("--numa-data", choices=("auto", "off"), default="auto",
                     help="auto: one input copy per NUMA node, each rank reads the copy on its GPU's node")
     ap.add_argument("--cpu-profile", default="",
@@ -167,7 +182,16 @@ def parse_args(argv=None):
                          "symbolise with tools/cpu_profile.py")
     ap.add_argument("--cpu-profile-period-us", type=int, default=250,
                     help="one sample per this much process CPU time (--cpu-profile)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    # The figures beside the headline: their default counts with --full, none in a plain run.
+    for name, count in (("wipe_passes", 200), ("single_passes", 100), ("cli_runs", 10)):
+        if getattr(args, name) is None:
+            setattr(args, name, count if args.full else 0)
+    if not args.full:
+        args.no_secondary = True
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs a run that writes its outputs (not --dry-run)")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -255,6 +279,52 @@ def _pass_items(items, out_root, k):
             made.add(d)
         out.append((f, d))
     return out
+
+
+DUMP_SAMPLE_SLICES = 8  # decoded as float32: 8 slices × 2 JPEGs × 512² RGB = 48 MB, under the 64 MB a dump may take
+
+
+def dump_outputs(dump_dir, items, codes, suffix=""):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float32 .npy.
+
+    `items` is that step's work list (input file, output directory) in order and `codes` the engine's
+    per-slice status. The step's other result is the two JPEG files per slice it wrote:
+      codes             [n]        per-slice status code
+      jpeg_bytes        [n, 2]     size of <stem>_original.jpg / <stem>_processed.jpg (-1 = missing)
+      sample_index      [s]        the slices decoded below: a fixed seeded sample of the n
+      original_pixels,
+      processed_pixels  [s, ...]   the sampled slices' two JPEGs decoded (Pillow); without Pillow
+      original_jpeg, processed_jpeg  [s, longest]  their bytes instead, zero-padded
+    The cohort is generated from fixed seeds, so two runs with the same arguments dump the same arrays."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    kinds = ("original", "processed")
+    paths = [[os.path.join(od, os.path.splitext(os.path.basename(f))[0] + f"_{kind}.jpg") for kind in kinds]
+             for f, od in items]
+    sizes = np.array([[os.path.getsize(p) if os.path.exists(p) else -1 for p in pair] for pair in paths],
+                     dtype=np.float32).reshape(len(paths), 2)
+    sample = np.sort(np.random.RandomState(0).choice(len(paths), min(DUMP_SAMPLE_SLICES, len(paths)), replace=False))
+    out = {"codes": np.asarray(codes, dtype=np.float32), "jpeg_bytes": sizes,
+           "sample_index": sample.astype(np.float32)}
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    for k, kind in enumerate(kinds):
+        blobs = []
+        for i in sample:
+            with open(paths[i][k], "rb") as f:
+                blobs.append(f.read())
+        if Image is not None:
+            import io
+            out[f"{kind}_pixels"] = np.stack([np.asarray(Image.open(io.BytesIO(b)), dtype=np.float32) for b in blobs])
+        else:
+            padded = np.zeros((len(blobs), max(len(b) for b in blobs)), dtype=np.float32)
+            for row, b in zip(padded, blobs):
+                row[:len(b)] = np.frombuffer(b, dtype=np.uint8)
+            out[f"{kind}_jpeg"] = padded
+    for name, a in out.items():
+        np.save(os.path.join(dump_dir, f"{name}{suffix}.npy"), a)
 
 
 class _DryEngine:
@@ -465,9 +535,15 @@ def run_rank(args):
             ok += len(codes) - len(msgs)
             for k in stage:
                 stage[k] += times[k]
+            last_codes = codes[len(codes) - len(mine):]
+            last_items = _pass_items(mine, out_root, steps - 1)
         else:
+            last_codes = None
+            last_items = trees[(steps - 1) % depth]  # passes() restarts at tree 0
+
             def sink(codes, msgs, times):
-                nonlocal ok
+                nonlocal ok, last_codes
+                last_codes = codes
                 ok += len(codes) - len(msgs)
                 for k in stage:
                     stage[k] += times[k]
@@ -496,6 +572,7 @@ def run_rank(args):
         per_rank["slices_per_s"] = [round(s / max(t, 1e-12), 1) for s, t in zip(per_rank["slices_ok"], per_rank["own_s"])]
         own = per_rank["own_s"]
         return {
+            "last_step": (last_items, last_codes),  # what the last timed step wrote and returned (--dump-outputs)
             "value": total_ok / dt,
             "ms_per_step": dt * 1e3 / steps,
             "global_batch": global_items,
@@ -547,6 +624,9 @@ def run_rank(args):
 
     primary = measure(args.scaling, args.out_root, args.steps, args.warmup, profile=args.cpu_profile)
     len_mine_primary = [primary["per_rank"]["slices"][rank] / args.steps]
+    if args.dump_outputs:
+        # Before anything else runs: later figures plan their own output trees under out_root.
+        dump_outputs(args.dump_outputs, *primary["last_step"], suffix=f"_rank{rank}" if world > 1 else "")
     secondary = None
     other = "strong" if args.scaling == "weak" else "weak"
     if not args.no_secondary and world > 1:

@@ -11,14 +11,18 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(tmp_path, *extra, env=None, timeout=240):
+def _bench_cmd(tmp_path, *args, env=None, timeout=240):
     e = dict(os.environ, NM03_COMM_TIMEOUT_S="30")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
     e.update(env or {})
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "2", "--warmup", "1",
-           "--data-root", str(tmp_path / "data"), "--out-root", str(tmp_path / "out"), "--numa-data", "off", *extra]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *args,
+           "--data-root", str(tmp_path / "data"), "--out-root", str(tmp_path / "out"), "--numa-data", "off"]
     return subprocess.run(cmd, cwd=str(tmp_path), env=e, capture_output=True, text=True, timeout=timeout)
+
+
+def _bench(tmp_path, *extra, env=None, timeout=240):
+    return _bench_cmd(tmp_path, "--dry-run", "--steps", "2", "--warmup", "1", *extra, env=env, timeout=timeout)
 
 
 def _json_line(out):
@@ -31,7 +35,7 @@ def _json_line(out):
 def test_bench_self_launch_n_ranks(tmp_path, n):
     """`python bench.py --gpus N` starts N ranks itself: n_gpus, per-rank arrays; the headline is
     BASELINE config 3 as written (strong: one cohort sharded), weak scaling the secondary."""
-    r = _bench(tmp_path, "--gpus", str(n), "--comm", "host")
+    r = _bench(tmp_path, "--gpus", str(n), "--comm", "host", "--full")
     assert r.returncode == 0, r.stderr
     rec = _json_line(r.stdout)
     assert rec["n_gpus"] == n and rec["config"]["parallelism"] == f"dp{n}"
@@ -85,6 +89,45 @@ def test_bench_single_rank_dry(tmp_path):
     assert r.returncode == 0, r.stderr
     rec = _json_line(r.stdout)
     assert rec["config"]["pipeline_depth"] == 3 and rec["config"]["per_rank"]["slices"] == [4.0 * 465]
+
+
+def test_bench_plain_run_times_only_its_steps(tmp_path):
+    """Without --full the record holds the headline alone; --full adds the other figures (the CLI
+    runs need the engine, so a dry run leaves them out either way)."""
+    r = _bench(tmp_path)
+    assert r.returncode == 0, r.stderr
+    rec = _json_line(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert not {"wipe_each_pass", "weak", "strong", "cli_wall"} & set(rec["config"])
+    r = _bench(tmp_path, "--full")
+    assert r.returncode == 0, r.stderr
+    cfg = _json_line(r.stdout)["config"]
+    assert cfg["wipe_each_pass"]["steps"] == 200 and cfg["strong"]["single_pass_passes"] == 100
+    assert cfg["weak"]["note"] == "1 rank: weak and strong coincide"
+
+
+def test_bench_dump_outputs_host_only(tmp_path):
+    """--dump-outputs: the last timed step's results as float32 .npy, at most 64 MB, the same from
+    run to run (host path: the real loads and writes, no GPU)."""
+    import numpy as np
+
+    def run(name):
+        r = _bench_cmd(tmp_path, "--host-only", "--steps", "3", "--warmup", "1", "--threads", "4",
+                       "--dump-outputs", str(tmp_path / name))
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert _json_line(r.stdout)["steps"] == 3
+        return {f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+
+    a, b = run("a"), run("b")
+    assert {"codes", "jpeg_bytes", "sample_index"} < set(a) and set(a) == set(b)
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["codes"].shape == (465,) and not a["codes"].any()
+    assert a["jpeg_bytes"].shape == (465, 2) and (a["jpeg_bytes"] > 0).all()
+    assert len(a["sample_index"]) == 8 and len(set(a["sample_index"])) == 8
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
 
 
 def test_bench_under_torchrun(tmp_path):

@@ -818,7 +818,7 @@ def test_bench_multirank_one_gpu(native, tmp_path):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(__file__)), "bench.py"),
                         "--gpus", "2", "--steps", "2", "--warmup", "1", "--threads", "8", "--numa-data", "off",
-                        "--cli-runs", "2", "--single-passes", "5",
+                        "--full", "--cli-runs", "2", "--single-passes", "5",
                         "--data-root", str(tmp_path / "d"), "--out-root", str(tmp_path / "o")],
                        env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -8,7 +8,7 @@ O=gpurun_out/r6_profile
 mkdir -p $O
 export PYTHONUNBUFFERED=1
 B="python -u bench.py --keep-data"
-timeout -k 10 240 $B --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || exit 1
+timeout -k 10 240 $B --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
 timeout -k 10 240 $B --steps 4000 --warmup 5 --no-secondary --wipe-passes 0 --single-passes 0 --cli-runs 0 \
   --cpu-profile $O/cpu > $O/bench_prof.json 2> $O/bench_prof.err || exit 1
 for r in 1 2 3; do
