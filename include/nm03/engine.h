@@ -67,17 +67,19 @@ struct EngineConfig {
   PipelineParams pipe;
   RenderParams render;
   bool export_jpeg = true;
-  bool resume = false;  // skip items whose two JPEGs already exist (SURVEY §5.4 --resume)
+  bool resume = false;  // skip items whose requested JPEGs (two, three with render.overlay) all exist (SURVEY §5.4 --resume)
   // Host path only: no HIP call at all. Every load, parse,
   // 12-bit pack into the (pageable) upload blob and every JPEG file write runs exactly as in a
   // GPU run; the GPU stages are replaced by streaming a fixed pair of pre-encoded JPEG segments
   // into the output buffer (what the encoder's PCIe stores would leave in memory). Measures the
   // host side's CPU per slice on its own, on any machine (bench.py --host-only).
+  // Not available with render.overlay (rendered and encoded on the GPU): the constructor throws.
   bool host_only = false;
   // Host-mapped bytes per image for the GPU encoder's stuffed output (0 = 3/8 of the canvas: 96 KiB
   // for 512² — full-contrast noise renders to 86.6 KB, a phantom slice to 14 KB; round 5 used half
   // the canvas, whose pinning was a third of a cold CLI's engine constructor). Larger images are CPU
-  // re-encoded (StageTimes counts them); tests force that path with a tiny capacity.
+  // re-encoded (StageTimes counts them); tests force that path with a tiny capacity. Overlay images
+  // (render.overlay) get twice the default, sized for colour; a value set here applies to them too.
   uint32_t jpeg_out_cap = 0;
   // Every slot and the uploads on ONE HIP stream (false: a stream per slot plus a shared upload
   // stream). For processes limited to one HW queue (GPU_MAX_HW_QUEUES=1, the CLIs' short jobs), where
@@ -117,6 +119,8 @@ struct SingleResult {
   int srg_iterations = 0;
   // canvases and JPEG files: original, preprocessed, segmentation, erosion, dilation
   std::vector<std::vector<uint8_t>> canvases, jpegs;
+  // RenderParams::overlay only: the RGB canvas [out_h, out_w, 3] (original + dilated mask) and its file.
+  std::vector<uint8_t> overlay, jpeg_overlay;
 };
 
 struct RunHandle;  // a submitted run (Engine::submit)

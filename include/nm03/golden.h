@@ -79,6 +79,14 @@ std::vector<uint8_t> render_gray(const std::vector<float>& values, const RenderG
 std::vector<uint8_t> render_labels(const std::vector<uint8_t>& label, const std::vector<uint8_t>& border_mask,
                                    const RenderGeom& g, uint8_t fill, uint8_t border_value);
 
+// Overlay (RenderParams::overlay): the gray render with the label colour blended over it, interleaved
+// RGB [out_h, out_w, 3]. Per pixel the opacity is `border_a` where the border bit is set, else `fill_a`
+// where the label bit is set, else 0 (labels sampled nearest, exactly render_labels); each channel is
+// overlay_blend(gray, color[c], a) (pixel_math.h). Pixels outside the image footprint stay black.
+std::vector<uint8_t> render_overlay(const std::vector<float>& values, const std::vector<uint8_t>& label,
+                                    const std::vector<uint8_t>& border_mask, const RenderGeom& g, float lo, float hi,
+                                    bool nearest, uint8_t fill_a, uint8_t border_a, const uint8_t* color);
+
 struct SliceResult {
   std::vector<float> clipped, median, sharpened;
   std::vector<uint8_t> band, region, eroded, dilated;
@@ -90,11 +98,14 @@ SliceResult run(const SliceInput& s, const PipelineParams& p, bool with_erosion)
 // Render + JPEG of the two exported images of seq/par (original, processed).
 struct SliceJpegs {
   std::vector<uint8_t> original, processed;
+  // RenderParams::overlay only: the RGB canvas (original + dilated mask) and its JPEG file.
+  std::vector<uint8_t> overlay_canvas, overlay;
 };
 SliceJpegs export_jpegs(const SliceInput& s, const SliceResult& r, const PipelineParams& p, const RenderParams& rp);
 
 // test_pipeline's five stage images (test_pipeline.cpp:164-179): original, preprocessed,
-// segmentation, erosion, dilation — canvases and their JPEG files.
+// segmentation, erosion, dilation — canvases and their JPEG files. With RenderParams::overlay a
+// sixth entry follows: the RGB overlay canvas (original + dilated mask) and its colour JPEG.
 struct StageImages {
   std::vector<std::vector<uint8_t>> canvases, jpegs;
 };

@@ -40,6 +40,15 @@ std::vector<uint8_t> encode_gray(const uint8_t* gray, int width, int height, int
 std::vector<uint8_t> encode_scan_gray(const uint8_t* gray, int width, int height, int stride, const Tables& t,
                                       Sampling s = kSampling420);
 
+// True-colour golden encoder: interleaved 8-bit RGB (`stride` bytes per row) → YCbCr 4:2:0 or
+// 4:4:4 with libjpeg's colour conversion and h2v2 downsampling (jpeg_common.h), any width and
+// height; byte-identical to libjpeg(-turbo). kSamplingGray throws std::invalid_argument.
+std::vector<uint8_t> encode_rgb(const uint8_t* rgb, int width, int height, int stride, int quality,
+                                Sampling s = kSampling420);
+// Its entropy-coded segment only: the reference for the GPU colour encoder (k4_jpeg_rgb.hip).
+std::vector<uint8_t> encode_scan_rgb(const uint8_t* rgb, int width, int height, int stride, const Tables& t,
+                                     Sampling s = kSampling420);
+
 // Write header + scan + EOI to a file (single writev-style write).
 void write_jpeg_file(const std::string& path, const std::vector<uint8_t>& header, const uint8_t* scan,
                      size_t scan_len);

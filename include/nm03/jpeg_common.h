@@ -100,6 +100,24 @@ inline constexpr HuffEnc kHuffAcLuma = build_huff(kAcLumaBits, kAcLumaVals);
 inline constexpr HuffEnc kHuffDcChroma = build_huff(kDcChromaBits, kDcChromaVals);
 inline constexpr HuffEnc kHuffAcChroma = build_huff(kAcChromaBits, kAcChromaVals);
 
+// libjpeg's RGB → YCbCr (jccolor.c rgb_ycc_convert): 16-bit fixed point, FIX(x) = round(x·2^16),
+// Y rounded to nearest, Cb/Cr offset by 128 with a rounding term of ONE_HALF − 1. R = G = B = v gives
+// exactly (v, 128, 128). Checked byte for byte against Pillow/libjpeg-turbo (tests/test_jpeg_rgb.py).
+NM03_HD int32_t rgb_to_y(int32_t r, int32_t g, int32_t b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
+NM03_HD int32_t rgb_to_cb(int32_t r, int32_t g, int32_t b) {
+  return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+}
+NM03_HD int32_t rgb_to_cr(int32_t r, int32_t g, int32_t b) {
+  return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+}
+// 4:2:0 chroma: libjpeg's plain h2v2_downsample (jcsample.c), the mean of the 2×2 full-resolution
+// samples with an alternating bias — 1 for even output columns, 2 for odd ones. Edges: columns are
+// replicated at full resolution (source column min(x, w − 1)) out to whole blocks, rows are
+// replicated after downsampling (output row min(cy, ceil(h/2) − 1); an odd last row pairs with itself).
+NM03_HD int32_t h2v2_sample(int32_t p00, int32_t p01, int32_t p10, int32_t p11, int out_col) {
+  return (p00 + p01 + p10 + p11 + 1 + (out_col & 1)) >> 2;
+}
+
 // libjpeg jpeg_quality_scaling + jpeg_add_quant_table(force_baseline=TRUE).
 inline void quality_table(const uint8_t* base, int quality, uint16_t* out) {
   if (quality <= 0) quality = 1;

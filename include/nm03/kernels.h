@@ -146,6 +146,28 @@ void launch_jpeg(const uint8_t* canvas, const JpegDesc* jd, int ncanvas, int out
 // Whether the fused encoder renders --render-filter nearest gray images for this layout (else callers
 // render them into canvases first).
 inline bool jpeg_fuses_nearest(int sampling) { return sampling == 0; }
+// K4-RGB (k4_jpeg_rgb.hip): colour JPEG of interleaved RGB canvases (out_w × out_h × 3 bytes at
+// JpegDesc::canvas_off of `canvas`; render and stage fields unused) → YCbCr 4:2:0 or 4:4:4 segments,
+// the gray encoder's structure and `out` / `out_sizes` / capacity semantics. `w` needs look_cap ≥
+// ncanvas × jpeg_rgb_parts(...) (its spill area is sized by look_cap as for launch_jpeg); it may be
+// the JpegWork of launch_jpeg calls on the same stream.
+size_t jpeg_rgb_parts(int out_w, int out_h, int sampling);
+void launch_jpeg_rgb(const uint8_t* canvas, const JpegDesc* jd, int ncanvas, int out_w, int out_h, const int32_t* div_luma,
+                     const int32_t* div_chroma, JpegWork& w, uint8_t* out, int32_t* out_sizes, hipStream_t stream,
+                     int sampling = 0);
+// Loads the colour encoder's code object on the current device. Not part of preload_kernels: only
+// an engine with the overlay on (in its constructor) and the Python op (before its first launch)
+// load it, so a default run never pays for it — and no slot thread ever loads it lazily.
+void preload_jpeg_rgb();
+
+// K3 overlay: RGB canvas i (3 · out_w · out_h bytes at rgb + i · 3 · out_w · out_h) = the gray render
+// rd[gray_first + i · stride] with colour `rgb_color` (R | G << 8 | B << 16) blended over it at the
+// opacity the label render rd[label_first + i · stride] gives the pixel (its border_value / fill / 0)
+// — pixel_math.h overlay_blend. Any geometry; out_w a multiple of 4.
+void launch_render_overlay(const uint16_t* raw, const float* f32, const uint64_t* bits, const SliceStats* stats,
+                           const RenderDesc* rd, int gray_first, int label_first, int stride, int ncanvas, int out_w,
+                           int out_h, uint32_t rgb_color, uint8_t* rgb, hipStream_t stream);
+
 // K6: binary threshold lo ≤ x ≤ hi → u8 0/1 (in 16-byte aligned, out 4-byte aligned).
 void launch_threshold(const float* in, uint8_t* out, size_t n, float lo, float hi, hipStream_t stream);
 

@@ -65,6 +65,13 @@ struct RenderParams {
   // Component layout of the JPEG files (jpeg::Sampling, --jpeg-sampling): YCbCr 4:2:0 (default),
   // 4:4:4, or a one-component gray file — which one Qt writes for FAST's image is not pinned.
   int jpeg_sampling = 0;
+  // Colour overlay export (--overlay): the original render with the dilated mask blended over it at
+  // label_opacity (fill) and border_opacity (border), pixel_math.h overlay_blend. Opt-in; needs a
+  // YCbCr layout (a one-component file cannot carry colour).
+  bool overlay = false;
+  // Label colour of the overlay (--overlay-color R,G,B). The reference's LabelColors{1: White} is
+  // 255,255,255, which over a gray slice is nearly invisible; pure green is this project's choice.
+  uint8_t overlay_color[3] = {0, 255, 0};
 };
 
 enum RenderFilter : int { kFilterBilinear = 0, kFilterNearest = 1 };

@@ -171,4 +171,17 @@ inline uint8_t opacity_u8(float alpha) {
   return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
+// Overlay blend (RenderParams::overlay): one channel of label colour `c` at 8-bit opacity `a` over
+// the gray value `g`: (a·c + (255 − a)·g + 127) / 255, exact integer arithmetic (a = 0 gives g,
+// a = 255 gives c). The numerator stays below 2^16, so on the device the division is one
+// multiply-high by ceil(2^32 / 255) (exact for every numerator < 2^16, as Div16 in the encoder).
+NM03_HD uint8_t overlay_blend(uint8_t g, uint8_t c, uint8_t a) {
+  const uint32_t n = (uint32_t)a * c + (uint32_t)(255 - a) * g + 127u;
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint8_t)__umulhi(n, 0x01010102u);
+#else
+  return (uint8_t)(n / 255u);
+#endif
+}
+
 }  // namespace nm03

@@ -45,6 +45,8 @@ class PipelineConfig:
     jpeg_quality: int = 75
     render_filter: int = 0  # gray renders: 0 bilinear (default), 1 nearest (params.h RenderFilter)
     jpeg_sampling: int = 0  # JPEG files: 0 YCbCr 4:2:0 (default), 1 YCbCr 4:4:4, 2 one gray component
+    overlay: bool = False  # also export <stem>_overlay.jpg: the original with the dilated mask blended over it (colour)
+    overlay_color: tuple = (0, 255, 0)  # label colour of the overlay (the reference's white is nearly invisible over gray)
     # engine
     batch_size: int = 25
     streams: int = 3
@@ -72,6 +74,8 @@ class PipelineConfig:
         for k in self._RENDER:
             setattr(r, k, getattr(self, k))
         r.filter = self.render_filter
+        r.overlay = bool(self.overlay)
+        r.overlay_color = [int(c) for c in self.overlay_color]
         return r
 
     def engine_config(self):

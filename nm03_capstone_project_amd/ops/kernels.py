@@ -147,3 +147,52 @@ def jpeg_encode(canvas, quality=75, header=True, sampling="420"):
         return segs
     hdr = native().jpeg_header(w, h, int(quality), samp)
     return [None if s is None else hdr + s + b"\xff\xd9" for s in segs]
+
+
+def jpeg_encode_rgb(canvas, quality=75, header=True, sampling="420", out_cap=0):
+    """GPU colour JPEG of uint8 RGB canvases [N,H,W,3] (H, W multiples of 16) → list of bytes
+    (complete JFIF files when header=True, else the entropy-coded segments). `sampling`: "420"
+    (YCbCr 4:2:0, the default) or "444"; "gray" raises: one component cannot carry colour.
+    `out_cap`: output bytes per image (0: the canvas size); an image that exceeds it comes back None."""
+    c = canvas.unsqueeze(0) if canvas.dim() == 3 else canvas
+    _check(c, (torch.uint8,), "canvas")
+    if c.dim() != 4 or c.shape[3] != 3:
+        raise ValueError("canvas must be [N, H, W, 3]")
+    n, h, w, _ = c.shape
+    samp = JPEG_SAMPLING[sampling] if isinstance(sampling, str) else int(sampling)
+    if samp not in (0, 1):
+        raise ValueError("a colour JPEG needs sampling '420' or '444'")
+    segs = native().k_jpeg_rgb(c.data_ptr(), n, h, w, int(quality), _stream(), samp, int(out_cap))
+    if not header:
+        return segs
+    hdr = native().jpeg_header(w, h, int(quality), samp)
+    return [None if s is None else hdr + s + b"\xff\xd9" for s in segs]
+
+
+def render_overlay(raw, label, border, spacing=(1.0, 1.0), out_w=512, out_h=512, pixel_type="u16", stored_bits=16,
+                   slope=1.0, intercept=0.0, nearest=False, fill_a=153, border_a=255, color=(0, 255, 0)):
+    """Overlay render (K3): the gray render of raw [N,H,W] (16-bit storage; window = each slice's
+    min/max) with `color` blended over it at 8-bit opacity `border_a` where `border` is set, else
+    `fill_a` where `label` is set (bool [N,H,W], sampled nearest) → uint8 [N, out_h, out_w, 3]."""
+    x = _as3d(raw)
+    _check(x, _U16, "raw")
+    lab, brd = _as3d(label), _as3d(border)
+    if lab.shape != x.shape or brd.shape != x.shape or not lab.is_cuda or not brd.is_cuda:
+        raise ValueError("label and border must be CUDA tensors of raw's shape")
+    n, h, w = x.shape
+    # Raw keys (pixel_math.h key_from_raw): unsigned data masked to stored_bits, signed data
+    # sign-extended and offset by 0x8000; their per-slice range is the render window.
+    v = x.view(torch.int16).to(torch.int32)
+    sh = 16 - int(stored_bits)
+    if pixel_type == "i16":
+        keys = (((v << (16 + sh)) >> (16 + sh)) + 0x8000) & 0xFFFF
+    else:
+        keys = (v & 0xFFFF) & (0xFFFF >> sh)
+    kmin = [int(k) for k in keys.reshape(n, -1).min(dim=1).values.tolist()]
+    kmax = [int(k) for k in keys.reshape(n, -1).max(dim=1).values.tolist()]
+    planes = torch.stack([pack_bits(lab.bool()), pack_bits(brd.bool())]).contiguous()
+    out = torch.empty((n, int(out_h), int(out_w), 3), dtype=torch.uint8, device=x.device)
+    native().k_render_overlay(x.data_ptr(), planes.data_ptr(), out.data_ptr(), n, h, w, pixel_type, int(stored_bits),
+                              float(slope), float(intercept), float(spacing[0]), float(spacing[1]), int(out_w), int(out_h),
+                              bool(nearest), int(fill_a), int(border_a), [int(c) for c in color], kmin, kmax, _stream())
+    return out if raw.dim() == 3 else out[0]

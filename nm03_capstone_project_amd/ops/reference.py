@@ -166,6 +166,48 @@ def render_labels(label, brd, fill=153, border_value=255, out_w=512, out_h=512):
     return torch.where(inside, out, torch.zeros_like(out))
 
 
+def overlay(values, lo, hi, label, brd, spacing=(1.0, 1.0), out_w=512, out_h=512, nearest=False, fill_a=153,
+            border_a=255, color=(0, 255, 0)):
+    """Overlay canvas [out_h, out_w, 3] uint8: the gray render of `values` [H, W] (window [lo, hi])
+    with `color` blended over it per channel as (a·C + (255 − a)·g + 127) // 255 in integers, where
+    a = border_a under a set `brd` pixel, else fill_a under a set `label` pixel, else 0 (both bool
+    [H, W], sampled nearest). The slice is fitted to the canvas preserving its physical aspect
+    (`spacing` = (x, y) mm per pixel) and centred; pixels outside it stay black."""
+    h, w = values.shape
+    dev = values.device
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)
+    spx, spy = (float(torch.tensor(s, dtype=torch.float32)) for s in spacing)
+    ew, eh = w * spx, h * spy
+    scale = min(out_w / ew, out_h / eh)
+    dw, dh = ew * scale, eh * scale
+    ox, oy = f32((out_w - dw) * 0.5), f32((out_h - dh) * 0.5)
+    invx, invy = f32(w / dw), f32(h / dh)
+    sx = ((torch.arange(out_w, device=dev, dtype=torch.float32) + 0.5) - ox) * invx
+    sy = ((torch.arange(out_h, device=dev, dtype=torch.float32) + 0.5) - oy) * invy
+    inside = ((sx >= 0) & (sx < w))[None, :] & ((sy >= 0) & (sy < h))[:, None]
+    xn, yn = torch.floor(sx).long().clamp(0, w - 1), torch.floor(sy).long().clamp(0, h - 1)
+    v = values.float()
+    if nearest:
+        val = v[yn][:, xn]
+    else:
+        fx, fy = sx - 0.5, sy - 0.5
+        x0, y0 = torch.floor(fx), torch.floor(fy)
+        wx, wy = (fx - x0)[None, :], (fy - y0)[:, None]
+        xa, xb = x0.long().clamp(0, w - 1), (x0.long() + 1).clamp(0, w - 1)
+        ya, yb = y0.long().clamp(0, h - 1), (y0.long() + 1).clamp(0, h - 1)
+        top = (1 - wx) * v[ya][:, xa] + wx * v[ya][:, xb]
+        bot = (1 - wx) * v[yb][:, xa] + wx * v[yb][:, xb]
+        val = (1 - wy) * top + wy * bot
+    inv = f32(1.0) / f32(hi - lo) if hi > lo else f32(0.0)
+    g = torch.floor(((val - lo) * inv).clamp(0, 1) * 255 + 0.5).to(torch.int32)
+    a = torch.where(brd.bool()[yn][:, xn], border_a, torch.where(label.bool()[yn][:, xn], fill_a, 0)).to(torch.int32)
+    g = torch.where(inside, g, torch.zeros_like(g))
+    a = torch.where(inside, a, torch.zeros_like(a))
+    c = torch.tensor([int(k) for k in color], dtype=torch.int32, device=dev)
+    out = (a[..., None] * c + (255 - a[..., None]) * g[..., None] + 127) // 255
+    return out.to(torch.uint8)
+
+
 def psnr(a, b):
     mse = ((a.double() - b.double()) ** 2).mean().item()
     return math.inf if mse == 0 else 10 * math.log10(255.0 ** 2 / mse)

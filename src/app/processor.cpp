@@ -56,6 +56,9 @@ void usage(const std::string& which) {
             << "  --render-filter bilinear|nearest  interpolation of the gray renders (default bilinear)\n"
             << "  --quality Q            JPEG quality (default 75)\n"
             << "  --jpeg-sampling 420|444|gray  JPEG component layout: YCbCr 4:2:0 (default), 4:4:4, one gray component\n"
+            << "  --overlay              also export the colour overlay (original + dilated mask): <stem>_overlay.jpg,\n"
+            << "                         test_pipeline: overlay.jpg (needs --jpeg-sampling 420 or 444; 2D only)\n"
+            << "  --overlay-color R,G,B  label colour of the overlay, three values 0..255 (default 0,255,0)\n"
             << "  --mode 2d|3d           3d: whole series as a volume (SRG 6-conn + cube dilation)\n"
             << "  --split-volume         3d: each volume split into z-slabs over all ranks (halo exchange)\n"
             << "  --input FILE           test_pipeline: slice to process\n"
@@ -237,10 +240,43 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
       c.engine.pipe.se_shape = v == "disc" ? kSeDisc : kSeSquare;
     }
     else if (a == "--split-volume") c.split_volume = true;
+    else if (a == "--overlay") c.engine.render.overlay = true;
+    else if (a == "--overlay-color") {
+      // Exactly three decimal values 0..255 separated by commas.
+      const std::string v = val();
+      int rgb[3] = {0, 0, 0}, n = 0;
+      bool ok = !v.empty();
+      size_t pos = 0;
+      while (ok && n < 3) {
+        size_t end = pos;
+        while (end < v.size() && std::isdigit((unsigned char)v[end])) ++end;
+        ok = end > pos && end - pos <= 3;
+        if (!ok) break;
+        rgb[n] = std::atoi(v.substr(pos, end - pos).c_str());
+        ok = rgb[n] <= 255;
+        ++n;
+        if (n < 3) ok = ok && end < v.size() && v[end] == ',';
+        pos = end + 1;
+        if (n == 3) ok = ok && end == v.size();
+      }
+      if (!ok || n != 3) {
+        std::cerr << "--overlay-color must be R,G,B with three values 0..255" << std::endl;
+        std::exit(2);
+      }
+      for (int k = 0; k < 3; ++k) c.engine.render.overlay_color[k] = (uint8_t)rgb[k];
+    }
     else {
       std::cerr << "unknown option " << a << " (see --help)" << std::endl;
       std::exit(2);
     }
+  }
+  if (c.engine.render.overlay && c.engine.render.jpeg_sampling == jpeg::kSamplingGray) {
+    std::cerr << "--overlay needs --jpeg-sampling 420 or 444: a one-component gray file cannot carry colour" << std::endl;
+    std::exit(2);
+  }
+  if (c.engine.render.overlay && c.mode == "3d") {
+    std::cerr << "--overlay is not available with --mode 3d" << std::endl;
+    std::exit(2);
   }
   // HW queues of the process, set before anything initialises HIP (rank processes inherit it).
   // Every stream past the first costs a new HW queue (≈ 9 ms cold) until GPU_MAX_HW_QUEUES is
@@ -1099,6 +1135,7 @@ int run_test_pipeline(const AppConfig& cfg) {
       SingleResult r = engine->run_single(in);
       canvases = std::move(r.canvases);
       jpegs = std::move(r.jpegs);
+      if (rp.overlay) jpegs.push_back(std::move(r.jpeg_overlay));
       d_sharp = std::move(r.sharpened);
       d_masks = {std::move(r.band), std::move(r.region), std::move(r.eroded), std::move(r.dilated)};
     }
@@ -1120,6 +1157,10 @@ int run_test_pipeline(const AppConfig& cfg) {
     for (int k = 0; k < 5; ++k) {
       std::ofstream f(cfg.out_dir + "/" + names[k] + ".jpg", std::ios::binary | std::ios::trunc);
       f.write((const char*)jpegs[k].data(), (std::streamsize)jpegs[k].size());
+    }
+    if (rp.overlay) {  // --overlay: the sixth stage image, the original with the dilated mask over it (colour)
+      std::ofstream f(cfg.out_dir + "/overlay.jpg", std::ios::binary | std::ios::trunc);
+      f.write((const char*)jpegs.at(5).data(), (std::streamsize)jpegs.at(5).size());
     }
     if (cfg.montage) {
       // Headless MultiViewWindow(5, Black, ...): the five views side by side.

@@ -59,6 +59,7 @@ int main(int argc, char** argv) {
       const std::string s = v();
       ec.render.jpeg_sampling = s == "gray" ? 2 : s == "444" ? 1 : 0;
     }
+    else if (a == "--overlay") ec.render.overlay = true;  // cohort: also the colour overlay per slice
     else if (a == "--se-shape") ec.pipe.se_shape = v() == "disc" ? nm03::kSeDisc : nm03::kSeSquare;
     else if (a == "--render-filter") ec.render.filter = v() == "nearest" ? nm03::kFilterNearest : nm03::kFilterBilinear;
     else {

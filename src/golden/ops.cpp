@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 #include <deque>
+#include <stdexcept>
 
 #include "nm03/dicom.h"
 #include "nm03/golden.h"
@@ -377,6 +378,26 @@ std::vector<uint8_t> render_labels(const std::vector<uint8_t>& label, const std:
   return out;
 }
 
+std::vector<uint8_t> render_overlay(const std::vector<float>& values, const std::vector<uint8_t>& label,
+                                    const std::vector<uint8_t>& bm, const RenderGeom& g, float lo, float hi, bool nearest,
+                                    uint8_t fill_a, uint8_t border_a, const uint8_t* color) {
+  // The two gray renders are the overlay's inputs by definition: the original canvas is the
+  // background and the label canvas (border_a / fill_a / 0) is the per-pixel opacity.
+  const std::vector<uint8_t> gray = render_gray(values, g, lo, hi, nearest);
+  const std::vector<uint8_t> alpha = render_labels(label, bm, g, fill_a, border_a);
+  std::vector<uint8_t> out(gray.size() * 3);
+  for (size_t i = 0; i < gray.size(); ++i)
+    for (int c = 0; c < 3; ++c) out[3 * i + c] = overlay_blend(gray[i], color[c], alpha[i]);
+  return out;
+}
+
+namespace {
+void check_overlay(const RenderParams& rp) {
+  if (rp.overlay && rp.jpeg_sampling == jpeg::kSamplingGray)
+    throw std::invalid_argument("overlay needs a YCbCr JPEG layout (4:2:0 or 4:4:4), not gray");
+}
+}  // namespace
+
 SliceResult run(const SliceInput& s, const PipelineParams& p, bool with_erosion) {
   SliceResult r;
   r.clipped = norm_clip(s, p);
@@ -403,6 +424,13 @@ SliceJpegs export_jpegs(const SliceInput& s, const SliceResult& r, const Pipelin
   std::vector<uint8_t> c1 =
       render_labels(r.dilated, bm, g, opacity_u8(rp.label_opacity), opacity_u8(rp.border_opacity));
   j.processed = jpeg::encode_gray(c1.data(), g.out_w, g.out_h, g.out_w, rp.jpeg_quality, (jpeg::Sampling)rp.jpeg_sampling);
+  if (rp.overlay) {
+    check_overlay(rp);
+    j.overlay_canvas = render_overlay(rescaled(s, p), r.dilated, bm, g, r.window_lo, r.window_hi, rp.filter == kFilterNearest,
+                                      opacity_u8(rp.label_opacity), opacity_u8(rp.border_opacity), rp.overlay_color);
+    j.overlay = jpeg::encode_rgb(j.overlay_canvas.data(), g.out_w, g.out_h, 3 * g.out_w, rp.jpeg_quality,
+                                 (jpeg::Sampling)rp.jpeg_sampling);
+  }
   return j;
 }
 
@@ -422,6 +450,13 @@ StageImages test_pipeline_images(const SliceInput& in, const PipelineParams& p, 
   c.push_back(render_labels(r.dilated, border(r.dilated, in.w, in.h, rp.border_radius), g, fill, bv));
   for (auto& cv : c) out.jpegs.push_back(jpeg::encode_gray(cv.data(), rp.out_width, rp.out_height, rp.out_width,
                                                             rp.jpeg_quality, (jpeg::Sampling)rp.jpeg_sampling));
+  if (rp.overlay) {
+    check_overlay(rp);
+    c.push_back(render_overlay(rescaled(in, p), r.dilated, border(r.dilated, in.w, in.h, rp.border_radius), g, r.window_lo,
+                               r.window_hi, nearest, fill, bv, rp.overlay_color));
+    out.jpegs.push_back(jpeg::encode_rgb(c.back().data(), rp.out_width, rp.out_height, 3 * rp.out_width, rp.jpeg_quality,
+                                         (jpeg::Sampling)rp.jpeg_sampling));
+  }
   if (stages) *stages = std::move(r);
   return out;
 }

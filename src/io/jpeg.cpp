@@ -150,9 +150,10 @@ std::vector<uint8_t> make_header(int width, int height, const Tables& t, Samplin
 
 namespace {
 
-// Luma block (bx, by) of the gray plane, edge-replicated past the image (libjpeg's
-// expand_right_edge and bottom-row replication), transformed and quantised into zig-zag order.
-void luma_block(const uint8_t* gray, int width, int height, int stride, int bx, int by, const Tables& t, int16_t* zz) {
+// Block (bx, by) of an 8-bit plane, edge-replicated past the image (libjpeg's expand_right_edge and
+// bottom-row replication), transformed and quantised with the divisors `div` into zig-zag order.
+// luma_block is the same for the gray plane with the luma divisors.
+void plane_block(const uint8_t* gray, int width, int height, int stride, int bx, int by, const int32_t* div, int16_t* zz) {
   int32_t blk[64];
   for (int r = 0; r < 8; ++r) {
     const int y = by * 8 + r < height ? by * 8 + r : height - 1;
@@ -162,7 +163,10 @@ void luma_block(const uint8_t* gray, int width, int height, int stride, int bx, 
     }
   }
   fdct_islow(blk);
-  for (int k = 0; k < 64; ++k) zz[k] = quantize(blk[kNatural[k]], t.div_luma[kNatural[k]]);
+  for (int k = 0; k < 64; ++k) zz[k] = quantize(blk[kNatural[k]], div[kNatural[k]]);
+}
+void luma_block(const uint8_t* gray, int width, int height, int stride, int bx, int by, const Tables& t, int16_t* zz) {
+  plane_block(gray, width, height, stride, bx, by, t.div_luma, zz);
 }
 
 }  // namespace
@@ -220,6 +224,84 @@ std::vector<uint8_t> encode_gray(const uint8_t* gray, int width, int height, int
   Tables t = make_tables(quality);
   std::vector<uint8_t> f = make_header(width, height, t, s);
   std::vector<uint8_t> sc = encode_scan_gray(gray, width, height, stride, t, s);
+  f.insert(f.end(), sc.begin(), sc.end());
+  f.push_back(0xFF);
+  f.push_back(0xD9);
+  return f;
+}
+
+std::vector<uint8_t> encode_scan_rgb(const uint8_t* rgb, int width, int height, int stride, const Tables& t, Sampling s) {
+  if (s != kSampling420 && s != kSampling444) throw std::invalid_argument("encode_rgb: a colour image needs 4:2:0 or 4:4:4");
+  if (width <= 0 || height <= 0) throw std::invalid_argument("encode_rgb: empty image");
+  // Colour conversion at full resolution (jpeg_common.h), then the chroma planes the scan reads.
+  std::vector<uint8_t> py((size_t)width * height), pcb(py.size()), pcr(py.size());
+  for (int y = 0; y < height; ++y)
+    for (int x = 0; x < width; ++x) {
+      const uint8_t* p = rgb + (size_t)y * stride + 3 * x;
+      const size_t i = (size_t)y * width + x;
+      py[i] = (uint8_t)rgb_to_y(p[0], p[1], p[2]);
+      pcb[i] = (uint8_t)rgb_to_cb(p[0], p[1], p[2]);
+      pcr[i] = (uint8_t)rgb_to_cr(p[0], p[1], p[2]);
+    }
+  std::vector<uint8_t> out;
+  out.reserve((size_t)width * height / 4);
+  BitWriter w(out);
+  const int bw = (width + 7) / 8, bh = (height + 7) / 8;
+  int last_dc_y = 0, last_dc_cb = 0, last_dc_cr = 0;
+  int16_t zz[64];
+  if (s == kSampling444) {
+    for (int by = 0; by < bh; ++by)
+      for (int bx = 0; bx < bw; ++bx) {
+        plane_block(py.data(), width, height, width, bx, by, t.div_luma, zz);
+        encode_block(w, zz, last_dc_y, kHuffDcLuma, kHuffAcLuma);
+        plane_block(pcb.data(), width, height, width, bx, by, t.div_chroma, zz);
+        encode_block(w, zz, last_dc_cb, kHuffDcChroma, kHuffAcChroma);
+        plane_block(pcr.data(), width, height, width, bx, by, t.div_chroma, zz);
+        encode_block(w, zz, last_dc_cr, kHuffDcChroma, kHuffAcChroma);
+      }
+    w.flush();
+    return out;
+  }
+  // 4:2:0: chroma planes of whole blocks in x (columns replicated at full resolution before the
+  // 2×2 mean) and ceil(h/2) rows (plane_block replicates the last downsampled row below them).
+  const int mcux = (width + 15) / 16, mcuy = (height + 15) / 16;
+  const int cw = mcux * 8, ch = (height + 1) / 2;
+  std::vector<uint8_t> dcb((size_t)cw * ch), dcr(dcb.size());
+  for (int cy = 0; cy < ch; ++cy) {
+    const size_t r0 = (size_t)(2 * cy) * width, r1 = (size_t)(2 * cy + 1 < height ? 2 * cy + 1 : height - 1) * width;
+    for (int cx = 0; cx < cw; ++cx) {
+      const int x0 = 2 * cx < width ? 2 * cx : width - 1, x1 = 2 * cx + 1 < width ? 2 * cx + 1 : width - 1;
+      dcb[(size_t)cy * cw + cx] = (uint8_t)h2v2_sample(pcb[r0 + x0], pcb[r0 + x1], pcb[r1 + x0], pcb[r1 + x1], cx);
+      dcr[(size_t)cy * cw + cx] = (uint8_t)h2v2_sample(pcr[r0 + x0], pcr[r0 + x1], pcr[r1 + x0], pcr[r1 + x1], cx);
+    }
+  }
+  for (int my = 0; my < mcuy; ++my) {
+    for (int mx = 0; mx < mcux; ++mx) {
+      for (int sub = 0; sub < 4; ++sub) {
+        const int by = my * 2 + (sub >> 1), bx = mx * 2 + (sub & 1);
+        if (by < bh && bx < bw) {
+          plane_block(py.data(), width, height, width, bx, by, t.div_luma, zz);
+        } else {  // dummy block, as in encode_scan_gray
+          std::memset(zz, 0, sizeof(zz));
+          zz[0] = (int16_t)last_dc_y;
+        }
+        encode_block(w, zz, last_dc_y, kHuffDcLuma, kHuffAcLuma);
+      }
+      plane_block(dcb.data(), cw, ch, cw, mx, my, t.div_chroma, zz);
+      encode_block(w, zz, last_dc_cb, kHuffDcChroma, kHuffAcChroma);
+      plane_block(dcr.data(), cw, ch, cw, mx, my, t.div_chroma, zz);
+      encode_block(w, zz, last_dc_cr, kHuffDcChroma, kHuffAcChroma);
+    }
+  }
+  w.flush();
+  return out;
+}
+
+std::vector<uint8_t> encode_rgb(const uint8_t* rgb, int width, int height, int stride, int quality, Sampling s) {
+  if (s != kSampling420 && s != kSampling444) throw std::invalid_argument("encode_rgb: a colour image needs 4:2:0 or 4:4:4");
+  Tables t = make_tables(quality);
+  std::vector<uint8_t> f = make_header(width, height, t, s);
+  std::vector<uint8_t> sc = encode_scan_rgb(rgb, width, height, stride, t, s);
   f.insert(f.end(), sc.begin(), sc.end());
   f.push_back(0xFF);
   f.push_back(0xD9);

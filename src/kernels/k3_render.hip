@@ -43,6 +43,51 @@ void launch_render(const uint16_t* raw, const float* f32, const uint64_t* bits, 
   check_launch("render_kernel");
 }
 
+// Overlay (RenderParams::overlay): per canvas pixel the gray render's value g and the label render's
+// value a (border_value / fill / 0, used as the opacity) through the same render_pixel as the two
+// gray outputs, then overlay_blend per channel. Each thread produces 4 adjacent pixels = 12 bytes.
+__global__ __launch_bounds__(256) void render_overlay_kernel(const uint16_t* __restrict__ raw, const float* __restrict__ f32,
+                                                             const uint64_t* __restrict__ bits,
+                                                             const SliceStats* __restrict__ stats,
+                                                             const RenderDesc* __restrict__ rds, int gray_first,
+                                                             int label_first, int stride, int out_w, int out_h,
+                                                             uint32_t rgb_color, uint8_t* __restrict__ rgb) {
+  const RenderDesc dg = rds[gray_first + (int)blockIdx.y * stride];
+  const RenderDesc dl = rds[label_first + (int)blockIdx.y * stride];
+  const int qpr = out_w >> 2;
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  const int v = q / qpr;
+  if (v >= out_h) return;
+  const int u0 = (q - v * qpr) * 4;
+  const RWindow win = render_window(dg, stats);
+  uint8_t px[12];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint8_t g = (uint8_t)render_pixel(dg, raw, f32, bits, win, u0 + k, v);
+    const uint8_t a = (uint8_t)render_pixel(dl, raw, f32, bits, RWindow{0.f, 0.f}, u0 + k, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) px[3 * k + c] = overlay_blend(g, (uint8_t)(rgb_color >> (8 * c)), a);
+  }
+  uint32_t* dst = reinterpret_cast<uint32_t*>(rgb + (size_t)blockIdx.y * 3 * out_w * out_h + ((size_t)v * out_w + u0) * 3);
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    dst[k] = (uint32_t)px[4 * k] | ((uint32_t)px[4 * k + 1] << 8) | ((uint32_t)px[4 * k + 2] << 16) |
+             ((uint32_t)px[4 * k + 3] << 24);
+}
+
+void launch_render_overlay(const uint16_t* raw, const float* f32, const uint64_t* bits, const SliceStats* stats,
+                           const RenderDesc* rd, int gray_first, int label_first, int stride, int ncanvas, int out_w,
+                           int out_h, uint32_t rgb_color, uint8_t* rgb, hipStream_t stream) {
+  if (ncanvas <= 0) return;
+  if (out_w % 4) throw DeviceError("canvas width must be a multiple of 4");
+  if ((uintptr_t)rgb & 3u) throw DeviceError("launch_render_overlay: the RGB canvas must be 4-byte aligned");
+  const int quads = out_w / 4 * out_h;
+  dim3 grid((quads + 255) / 256, ncanvas);
+  render_overlay_kernel<<<grid, 256, 0, stream>>>(raw, f32, bits, stats, rd, gray_first, label_first, stride, out_w, out_h,
+                                                  rgb_color, rgb);
+  check_launch("render_overlay_kernel");
+}
+
 void preload_render() {
   hipFuncAttributes a;
   check_hip(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&render_kernel)), "preload render_kernel");

@@ -10,9 +10,12 @@
 #include <sys/mman.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <mutex>
 #include <thread>
+#include <vector>
 
 #include "nm03/app.h"
 #include "nm03/cohort.h"
@@ -270,7 +273,17 @@ PYBIND11_MODULE(_nm03, m) {
       .def_readwrite("border_radius", &RenderParams::border_radius)
       .def_readwrite("jpeg_quality", &RenderParams::jpeg_quality)
       .def_readwrite("filter", &RenderParams::filter)
-      .def_readwrite("jpeg_sampling", &RenderParams::jpeg_sampling);
+      .def_readwrite("jpeg_sampling", &RenderParams::jpeg_sampling)
+      .def_readwrite("overlay", &RenderParams::overlay)
+      .def_property(
+          "overlay_color",
+          [](const RenderParams& r) { return py::make_tuple(r.overlay_color[0], r.overlay_color[1], r.overlay_color[2]); },
+          [](RenderParams& r, const std::vector<int>& c) {
+            if (c.size() != 3) throw std::invalid_argument("overlay_color must have three values 0..255");
+            for (int v : c)
+              if (v < 0 || v > 255) throw std::invalid_argument("overlay_color must have three values 0..255");
+            for (int k = 0; k < 3; ++k) r.overlay_color[k] = (uint8_t)c[k];
+          });
   py::class_<EngineConfig>(m, "EngineConfig")
       .def(py::init<>())
       .def_readwrite("device", &EngineConfig::device)
@@ -577,6 +590,10 @@ PYBIND11_MODULE(_nm03, m) {
         golden::SliceJpegs j = golden::export_jpegs(s, r, p, rp);
         d["jpeg_original"] = py::bytes((const char*)j.original.data(), j.original.size());
         d["jpeg_processed"] = py::bytes((const char*)j.processed.data(), j.processed.size());
+        if (rp.overlay) {
+          d["overlay"] = to_np<uint8_t>(j.overlay_canvas, {rp.out_height, rp.out_width, 3});
+          d["jpeg_overlay"] = py::bytes((const char*)j.overlay.data(), j.overlay.size());
+        }
         return d;
       },
       py::arg("raw"), py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f,
@@ -653,6 +670,26 @@ PYBIND11_MODULE(_nm03, m) {
     return to_np<uint8_t>(golden::render_labels(from_np<uint8_t>(lab), from_np<uint8_t>(brd), g, (uint8_t)fill, (uint8_t)bv),
                           {out_h, out_w});
   });
+  m.def(
+      "golden_render_overlay",
+      [](py::array_t<float, py::array::c_style | py::array::forcecast> v,
+         py::array_t<uint8_t, py::array::c_style | py::array::forcecast> lab,
+         py::array_t<uint8_t, py::array::c_style | py::array::forcecast> brd, float lo, float hi, float sx, float sy,
+         int out_w, int out_h, bool nearest, int fill_a, int border_a, const std::vector<int>& color) {
+        const int h = (int)v.shape(0), w = (int)v.shape(1);
+        if (lab.ndim() != 2 || brd.ndim() != 2 || lab.shape(0) != h || lab.shape(1) != w || brd.shape(0) != h ||
+            brd.shape(1) != w)
+          throw std::invalid_argument("label and border must have the shape of values");
+        if (color.size() != 3) throw std::invalid_argument("color must have three values");
+        const uint8_t c[3] = {(uint8_t)color[0], (uint8_t)color[1], (uint8_t)color[2]};
+        RenderGeom g = make_render_geom(w, h, sx, sy, out_w, out_h);
+        return to_np<uint8_t>(golden::render_overlay(from_np<float>(v), from_np<uint8_t>(lab), from_np<uint8_t>(brd), g, lo,
+                                                     hi, nearest, (uint8_t)fill_a, (uint8_t)border_a, c),
+                              {out_h, out_w, 3});
+      },
+      py::arg("values"), py::arg("label"), py::arg("border"), py::arg("lo"), py::arg("hi"), py::arg("sx") = 1.f,
+      py::arg("sy") = 1.f, py::arg("out_w") = 512, py::arg("out_h") = 512, py::arg("nearest") = false,
+      py::arg("fill_a") = 153, py::arg("border_a") = 255, py::arg("color") = std::vector<int>{0, 255, 0});
   m.def("opacity_u8", &opacity_u8);
 
   // ---- JPEG --------------------------------------------------------------------------------------
@@ -669,6 +706,15 @@ PYBIND11_MODULE(_nm03, m) {
     auto b = jpeg::encode_gray(g.data(), w, h, w, quality, (jpeg::Sampling)sampling);
     return py::bytes((const char*)b.data(), b.size());
   }, py::arg("gray"), py::arg("quality") = 75, py::arg("sampling") = 0);
+  // Interleaved RGB [H, W, 3] → complete colour JFIF file (golden encoder; sampling 0 or 1).
+  m.def("jpeg_encode_rgb", [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> rgb, int quality,
+                              int sampling) {
+    if (rgb.ndim() != 3 || rgb.shape(2) != 3) throw std::invalid_argument("rgb must be [H, W, 3] uint8");
+    if (sampling != 0 && sampling != 1) throw std::invalid_argument("a colour image needs sampling 0 (4:2:0) or 1 (4:4:4)");
+    const int h = (int)rgb.shape(0), w = (int)rgb.shape(1);
+    auto b = jpeg::encode_rgb(rgb.data(), w, h, 3 * w, quality, (jpeg::Sampling)sampling);
+    return py::bytes((const char*)b.data(), b.size());
+  }, py::arg("rgb"), py::arg("quality") = 75, py::arg("sampling") = 0);
   m.def("jpeg_header", [](int w, int h, int quality, int sampling) {
     if (sampling < 0 || sampling > 2) throw std::invalid_argument("sampling must be 0, 1 or 2");
     auto b = jpeg::make_header(w, h, jpeg::make_tables(quality), (jpeg::Sampling)sampling);
@@ -829,6 +875,10 @@ PYBIND11_MODULE(_nm03, m) {
              for (auto& j : r.jpegs) jp.append(py::bytes((const char*)j.data(), j.size()));
              d["canvases"] = cv;
              d["jpegs"] = jp;
+             if (e.config().render.overlay) {
+               d["overlay"] = to_np<uint8_t>(r.overlay, {ch, cw, 3});
+               d["jpeg_overlay"] = py::bytes((const char*)r.jpeg_overlay.data(), r.jpeg_overlay.size());
+             }
              return d;
            },
            py::arg("raw"), py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f,
@@ -1193,6 +1243,132 @@ PYBIND11_MODULE(_nm03, m) {
     return res;
   }, py::arg("canvas"), py::arg("n"), py::arg("h"), py::arg("w"), py::arg("quality"), py::arg("stream"),
      py::arg("sampling") = 0);
+
+  // Colour encoder on RGB canvases [n, h, w, 3] (device pointer); `out_cap` bytes per image (0: the
+  // canvas size, which no baseline scan of 8-bit samples exceeds in practice). None for an image
+  // that overflowed.
+  m.def("k_jpeg_rgb", [](uintptr_t canvas, int n, int h, int w, int quality, uintptr_t stream, int sampling,
+                         uint32_t out_cap) {
+    hipStream_t st = as_stream(stream);
+    if (sampling != 0 && sampling != 1) throw std::invalid_argument("a colour image needs sampling 0 (4:2:0) or 1 (4:4:4)");
+    if (n <= 0 || h <= 0 || w <= 0 || h % 16 || w % 16) throw std::invalid_argument("canvas dims must be multiples of 16");
+    if ((size_t)n * h * w * 3 > 0xFFFFFFFFull) throw std::invalid_argument("canvases exceed 4 GiB");
+    {
+      // The colour encoder's code object, loaded on the current device before this op's first launch
+      // there (once per device: a process may use the op on several).
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_jpeg_rgb();
+        preloaded.push_back(dev);
+      }
+    }
+    if (!out_cap) out_cap = (uint32_t)((size_t)h * w * 3 + 1024);
+    out_cap = (out_cap + 15u) & ~15u;
+    std::vector<gpu::JpegDesc> jd(n);
+    for (int i = 0; i < n; ++i) {
+      std::memset(&jd[i], 0, sizeof(jd[i]));
+      jd[i].canvas_off = (uint32_t)((size_t)i * w * h * 3);
+      jd[i].out_off = (uint64_t)i * out_cap;
+      jd[i].out_cap = out_cap;
+      jd[i].render = -1;
+    }
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+      size_t o = off;
+      off += (bytes + 255) / 256 * 256;
+      return o;
+    };
+    const size_t look_cap = (size_t)n * gpu::jpeg_rgb_parts(w, h, sampling);
+    const size_t o_jd = take(sizeof(gpu::JpegDesc) * n), o_look = take(6 * look_cap * 8), o_ticket = take(4 * (size_t)n),
+                 o_spill = take(look_cap * 256 * 56 * 4), o_out = take((size_t)n * out_cap), o_sz = take((size_t)n * 4);
+    uint8_t* dev = (uint8_t*)scratch().get(off);
+    gpu::check_hip(hipMemcpyAsync(dev + o_jd, jd.data(), sizeof(gpu::JpegDesc) * n, hipMemcpyHostToDevice, st), "H2D");
+    gpu::check_hip(hipMemsetAsync(dev + o_ticket, 0, 4 * (size_t)n, st), "memset tickets");
+    gpu::check_hip(hipMemsetAsync(dev + o_look, 0, 6 * look_cap * 8, st), "memset look-back");
+    gpu::JpegWork wk;
+    wk.look = (uint64_t*)(dev + o_look);
+    wk.look_cap = look_cap;
+    wk.ticket = (uint32_t*)(dev + o_ticket);
+    wk.spill = (uint32_t*)(dev + o_spill);
+    const jpeg::Tables t = jpeg::make_tables(quality);
+    gpu::launch_jpeg_rgb((const uint8_t*)canvas, (const gpu::JpegDesc*)(dev + o_jd), n, w, h, t.div_luma, t.div_chroma, wk,
+                         dev + o_out, (int32_t*)(dev + o_sz), st, sampling);
+    std::vector<int32_t> sizes(n);
+    gpu::check_hip(hipMemcpyAsync(sizes.data(), dev + o_sz, 4 * n, hipMemcpyDeviceToHost, st), "D2H");
+    gpu::check_hip(hipStreamSynchronize(st), "k_jpeg_rgb");
+    py::list res;
+    for (int i = 0; i < n; ++i) {
+      if (sizes[i] < 0) {
+        res.append(py::none());
+        continue;
+      }
+      std::string b((size_t)sizes[i], '\0');
+      gpu::check_hip(hipMemcpy(b.data(), dev + o_out + (size_t)i * out_cap, sizes[i], hipMemcpyDeviceToHost), "D2H");
+      res.append(py::bytes(b));
+    }
+    return res;
+  }, py::arg("canvas"), py::arg("n"), py::arg("h"), py::arg("w"), py::arg("quality"), py::arg("stream"),
+     py::arg("sampling") = 0, py::arg("out_cap") = 0);
+  // Overlay render of n equally sized slices: raw [n, h, w] u16, planes [2, n, h, wpr] u64 words
+  // (label, then border), per-slice raw key range (the render window) → rgb [n, out_h, out_w, 3].
+  m.def("k_render_overlay", [](uintptr_t raw, uintptr_t planes, uintptr_t rgb, int n, int h, int w, const std::string& type,
+                               int stored_bits, float slope, float intercept, float sx, float sy, int out_w, int out_h,
+                               bool nearest, int fill_a, int border_a, const std::vector<int>& color,
+                               const std::vector<uint32_t>& key_min, const std::vector<uint32_t>& key_max, uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    if (n <= 0 || (int)key_min.size() != n || (int)key_max.size() != n) throw std::invalid_argument("one key range per slice");
+    if (color.size() != 3) throw std::invalid_argument("color must have three values");
+    if (out_w <= 0 || out_h <= 0 || out_w % 4) throw std::invalid_argument("canvas width must be a multiple of 4");
+    if (w <= 0 || h <= 0 || w > 0xFFFF || h > 0xFFFF) throw std::invalid_argument("bad slice size");
+    const PixelType pt = parse_type(type);
+    const int wpr = (w + 63) / 64;
+    const RenderGeom g = make_render_geom(w, h, sx, sy, out_w, out_h);
+    std::vector<gpu::RenderDesc> rd(2 * (size_t)n);
+    std::vector<gpu::SliceStats> stats(n);
+    for (int i = 0; i < n; ++i) {
+      gpu::RenderDesc r;
+      std::memset(&r, 0, sizeof(r));
+      r.kind = gpu::kRenderRawGray;
+      r.type = pt == kU8 ? kU16 : pt;
+      r.stored_bits = (uint8_t)stored_bits;
+      r.fill = (uint8_t)fill_a;
+      r.border_value = (uint8_t)border_a;
+      r.filter = nearest ? 1 : 0;
+      r.slice = (uint32_t)i;
+      r.src_w = (uint16_t)w;
+      r.src_h = (uint16_t)h;
+      r.wpr = (uint16_t)wpr;
+      r.ox = g.ox;
+      r.oy = g.oy;
+      r.invx = g.invx;
+      r.invy = g.invy;
+      r.slope = slope;
+      r.intercept = intercept;
+      r.src_off = (uint32_t)((size_t)i * h * w);
+      rd[i] = r;
+      r.kind = gpu::kRenderLabels;
+      r.src_off = (uint32_t)((size_t)i * h * wpr);
+      r.border_off = (uint32_t)(((size_t)n + i) * h * wpr);
+      rd[(size_t)n + i] = r;
+      stats[i] = gpu::SliceStats{key_min[i], key_max[i], 0xFFFFFFFFu, 0u};
+    }
+    const size_t o_rd = 0, o_st = (rd.size() * sizeof(gpu::RenderDesc) + 255) / 256 * 256,
+                 total = o_st + stats.size() * sizeof(gpu::SliceStats);
+    std::vector<uint8_t> blob(total);
+    std::memcpy(blob.data() + o_rd, rd.data(), rd.size() * sizeof(gpu::RenderDesc));
+    std::memcpy(blob.data() + o_st, stats.data(), stats.size() * sizeof(gpu::SliceStats));
+    uint8_t* dev = (uint8_t*)scratch().get(total);
+    gpu::check_hip(hipMemcpyAsync(dev, blob.data(), total, hipMemcpyHostToDevice, st), "H2D tables");
+    gpu::check_hip(hipStreamSynchronize(st), "sync tables");
+    const uint32_t col = (uint32_t)(color[0] & 255) | ((uint32_t)(color[1] & 255) << 8) | ((uint32_t)(color[2] & 255) << 16);
+    gpu::launch_render_overlay((const uint16_t*)raw, nullptr, (const uint64_t*)planes, (const gpu::SliceStats*)(dev + o_st),
+                               (const gpu::RenderDesc*)(dev + o_rd), 0, n, 1, n, out_w, out_h, col, (uint8_t*)rgb, st);
+    gpu::check_hip(hipStreamSynchronize(st), "k_render_overlay");
+  });
 
   // ---- comm self-tests (CPU) ------------------------------------------------------------------------
   m.def("loopback_selftest", [](int n) {

@@ -152,6 +152,17 @@ struct Slot {
   // h_blob / h_out / h_sizes live in the engine's pinned arenas (freed with the engine, not here).
   bool arena = false;
   size_t out_bytes = 0;
+  // Overlay export (RenderParams::overlay; all null without it): RGB canvas c of the batch's slice c,
+  // the colour encoder's own work area and host-mapped output (slice c at c × ov_cap), and its
+  // JPEG descriptors, which depend on the slot alone and are uploaded once. (Kept behind every other
+  // member: the loaders' atomics above stay on the cache lines they were measured on.)
+  uint8_t* d_rgb = nullptr;
+  JpegWork ov_jw;
+  uint8_t* h_ov_out = nullptr;
+  uint8_t* d_ov_out = nullptr;
+  int32_t* h_ov_sizes = nullptr;
+  int32_t* d_ov_sizes = nullptr;
+  JpegDesc* d_ov_jd = nullptr;
 };
 
 // Private fd tables for the host pool's workers. Every open and
@@ -220,6 +231,10 @@ void hip_free_all(Slot& s) {
     if (s.h_sizes) (void)hipHostFree(s.h_sizes);
   }
   if (s.h_single) (void)hipHostFree(s.h_single);
+  if (s.h_ov_out) (void)hipHostFree(s.h_ov_out);
+  if (s.h_ov_sizes) (void)hipHostFree(s.h_ov_sizes);
+  for (void* p : {(void*)s.d_rgb, (void*)s.ov_jw.look, (void*)s.ov_jw.ticket, (void*)s.ov_jw.spill, (void*)s.d_ov_jd})
+    if (p) (void)hipFree(p);
   for (void* p : {(void*)s.d_blob, (void*)s.d_raw_x, (void*)s.d_med, (void*)s.d_tile_mm, (void*)s.d_f32, (void*)s.d_bits, (void*)s.d_srg_scratch, (void*)s.d_canvas,
                   (void*)s.jw.look, (void*)s.jw.ticket, (void*)s.jw.spill})
     if (p) (void)hipFree(p);
@@ -291,6 +306,14 @@ struct Engine::Impl {
     out_cap_ = cfg.jpeg_out_cap ? std::max<uint32_t>(64, cfg.jpeg_out_cap)
                                 : (uint32_t)std::max<size_t>(32 * 1024, (size_t)cfg.render.out_width * cfg.render.out_height * 3 / 8) + 64;
     out_cap_ = (out_cap_ + 15u) & ~15u;  // 16-byte aligned segments (the encoder's dwordx4 stores)
+    overlay_ = cfg.render.overlay;
+    if (overlay_ && cfg.host_only)
+      throw std::invalid_argument("overlay is rendered and encoded on the GPU: not available with host_only");
+    if (overlay_ && cfg.render.jpeg_sampling == jpeg::kSamplingGray)
+      throw std::invalid_argument("overlay needs a YCbCr JPEG layout (jpeg_sampling 0 or 1): a gray file cannot carry colour");
+    ov_cap_ = cfg.jpeg_out_cap ? out_cap_ : (2 * (out_cap_ - 64) + 64 + 15u) & ~15u;
+    ov_color_ = (uint32_t)cfg.render.overlay_color[0] | ((uint32_t)cfg.render.overlay_color[1] << 8) |
+                ((uint32_t)cfg.render.overlay_color[2] << 16);
     upload_chunk_ = cfg.upload_chunk_kb < 0 ? (size_t)2 << 20 : (size_t)cfg.upload_chunk_kb << 10;
     host_only_ = cfg.host_only;
     if (host_only_) upload_chunk_ = 0;  // nothing to upload
@@ -324,6 +347,7 @@ struct Engine::Impl {
     pc.se_disc = p.se_shape == kSeDisc ? 1 : 0;
     jpeg::Tables t = jpeg::make_tables(cfg.render.jpeg_quality);
     for (int i = 0; i < 64; ++i) divs[i] = t.div_luma[i];
+    for (int i = 0; i < 64; ++i) divs_chroma_[i] = t.div_chroma[i];
     if (cfg.render.jpeg_sampling < jpeg::kSampling420 || cfg.render.jpeg_sampling > jpeg::kSamplingGray)
       throw std::invalid_argument("jpeg_sampling must be 0 (4:2:0), 1 (4:4:4) or 2 (gray)");
     jpeg_header = jpeg::make_header(cfg.render.out_width, cfg.render.out_height, t,
@@ -339,6 +363,9 @@ struct Engine::Impl {
       // there first (a no-op when the CLI's start-up thread already did it). The 2D engine never
       // launches the volume or threshold kernels.
       preload_kernels(/*with_volume=*/false);
+      // The colour encoder's code object only when this engine will launch it (a default run never
+      // loads it), and here — never lazily from a slot thread.
+      if (overlay_) preload_jpeg_rgb();
       d_lut_ = dmalloc<float>(kLutArenaFloats, "hipMalloc norm tables");
     }
     const double t1 = now_s();
@@ -662,6 +689,31 @@ struct Engine::Impl {
         check_hip(hipHostGetDevicePointer((void**)&s.d_sizes, s.h_sizes, 0), "hipHostGetDevicePointer sizes");
       }
       mark("mapped out");
+      if (overlay_) {
+        const int n = s.cap_slices;
+        s.d_rgb = dmalloc<uint8_t>(3 * canvas_bytes * n, "hipMalloc overlay canvases");
+        s.ov_jw.look_cap = (size_t)n * jpeg_rgb_parts(cw, ch, cfg.render.jpeg_sampling);
+        s.ov_jw.look = dmalloc<uint64_t>(6 * s.ov_jw.look_cap, "hipMalloc overlay look-back");
+        s.ov_jw.ticket = dmalloc<uint32_t>(n, "hipMalloc overlay tickets");
+        s.ov_jw.spill = dmalloc<uint32_t>(s.ov_jw.look_cap * 256 * 56, "hipMalloc overlay spill");
+        check_hip(hipMemsetAsync(s.ov_jw.look, 0, 6 * s.ov_jw.look_cap * sizeof(uint64_t), s.stream), "memset look-back");
+        check_hip(hipMemsetAsync(s.ov_jw.ticket, 0, sizeof(uint32_t) * n, s.stream), "memset tickets");
+        check_hip(hipHostMalloc((void**)&s.h_ov_out, (size_t)ov_cap_ * n, hipHostMallocMapped), "hipHostMalloc overlay out");
+        check_hip(hipHostGetDevicePointer((void**)&s.d_ov_out, s.h_ov_out, 0), "hipHostGetDevicePointer overlay out");
+        check_hip(hipHostMalloc((void**)&s.h_ov_sizes, sizeof(int32_t) * n, hipHostMallocMapped), "hipHostMalloc overlay sizes");
+        check_hip(hipHostGetDevicePointer((void**)&s.d_ov_sizes, s.h_ov_sizes, 0), "hipHostGetDevicePointer overlay sizes");
+        std::vector<JpegDesc> jd((size_t)n);
+        for (int c = 0; c < n; ++c) {
+          std::memset(&jd[(size_t)c], 0, sizeof(JpegDesc));
+          jd[(size_t)c].canvas_off = (uint32_t)(3 * canvas_bytes * c);
+          jd[(size_t)c].out_off = (uint64_t)c * ov_cap_;
+          jd[(size_t)c].out_cap = ov_cap_;
+          jd[(size_t)c].render = -1;
+        }
+        s.d_ov_jd = dmalloc<JpegDesc>((size_t)n, "hipMalloc overlay descriptors");
+        check_hip(hipMemcpy(s.d_ov_jd, jd.data(), sizeof(JpegDesc) * n, hipMemcpyHostToDevice), "H2D overlay descriptors");
+        mark("overlay");
+      }
     } catch (...) {
       hip_free_all(s);
       throw;
@@ -906,9 +958,11 @@ struct Engine::Impl {
     load_ns += (int64_t)((now_s() - t0) * 1e9);
   }
 
-  static bool outputs_exist(const WorkItem& w) {
+  // Every requested file of the item (the overlay too when it is on).
+  bool outputs_exist(const WorkItem& w) const {
     const std::string base = cohort::with_slash(w.out_dir) + cohort::stem(w.path);
-    return access((base + "_original.jpg").c_str(), F_OK) == 0 && access((base + "_processed.jpg").c_str(), F_OK) == 0;
+    return access((base + "_original.jpg").c_str(), F_OK) == 0 && access((base + "_processed.jpg").c_str(), F_OK) == 0 &&
+           (!overlay_ || access((base + "_overlay.jpg").c_str(), F_OK) == 0);
   }
 
   // ---- descriptor build + GPU enqueue --------------------------------------------------------
@@ -1116,6 +1170,14 @@ struct Engine::Impl {
     rsrc.nrd = ncanv;
     launch_jpeg(s.d_canvas, d_jd, ncanv, cw, ch, divs, s.jw, s.d_out, s.d_sizes, s.stream, &rsrc,
                 cfg.render.jpeg_sampling, cfg.render.filter == kFilterNearest && jpeg_fuses_nearest(cfg.render.jpeg_sampling));
+    if (overlay_) {
+      // Slice c's gray and dilated-label descriptors are rd[2c], rd[2c + 1] (export) or rd[0], rd[4]
+      // (test_pipeline): the overlay cannot drift from the two gray outputs.
+      launch_render_overlay(d_raw, s.d_f32, s.d_bits, d_stats, d_rd, 0, mode == 0 ? 1 : 4, mode == 0 ? 2 : 5, nl, cw, ch,
+                            ov_color_, s.d_rgb, s.stream);
+      launch_jpeg_rgb(s.d_rgb, s.d_ov_jd, nl, cw, ch, divs, divs_chroma_, s.ov_jw, s.d_ov_out, s.d_ov_sizes, s.stream,
+                      cfg.render.jpeg_sampling);
+    }
     check_hip(hipEventRecord(s.ev2, s.stream), "event");
     if (mark) mark->enq = now_s();
     wait_batch(s, s.ev2, t_enq, nl);
@@ -1152,6 +1214,19 @@ struct Engine::Impl {
               "canvas D2H");
     jpeg::Tables t = jpeg::make_tables(cfg.render.jpeg_quality);
     fallback = jpeg::encode_scan_gray(canvas.data(), cw, ch, cw, t, (jpeg::Sampling)cfg.render.jpeg_sampling);
+    if (fallbacks) ++*fallbacks;
+    return false;
+  }
+
+  // Overlay image of the batch's slice c: true when the GPU segment in h_ov_out is valid, else the
+  // host re-encode of its RGB canvas in `fallback` (capacity overflow, as jpeg_segment).
+  bool overlay_segment(Slot& s, int c, std::vector<uint8_t>& fallback, int64_t* fallbacks) {
+    if (s.h_ov_sizes[c] >= 0) return true;
+    const int cw = cfg.render.out_width, ch = cfg.render.out_height;
+    std::vector<uint8_t> rgb((size_t)cw * ch * 3);
+    check_hip(hipMemcpy(rgb.data(), s.d_rgb + (size_t)c * rgb.size(), rgb.size(), hipMemcpyDeviceToHost), "overlay D2H");
+    jpeg::Tables t = jpeg::make_tables(cfg.render.jpeg_quality);
+    fallback = jpeg::encode_scan_rgb(rgb.data(), cw, ch, 3 * cw, t, (jpeg::Sampling)cfg.render.jpeg_sampling);
     if (fallbacks) ++*fallbacks;
     return false;
   }
@@ -1254,6 +1329,15 @@ struct Engine::Impl {
           status[item] = SliceStatus{kSliceExportError, e.what()};
         }
       }
+      std::vector<std::vector<uint8_t>> ofb(overlay_ ? s.live.size() : 0);
+      std::vector<char> use_ofb(ofb.size(), 0);
+      for (size_t c = 0; c < ofb.size(); ++c) {
+        try {
+          use_ofb[c] = !overlay_segment(s, (int)c, ofb[c], &fallbacks);
+        } catch (const std::exception& e) {
+          status[first + s.live[c]] = SliceStatus{kSliceExportError, e.what()};
+        }
+      }
       // Export order: round-robin over the batch's output directories, so the pool's concurrent
       // writers spread over several patient directories. Creating a file takes its directory's
       // lock exclusively; in slice order every writer would create in the same directory.
@@ -1311,6 +1395,13 @@ struct Engine::Impl {
                 const uint8_t* seg = use_fb[cv] ? fb[cv].data() : jpeg_bytes(s, cv);
                 const size_t len = use_fb[cv] ? fb[cv].size() : (size_t)s.h_sizes[cv];
                 jpeg::write_jpeg_at(AT_FDCWD, std::string(), name, jpeg_header, seg, len,
+                                    &dirs.creating[dirs.out_dir[item]]);
+                bytes_out += (int64_t)(jpeg_header.size() + len + 2);
+              }
+              if (overlay_) {
+                const uint8_t* seg = use_ofb[c] ? ofb[c].data() : s.h_ov_out + c * (size_t)ov_cap_;
+                const size_t len = use_ofb[c] ? ofb[c].size() : (size_t)s.h_ov_sizes[c];
+                jpeg::write_jpeg_at(AT_FDCWD, std::string(), base + "_overlay.jpg", jpeg_header, seg, len,
                                     &dirs.creating[dirs.out_dir[item]]);
                 bytes_out += (int64_t)(jpeg_header.size() + len + 2);
               }
@@ -1648,8 +1739,30 @@ struct Engine::Impl {
       f.push_back(0xD9);
       r.jpegs.push_back(std::move(f));
     }
+    if (overlay_) {
+      r.overlay.resize(3 * cvb);
+      check_hip(hipMemcpy(r.overlay.data(), s.d_rgb, r.overlay.size(), hipMemcpyDeviceToHost), "overlay D2H");
+      std::vector<uint8_t> fb;
+      const bool gpu_ok = overlay_segment(s, 0, fb, nullptr);
+      r.jpeg_overlay = jpeg_header;
+      if (gpu_ok)
+        r.jpeg_overlay.insert(r.jpeg_overlay.end(), s.h_ov_out, s.h_ov_out + s.h_ov_sizes[0]);
+      else
+        r.jpeg_overlay.insert(r.jpeg_overlay.end(), fb.begin(), fb.end());
+      r.jpeg_overlay.push_back(0xFF);
+      r.jpeg_overlay.push_back(0xD9);
+    }
     return r;
   }
+
+  // Overlay export (RenderParams::overlay): host-mapped bytes per overlay image — twice the gray
+  // capacity, 3/4 of the canvas (a colour file codes 1.5× the blocks, and its chroma is not flat) —
+  // unless EngineConfig::jpeg_out_cap sets both; the chroma divisors; the label colour as R | G << 8 | B << 16.
+  // (The last members of Impl: every other member keeps its offset.)
+  bool overlay_ = false;
+  uint32_t ov_cap_ = 0;
+  int32_t divs_chroma_[64] = {};
+  uint32_t ov_color_ = 0;
 };
 
 Engine::Engine(const EngineConfig& cfg) : impl_(std::make_unique<Impl>(cfg)) {}
