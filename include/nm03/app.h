@@ -71,7 +71,7 @@ struct AppConfig {
   // omp_set_num_threads(16) uses the whole laptop (main_parallel.cpp:401); N ≥ 1: exactly N.
   int gpus = -1;
   bool quiet = false;
-  bool cpu = false;        // test_pipeline: golden CPU path (BASELINE config 1)
+  bool cpu = false;        // golden CPU path: test_pipeline (BASELINE config 1), --mode 3d, the 2D cohort CLIs
   bool montage = true;     // test_pipeline: 5-view montage JPEG (headless MultiViewWindow)
   bool html = false;       // test_pipeline --html: the five views as a page (MultiViewWindow 2300×450)
   std::string json;        // metrics file
@@ -125,6 +125,24 @@ bool fast_exit_enabled();
 int run_sequential(const AppConfig& cfg);
 int run_parallel(const AppConfig& cfg);
 int run_test_pipeline(const AppConfig& cfg);
+
+// --measure (measurements.cpp): <out_root>/measurements.csv from the sidecars of the work list, in
+// patient / slice order: a header, one row per slice (patient, file, status, then the sidecar's
+// fields with bbox flattened; a slice without a sidecar has its status name and empty fields) and
+// one TOTAL row per patient with the summed area_px and area_mm2. Returns the job's totals.
+struct MeasurePatient {
+  std::string id, out_dir;
+  std::vector<std::string> files;  // the patient's slices, in order
+  std::vector<int32_t> status;     // SliceStatus::code of each
+};
+struct MeasureTotals {
+  int64_t slices = 0;  // slices with a sidecar
+  uint64_t area_px = 0;
+  double area_mm2 = 0;
+};
+MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients);
+std::string measure_totals_json(const MeasureTotals& t);  // the --json record's "measure" object
+const char* slice_status_name(int code);
 
 // Number of GPUs visible to this process, counted WITHOUT initialising HIP (KFD topology +
 // HIP/ROCR_VISIBLE_DEVICES), so the launcher can still fork safely afterwards.

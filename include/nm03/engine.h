@@ -67,13 +67,14 @@ struct EngineConfig {
   PipelineParams pipe;
   RenderParams render;
   bool export_jpeg = true;
-  bool resume = false;  // skip items whose requested JPEGs (two, three with render.overlay) all exist (SURVEY §5.4 --resume)
+  bool resume = false;  // skip items whose requested files (two JPEGs, three with render.overlay, the sidecar with pipe.measure) all exist (SURVEY §5.4 --resume)
   // Host path only: no HIP call at all. Every load, parse,
   // 12-bit pack into the (pageable) upload blob and every JPEG file write runs exactly as in a
   // GPU run; the GPU stages are replaced by streaming a fixed pair of pre-encoded JPEG segments
   // into the output buffer (what the encoder's PCIe stores would leave in memory). Measures the
   // host side's CPU per slice on its own, on any machine (bench.py --host-only).
-  // Not available with render.overlay (rendered and encoded on the GPU): the constructor throws.
+  // Not available with render.overlay (rendered and encoded on the GPU) or pipe.measure (measured on
+  // the GPU): the constructor throws.
   bool host_only = false;
   // Host-mapped bytes per image for the GPU encoder's stuffed output (0 = 3/8 of the canvas: 96 KiB
   // for 512² — full-contrast noise renders to 86.6 KB, a phantom slice to 14 KB; round 5 used half
@@ -121,6 +122,9 @@ struct SingleResult {
   std::vector<std::vector<uint8_t>> canvases, jpegs;
   // RenderParams::overlay only: the RGB canvas [out_h, out_w, 3] (original + dilated mask) and its file.
   std::vector<uint8_t> overlay, jpeg_overlay;
+  // PipelineParams::measure only: the K7 record of the dilated mask and its sidecar text (measure::to_json).
+  SliceMeasure measure{};
+  std::string measure_json;
 };
 
 struct RunHandle;  // a submitted run (Engine::submit)

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "nm03/common.h"
+#include "nm03/measure.h"
 #include "nm03/params.h"
 #include "nm03/pixel_math.h"
 
@@ -86,6 +87,14 @@ std::vector<uint8_t> render_labels(const std::vector<uint8_t>& label, const std:
 std::vector<uint8_t> render_overlay(const std::vector<float>& values, const std::vector<uint8_t>& label,
                                     const std::vector<uint8_t>& border_mask, const RenderGeom& g, float lo, float hi,
                                     bool nearest, uint8_t fill_a, uint8_t border_a, const uint8_t* color);
+
+// Measurements of a slice (PipelineParams::measure, nm03/measure.h): the record on the `dilated` plane
+// plus popcount(`region`), intensities from s.raw as stored_sample gives them. Flood-fill labelling;
+// holes by labelling the complement of the padded mask at the dual connectivity.
+SliceMeasure measure(const std::vector<uint8_t>& dilated, const std::vector<uint8_t>& region, const SliceInput& s,
+                     int connectivity);
+// The sidecar text of a record for slice `s` under `p` (measure::to_json with the slice's fields).
+std::string measure_json(const SliceMeasure& m, const SliceInput& s, const PipelineParams& p);
 
 struct SliceResult {
   std::vector<float> clipped, median, sharpened;

@@ -59,5 +59,8 @@ void write_jpeg_file(const std::string& path, const std::vector<uint8_t>& header
 void write_jpeg_at(int dirfd, const std::string& dir, const std::string& name, const std::vector<uint8_t>& header,
                    const uint8_t* scan, size_t scan_len,
                    std::atomic<uint8_t>* creating = nullptr);
+// The same open / overwrite-in-place path for a file of plain bytes (the --measure sidecars).
+void write_bytes_at(int dirfd, const std::string& dir, const std::string& name, const void* data, size_t len,
+                    std::atomic<uint8_t>* creating = nullptr);
 
 }  // namespace nm03::jpeg

@@ -8,6 +8,7 @@
 
 #include "nm03/common.h"
 #include "nm03/gpu_types.h"
+#include "nm03/measure.h"
 #include "nm03/pixel_math.h"
 
 namespace nm03::gpu {
@@ -167,6 +168,21 @@ void preload_jpeg_rgb();
 void launch_render_overlay(const uint16_t* raw, const float* f32, const uint64_t* bits, const SliceStats* stats,
                            const RenderDesc* rd, int gray_first, int label_first, int stride, int ncanvas, int out_w,
                            int out_h, uint32_t rgb_color, uint8_t* rgb, hipStream_t stream);
+
+// K7 (k7_measure.hip): per-slice measurements of the `dilated` plane plus popcount(`region`)
+// (nm03/measure.h), one workgroup per slice, slices of different sizes in one launch (SliceDesc::w, h,
+// wpr, mask_off, raw_off, type, stored_bits). `raw`: the expanded 16-bit samples at raw_off. `out`:
+// nslices records, written with plain vector stores (device or host-mapped memory). `scratch`: nslices ×
+// measure_scratch_words(max_w, max_h) words for the labelling's parents and areas, no initialisation
+// needed; max_w / max_h bound every slice of the launch (a slice that does not fit its share is not
+// measured and reports components = 0xFFFFFFFF). No host round trip, no allocation.
+size_t measure_scratch_words(int max_w, int max_h);
+void launch_measure(const uint64_t* dilated, const uint64_t* region, const uint16_t* raw, const SliceDesc* descs, int nslices,
+                    int connectivity, SliceMeasure* out, uint32_t* scratch, int max_w, int max_h, hipStream_t stream);
+// Loads K7's code object on the current device. Not part of preload_kernels: only an engine with
+// PipelineParams::measure (in its constructor) and the Python op (before its first launch) load it,
+// so a default run never pays for it — and no slot thread ever loads it lazily.
+void preload_measure();
 
 // K6: binary threshold lo ≤ x ≤ hi → u8 0/1 (in 16-byte aligned, out 4-byte aligned).
 void launch_threshold(const float* in, uint8_t* out, size_t n, float lo, float hi, hipStream_t stream);

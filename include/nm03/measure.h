@@ -1,0 +1,100 @@
+// nm03/measure.h — per-slice lesion measurements (--measure): the record the K7 kernel writes, the
+// bit-quad arithmetic shared by the kernel and the host (as pixel_math.h shares the pixel
+// arithmetic), and the one function that turns a record into the sidecar text.
+//
+// Everything in the record is an exact integer, measured on the DILATED plane (the mask that
+// `_processed.jpg` shows) plus the popcount of the region plane; the derived doubles (mm², centroid,
+// mean) exist only in to_json, which the engine, run_single, the --cpu paths and the Python binding
+// all call, so they cannot differ between the GPU path and the golden path.
+#pragma once
+
+#include <cstdint>
+#include <string>
+
+#include "nm03/common.h"
+
+namespace nm03 {
+
+struct alignas(64) SliceMeasure {
+  uint32_t area_px;          // popcount(dilated)
+  uint32_t region_px;        // popcount(region)
+  int32_t bbox[4];           // x0, y0, x1, y1 inclusive; all −1 for an empty mask
+  uint64_t sum_x, sum_y;     // coordinate sums over mask pixels (centroid = sum / area, on the host)
+  uint32_t perimeter_edges;  // 4-neighbour pixel edges between a mask pixel and a non-mask pixel or the frame
+  uint32_t components;       // connected components at the measurement connectivity (4 | 8)
+  uint32_t largest_px;       // area of the largest component
+  uint32_t holes;            // background components that do not reach the frame, at the dual connectivity
+  int64_t raw_sum;           // over the stored sample values under the mask (0 / 0 / 0 when empty)
+  int32_t raw_min, raw_max;
+};
+static_assert(sizeof(SliceMeasure) == 128, "SliceMeasure layout");
+
+// ---------------------------------------------------------------------------------------------
+// Bit quads (Gray 1971). Over every 2×2 window of the zero-padded mask, Q1 / Q3 count the windows
+// with exactly one / three set pixels and QD the two diagonal patterns. The Euler number
+// (components − holes, holes at the dual connectivity) is (Q1 − Q3 − 2·QD) / 4 at 8-connectivity and
+// (Q1 − Q3 + 2·QD) / 4 at 4-connectivity. A w × h mask has (w + 1) × (h + 1) windows; on bit planes
+// (LSB = left-most pixel) the window whose right column is pixel x sits at bit x.
+// ---------------------------------------------------------------------------------------------
+struct QuadCounts {
+  uint32_t q1 = 0, q3 = 0, qd = 0;
+};
+
+// 64 windows at once: bit x of tl / tr / bl / br is the window's top-left / top-right / bottom-left /
+// bottom-right pixel.
+NM03_HD void quad_accumulate(uint64_t tl, uint64_t tr, uint64_t bl, uint64_t br, QuadCounts& q) {
+  const uint64_t odd = tl ^ tr ^ bl ^ br;                 // one or three set
+  const uint64_t three = odd & ((tl & tr) | (bl & br));   // three set ⇔ odd and one row of the window full
+  q.q1 += (uint32_t)__builtin_popcountll(odd & ~three);
+  q.q3 += (uint32_t)__builtin_popcountll(three);
+  q.qd += (uint32_t)__builtin_popcountll((tl & br & ~tr & ~bl) | (tr & bl & ~tl & ~br));
+}
+
+// The windows of word k of one row pair: `u` / `l` are word k of the upper / lower row (0 for the
+// padding rows above and below the mask, and masked to the width in the last word), `u_prev` /
+// `l_prev` word k − 1 (0 for k = 0). `closes_row`: k is the last word and the width is a multiple of
+// 64, so the window right of the last pixel (bit 0 of a word that does not exist) is counted here.
+NM03_HD void quad_word(uint64_t u_prev, uint64_t u, uint64_t l_prev, uint64_t l, bool closes_row, QuadCounts& q) {
+  quad_accumulate((u << 1) | (u_prev >> 63), u, (l << 1) | (l_prev >> 63), l, q);
+  if (closes_row) quad_accumulate(u >> 63, 0ull, l >> 63, 0ull, q);
+}
+
+NM03_HD int64_t euler_from_quads(const QuadCounts& q, int connectivity) {
+  const int64_t d = 2 * (int64_t)q.qd;
+  return ((int64_t)q.q1 - (int64_t)q.q3 + (connectivity == 8 ? -d : d)) / 4;
+}
+
+// Mask of the valid bits of word k of a row of width w.
+NM03_HD uint64_t row_word_mask(int k, int w) {
+  const int rem = w - (k << 6);
+  return rem >= 64 ? ~0ull : (rem <= 0 ? 0ull : ((1ull << rem) - 1ull));
+}
+
+// Stored sample value as golden::SliceInput holds it: unsigned data masked to stored_bits, signed
+// data sign-extended from stored_bits.
+NM03_HD int32_t stored_sample(uint16_t raw_bits, uint8_t type, uint8_t stored_bits) {
+  const int sh = 16 - (int)stored_bits;
+  if (type == kI16) return (int32_t)(int16_t)((int16_t)(uint16_t)(raw_bits << sh) >> sh);
+  return (int32_t)(raw_bits & (uint16_t)(0xFFFFu >> sh));
+}
+
+namespace measure {
+
+// Euler number of a bit plane (h rows of wpr words, bits past w ignored) from the quad counts above.
+int64_t euler_plane(const uint64_t* plane, int w, int h, int wpr, int connectivity);
+
+// The sidecar text: one JSON object on one line plus '\n', keys in fixed order — the slice's width,
+// height and the connectivity, the record's integers (bbox as [x0, y0, x1, y1]), then the derived
+// doubles, each printed with %.9g:
+//   area_mm2 = area_px · spacing_x · spacing_y
+//   centroid_x / centroid_y = sum / area_px (pixel indices), centroid_*_mm = centroid · spacing
+//   mean = raw_sum / area_px, mapped through slope · v + intercept when apply_rescale
+// Centroids and mean are null for an empty mask.
+std::string to_json(const SliceMeasure& m, int w, int h, float spacing_x, float spacing_y, float slope, float intercept,
+                    bool apply_rescale, int connectivity);
+
+// File name of a slice's sidecar next to its JPEGs.
+inline std::string sidecar_name(const std::string& stem) { return stem + "_measure.json"; }
+
+}  // namespace measure
+}  // namespace nm03

@@ -42,6 +42,12 @@ struct PipelineParams {
   int min_dim = 100;
   // Apply DICOM modality rescale (slope/intercept) if present.
   bool apply_rescale = true;
+  // Per-slice measurements of the dilated mask (--measure, nm03/measure.h): <stem>_measure.json next
+  // to the JPEGs. Opt-in; components are counted at measure_connectivity (4 | 8), holes at its dual.
+  // (Two bytes in the padding after apply_rescale: the struct, and everything laid out after it in
+  // EngineConfig and the engine's state, keep their sizes and offsets.)
+  bool measure = false;
+  uint8_t measure_connectivity = 8;
   // Multi-frame files (dicom::select_frame): -1 rejects them (default), k ≥ 0 imports frame k.
   int frame = -1;
 };

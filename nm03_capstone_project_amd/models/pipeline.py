@@ -36,6 +36,8 @@ class PipelineConfig:
     apply_rescale: bool = True
     se_shape: int = 0  # structuring element of dilation/erosion: 0 square (default), 1 disc (params.h SeShape)
     frame: int = -1  # multi-frame DICOM: -1 rejects such files, k >= 0 imports frame k (dicom.h select_frame)
+    measure: bool = False  # also write <stem>_measure.json per slice; run_array / golden gain "measure", "measure_json"
+    measure_connectivity: int = 8  # components of the dilated mask counted 8- (default) or 4-connected; holes at the dual
     # render / export
     out_width: int = 512
     out_height: int = 512
@@ -59,7 +61,8 @@ class PipelineConfig:
 
     _PIPE = ("norm_low", "norm_high", "norm_min", "norm_max", "clip_min", "clip_max", "median_window",
              "sharpen_gain", "sharpen_sigma", "sharpen_mask", "srg_min", "srg_max", "srg_connectivity",
-             "dilation_size", "erosion_size", "min_dim", "apply_rescale", "frame", "se_shape")
+             "dilation_size", "erosion_size", "min_dim", "apply_rescale", "frame", "se_shape", "measure",
+             "measure_connectivity")
     _RENDER = ("out_width", "out_height", "label_opacity", "border_opacity", "border_radius", "jpeg_quality",
                "jpeg_sampling")
 

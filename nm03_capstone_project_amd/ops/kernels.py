@@ -196,3 +196,37 @@ def render_overlay(raw, label, border, spacing=(1.0, 1.0), out_w=512, out_h=512,
                               float(slope), float(intercept), float(spacing[0]), float(spacing[1]), int(out_w), int(out_h),
                               bool(nearest), int(fill_a), int(border_a), [int(c) for c in color], kmin, kmax, _stream())
     return out if raw.dim() == 3 else out[0]
+
+
+def measure_mask(dilated, region, raw, connectivity=8, pixel_type="u16", stored_bits=16):
+    """Measurements of masks (K7, nm03/measure.h) → list of dicts of the record's integers: area_px,
+    region_px, bbox [x0, y0, x1, y1], sum_x, sum_y, perimeter_edges, components, largest_px, holes
+    (on `dilated`, components at `connectivity` 4 | 8, holes at its dual), raw_sum / raw_min / raw_max
+    (the stored samples of `raw` under `dilated`) and region_px = popcount(`region`).
+
+    `dilated`, `region` (bool) and `raw` (16-bit storage) are CUDA tensors [N, H, W] or [H, W], or
+    lists of [H, W] tensors of ANY sizes: the whole batch is one launch, one workgroup per slice."""
+    def as_list(t):
+        if isinstance(t, (list, tuple)):
+            return list(t)
+        return list(_as3d(t))
+    dl, rl, xl = as_list(dilated), as_list(region), as_list(raw)
+    if not dl or len(rl) != len(dl) or len(xl) != len(dl):
+        raise ValueError("dilated, region and raw must hold the same number of slices")
+    hs, ws, dw, rw, xs = [], [], [], [], []
+    for d, r, x in zip(dl, rl, xl):
+        if d.dim() != 2 or r.shape != d.shape or x.shape != d.shape:
+            raise ValueError("every slice needs dilated, region and raw of one [H, W] shape")
+        if not (d.is_cuda and r.is_cuda):
+            raise ValueError("masks must be CUDA (HIP) tensors")
+        x = x.contiguous()
+        _check(x, _U16, "raw")
+        hs.append(int(d.shape[0]))
+        ws.append(int(d.shape[1]))
+        dw.append(pack_bits(d.bool().unsqueeze(0)).reshape(-1))
+        rw.append(pack_bits(r.bool().unsqueeze(0)).reshape(-1))
+        xs.append(x.reshape(-1).view(torch.int16))
+    planes = torch.cat(dw + rw).contiguous()
+    samples = torch.cat(xs).contiguous()
+    return native().k_measure(planes.data_ptr(), samples.data_ptr(), hs, ws, pixel_type, int(stored_bits),
+                              int(connectivity), _stream())

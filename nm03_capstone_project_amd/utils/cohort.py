@@ -95,3 +95,20 @@ class Cohort:
                 os.makedirs(od, exist_ok=True)
             items.extend((f, od) for f in p.files)
         return items
+
+
+def read_measurements(out_dir):
+    """Rows of <out_dir>/measurements.csv (written by the CLIs with --measure) as dicts keyed by the
+    header: one per slice (`status` "ok" or the failure's name, then empty fields) and one per patient
+    with file == "TOTAL" carrying the summed area_px and area_mm2. Integer columns come back as int,
+    the derived ones as float, empty fields as None."""
+    import csv
+    import os
+    floats = {"area_mm2", "centroid_x", "centroid_y", "centroid_x_mm", "centroid_y_mm", "mean"}
+    text = {"patient", "file", "status"}
+    rows = []
+    with open(os.path.join(out_dir, "measurements.csv"), newline="") as f:
+        for r in csv.DictReader(f):
+            rows.append({k: v if k in text else None if v == "" else float(v) if k in floats else int(v)
+                         for k, v in r.items()})
+    return rows

@@ -1,0 +1,126 @@
+// --measure: the cohort table. After a job's final barrier rank 0 reads the sidecars the ranks wrote
+// (<out>/<patient>/<stem>_measure.json, measure::to_json) in patient / slice order and writes
+// <out>/measurements.csv. Reading the files — not gathering records over the comm — keeps the
+// table identical at any rank count and batch size, and under --resume.
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <sstream>
+
+#include "nm03/app.h"
+#include "nm03/cohort.h"
+#include "nm03/measure.h"
+
+namespace nm03::app {
+
+const char* slice_status_name(int code) {
+  switch (code) {
+    case kSliceOk: return "ok";
+    case kSliceLoadError: return "load_error";
+    case kSliceTooSmall: return "too_small";
+    case kSliceDeviceError: return "device_error";
+    case kSliceExportError: return "export_error";
+    default: return "not_run";
+  }
+}
+
+namespace {
+
+// Columns after patient, file, status: the sidecar's keys in its order, bbox flattened.
+const char* const kColumns[] = {"width",      "height",        "connectivity",  "area_px",    "region_px",  "bbox_x0",
+                                "bbox_y0",    "bbox_x1",       "bbox_y1",       "sum_x",      "sum_y",      "perimeter_edges",
+                                "components", "largest_px",    "holes",         "raw_sum",    "raw_min",    "raw_max",
+                                "area_mm2",   "centroid_x",    "centroid_y",    "centroid_x_mm", "centroid_y_mm", "mean"};
+constexpr size_t kNumColumns = sizeof(kColumns) / sizeof(kColumns[0]);
+constexpr size_t kColAreaPx = 3, kColAreaMm2 = 18;
+
+// The values of one sidecar line in column order ("" for null). The text is this program's own
+// (one flat object, one array of four integers): values are what stands between ':' or ',' and the
+// next ',' / ']' / '}'.
+bool parse_sidecar(const std::string& text, std::vector<std::string>& out) {
+  out.clear();
+  size_t i = text.find('{');
+  if (i == std::string::npos) return false;
+  ++i;
+  while (i < text.size() && text[i] != '}') {
+    if (text[i] == ',') ++i;
+    if (text[i] != '"') return false;
+    const size_t kend = text.find('"', i + 1);
+    if (kend == std::string::npos || kend + 1 >= text.size() || text[kend + 1] != ':') return false;
+    i = kend + 2;
+    if (i < text.size() && text[i] == '[') {
+      const size_t aend = text.find(']', i);
+      if (aend == std::string::npos) return false;
+      std::stringstream ss(text.substr(i + 1, aend - i - 1));
+      std::string v;
+      while (std::getline(ss, v, ',')) out.push_back(v);
+      i = aend + 1;
+    } else {
+      size_t vend = i;
+      while (vend < text.size() && text[vend] != ',' && text[vend] != '}') ++vend;
+      const std::string v = text.substr(i, vend - i);
+      out.push_back(v == "null" ? std::string() : v);
+      i = vend;
+    }
+  }
+  return out.size() == kNumColumns;
+}
+
+}  // namespace
+
+MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients) {
+  MeasureTotals tot;
+  std::ostringstream o;
+  o << "patient,file,status";
+  for (const char* c : kColumns) o << "," << c;
+  o << "\n";
+  char buf[64];
+  for (const auto& p : patients) {
+    uint64_t area_px = 0;
+    double area_mm2 = 0;
+    for (size_t i = 0; i < p.files.size(); ++i) {
+      const std::string name = cohort::filename(p.files[i]);
+      std::vector<std::string> v;
+      bool have = false;
+      if (p.status[i] == kSliceOk) {
+        std::ifstream f(cohort::with_slash(p.out_dir) + measure::sidecar_name(cohort::stem(p.files[i])), std::ios::binary);
+        std::stringstream ss;
+        if (f) ss << f.rdbuf();
+        have = f && parse_sidecar(ss.str(), v);
+      }
+      o << p.id << "," << name << "," << (p.status[i] == kSliceOk && !have ? "no_sidecar" : slice_status_name(p.status[i]));
+      for (size_t c = 0; c < kNumColumns; ++c) o << "," << (have ? v[c] : std::string());
+      o << "\n";
+      if (!have) continue;
+      ++tot.slices;
+      area_px += std::strtoull(v[kColAreaPx].c_str(), nullptr, 10);
+      area_mm2 += std::strtod(v[kColAreaMm2].c_str(), nullptr);
+    }
+    o << p.id << ",TOTAL,";
+    for (size_t c = 0; c < kNumColumns; ++c) {
+      o << ",";
+      if (c == kColAreaPx) o << area_px;
+      if (c == kColAreaMm2) {
+        std::snprintf(buf, sizeof buf, "%.9g", area_mm2);
+        o << buf;
+      }
+    }
+    o << "\n";
+    tot.area_px += area_px;
+    tot.area_mm2 += area_mm2;
+  }
+  const std::string text = o.str();
+  std::ofstream f(cohort::with_slash(out_root) + "measurements.csv", std::ios::binary | std::ios::trunc);
+  f.write(text.data(), (std::streamsize)text.size());
+  if (!f) throw std::runtime_error("Cannot write " + cohort::with_slash(out_root) + "measurements.csv");
+  return tot;
+}
+
+std::string measure_totals_json(const MeasureTotals& t) {
+  char buf[160];
+  std::snprintf(buf, sizeof buf, "{\"slices\": %lld, \"area_px_total\": %llu, \"area_mm2_total\": %.9g}", (long long)t.slices,
+                (unsigned long long)t.area_px, t.area_mm2);
+  return buf;
+}
+
+}  // namespace nm03::app

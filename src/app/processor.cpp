@@ -59,16 +59,20 @@ void usage(const std::string& which) {
             << "  --overlay              also export the colour overlay (original + dilated mask): <stem>_overlay.jpg,\n"
             << "                         test_pipeline: overlay.jpg (needs --jpeg-sampling 420 or 444; 2D only)\n"
             << "  --overlay-color R,G,B  label colour of the overlay, three values 0..255 (default 0,255,0)\n"
+            << "  --measure              also write per-slice measurements of the dilated mask: <stem>_measure.json and\n"
+            << "                         <out>/measurements.csv; test_pipeline: measure.json (2D only)\n"
+            << "  --measure-connectivity 4|8  connectivity of the component count (default 8; holes use the dual)\n"
             << "  --mode 2d|3d           3d: whole series as a volume (SRG 6-conn + cube dilation)\n"
             << "  --split-volume         3d: each volume split into z-slabs over all ranks (halo exchange)\n"
             << "  --input FILE           test_pipeline: slice to process\n"
-            << "  --cpu                  test_pipeline / --mode 3d: golden CPU model instead of the GPU\n"
+            << "  --cpu                  golden CPU model instead of the GPU (test_pipeline, --mode 3d, and the 2D\n"
+            << "                         cohort CLIs, whose ranks are then CPU processes)\n"
             << "  --no-montage           test_pipeline: skip the 5-view montage JPEG\n"
             << "  --html                 test_pipeline: also write multi_view.html, the five views in a 2300x450 window\n"
             << "  --dump-mhd DIR         test_pipeline: write stage arrays as MetaImage (.mhd/.raw)\n"
             << "  --repeat N             process the cohort N times (benchmarking)\n"
             << "  --json FILE            write run metrics as JSON\n"
-            << "  --resume               keep existing outputs; skip slices whose two JPEGs exist\n"
+            << "  --resume               keep existing outputs; skip slices whose requested files all exist\n"
             << "  --frame K              import frame K of multi-frame DICOM files (default: reject them)\n"
             << "  --hw-queues N|auto     HIP hardware queues of this process (GPU_MAX_HW_QUEUES, 1..32; auto: 1 for short\n"
             << "                         2D jobs on shader copies unless the environment chose a value, else unchanged;\n"
@@ -241,6 +245,15 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
     }
     else if (a == "--split-volume") c.split_volume = true;
     else if (a == "--overlay") c.engine.render.overlay = true;
+    else if (a == "--measure") c.engine.pipe.measure = true;
+    else if (a == "--measure-connectivity") {
+      const std::string v = val();
+      if (v != "4" && v != "8") {
+        std::cerr << "--measure-connectivity must be 4 or 8" << std::endl;
+        std::exit(2);
+      }
+      c.engine.pipe.measure_connectivity = v == "4" ? 4 : 8;
+    }
     else if (a == "--overlay-color") {
       // Exactly three decimal values 0..255 separated by commas.
       const std::string v = val();
@@ -274,6 +287,10 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
     std::cerr << "--overlay needs --jpeg-sampling 420 or 444: a one-component gray file cannot carry colour" << std::endl;
     std::exit(2);
   }
+  if (c.engine.pipe.measure && c.mode == "3d") {
+    std::cerr << "--measure is not available with --mode 3d" << std::endl;
+    std::exit(2);
+  }
   if (c.engine.render.overlay && c.mode == "3d") {
     std::cerr << "--overlay is not available with --mode 3d" << std::endl;
     std::exit(2);
@@ -291,8 +308,16 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
 // =============================================================================================
 // img_processing_sequential
 // =============================================================================================
+namespace {
+int run_cohort_cpu(const AppConfig& cfg, int ranks, const char* mode_name);  // below, with the parallel CLI
+}
+
 int run_sequential(const AppConfig& cfg) {
   try {
+    if (cfg.cpu) {  // golden model, one CPU process
+      cohort::make_dirs(cfg.out_dir);
+      return run_cohort_cpu(cfg, 1, "sequential");
+    }
     const int64_t cohort_slices = cfg.copy_engine == kCopyAuto ? count_cohort_slices(cfg) : -1;
     apply_copy_engine(cfg, cohort_slices < 0 ? -1 : cohort_slices * std::max(1, cfg.repeat));
     // HIP start-up and the engine's construction on the start-up thread while the output root is set up.
@@ -322,7 +347,9 @@ int run_sequential(const AppConfig& cfg) {
     const double t0 = now_s();
     StageTimes total;
     int64_t slices = 0, slices_ok = 0;
+    MeasureTotals measure_totals;
     for (int rep = 0; rep < cfg.repeat; ++rep) {
+      std::vector<MeasurePatient> measured;  // --measure: this pass's patients, for the cohort table
       std::cout << "\n=== Starting Sequential Processing for All Patients ===\n" << std::endl;  // :317
       std::vector<std::string> patients;
       try {
@@ -368,6 +395,14 @@ int run_sequential(const AppConfig& cfg) {
                 items, &t, [&](size_t i) {
                   if (!cfg.quiet) std::cout << "Processing: \"" << cohort::filename(items[i].path) << "\"" << std::endl;  // :172
                 });
+            if (cfg.engine.pipe.measure) {
+              MeasurePatient m;
+              m.id = pid;
+              m.out_dir = out;
+              m.files = series.files;
+              for (const auto& x : st) m.status.push_back(x.code);
+              measured.push_back(std::move(m));
+            }
             int ok = 0;
             for (size_t i = 0; i < st.size(); ++i) {
               if (st[i].code == kSliceOk) {
@@ -410,6 +445,13 @@ int run_sequential(const AppConfig& cfg) {
       }
       std::cout << "\n=== All Processing Completed ===\n" << std::endl;                              // :340
       std::cout << "Successfully processed " << successful << "/" << patients.size() << " patients." << std::endl;  // :341
+      if (cfg.engine.pipe.measure) {
+        try {
+          measure_totals = write_measurements_csv(cfg.out_dir, measured);
+        } catch (const std::exception& e) {
+          std::cerr << "Error writing measurements.csv: " << e.what() << std::endl;
+        }
+      }
     }
     reaper.drain();
     const double wall = now_s() - t0;
@@ -417,7 +459,9 @@ int run_sequential(const AppConfig& cfg) {
                              ", \"slices\": " + std::to_string(slices) + ", \"slices_ok\": " + std::to_string(slices_ok) +
                              ", \"slices_per_s\": " + fmt(slices_ok / std::max(wall, 1e-9)) +
                              ", \"load_s\": " + fmt(total.load_s) + ", \"h2d_s\": " + fmt(total.h2d_s) +
-                             ", \"kernels_s\": " + fmt(total.kernels_s) + ", \"write_s\": " + fmt(total.write_s) + "}");
+                             ", \"kernels_s\": " + fmt(total.kernels_s) + ", \"write_s\": " + fmt(total.write_s) +
+                             (cfg.engine.pipe.measure ? ", \"measure\": " + measure_totals_json(measure_totals) : std::string()) +
+                             "}");
   } catch (const std::exception& e) {
     std::cerr << "Fatal error: " << e.what() << std::endl;  // :359-360
     return 1;
@@ -531,6 +575,32 @@ HeaderScan scan_headers(const std::vector<PatientPlan>& plan, int threads) {
   work();
   for (auto& t : th) t.join();
   return {md.load(), mb.load()};
+}
+
+// --measure: the plan's patients with the gathered statuses (plan order), for the cohort table.
+std::vector<MeasurePatient> measure_patients(const std::vector<PatientPlan>& plan, const std::vector<SliceStatus>& gst) {
+  std::vector<MeasurePatient> out;
+  size_t cursor = 0;
+  for (const auto& p : plan) {
+    MeasurePatient m;
+    m.id = p.id;
+    m.out_dir = p.out_dir;
+    m.files = p.files;
+    for (size_t i = 0; i < p.files.size(); ++i, ++cursor)
+      m.status.push_back(cursor < gst.size() ? gst[cursor].code : (int32_t)kSliceNotRun);
+    out.push_back(std::move(m));
+  }
+  return out;
+}
+
+// Rank 0, after the job's final barrier: the cohort table (an error is reported, not fatal).
+void write_measure_table(const AppConfig& cfg, const std::vector<PatientPlan>& plan, const std::vector<SliceStatus>& gst,
+                         MeasureTotals* totals) {
+  try {
+    *totals = write_measurements_csv(cfg.out_dir, measure_patients(plan, gst));
+  } catch (const std::exception& e) {
+    std::cerr << "Error writing measurements.csv: " << e.what() << std::endl;
+  }
 }
 
 }  // namespace
@@ -690,6 +760,7 @@ int parallel_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int devi
   double proc_wall = 0, my_wall = 0;
   int64_t total_ok = 0, total_slices = 0, my_slices = 0, my_ok = 0;
   StageTimes agg;
+  MeasureTotals measure_totals;  // --measure: the last pass's table (rank 0)
   // Rank 0 wipes the patient directories by renaming them aside; 4 background threads delete the
   // old files while the ranks process (cohort.h OutputReaper), waited for before the run ends.
   std::unique_ptr<cohort::OutputReaper> reaper;
@@ -911,6 +982,8 @@ int parallel_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int devi
         std::cout << "\n=== All Processing Completed ===\n" << std::endl;  // :383
         std::cout << "Successfully processed " << successful << "/" << plan.size() << " patients." << std::endl;
       }
+      // Every rank's files are on disk (the barrier after the run): the table from the sidecars.
+      if (cfg.engine.pipe.measure) write_measure_table(cfg, plan, gst, &measure_totals);
     }
   }
   if (reaper) reaper->drain();
@@ -955,7 +1028,9 @@ int parallel_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int devi
                              fmt(dp.wait_s) + ", \"comm_init_s\": " + fmt(dp.init_upper_s) + ", \"wall_s\": " + fmt(tot) +
                              ", \"processing_wall_s\": " + fmt(proc_wall) + ", \"slices\": " + std::to_string(total_slices) +
                              ", \"slices_ok\": " + std::to_string(total_ok) + ", \"slices_per_s\": " +
-                             fmt(total_ok / std::max(proc_wall, 1e-9)) + ", \"rank0\": {\"load_s\": " + fmt(agg.load_s) +
+                             fmt(total_ok / std::max(proc_wall, 1e-9)) +
+                             (cfg.engine.pipe.measure ? ", \"measure\": " + measure_totals_json(measure_totals) : std::string()) +
+                             ", \"rank0\": {\"load_s\": " + fmt(agg.load_s) +
                              ", \"h2d_s\": " + fmt(agg.h2d_s) + ", \"kernels_s\": " + fmt(agg.kernels_s) +
                              ", \"write_s\": " + fmt(agg.write_s) + ", \"jpeg_fallbacks\": " +
                              std::to_string(agg.jpeg_fallbacks) + "}, \"per_rank\": " + per_rank_json(rows) +
@@ -970,6 +1045,159 @@ int parallel_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int devi
     (void)engine_p.release();
   }
   return 0;
+}
+
+// ---- --cpu on the 2D cohort CLIs: the golden model writes the files the engine would -------------
+// One slice: load, golden::run, the two (three with --overlay) JPEGs and, with --measure, the sidecar.
+SliceStatus cpu_slice(const AppConfig& cfg, const WorkItem& w) {
+  const PipelineParams& p = cfg.engine.pipe;
+  const RenderParams& rp = cfg.engine.render;
+  const std::string base = cohort::with_slash(w.out_dir) + cohort::stem(w.path);
+  auto exists = [](const std::string& f) { return access(f.c_str(), F_OK) == 0; };
+  if (cfg.engine.resume && exists(base + "_original.jpg") && exists(base + "_processed.jpg") &&
+      (!rp.overlay || exists(base + "_overlay.jpg")) && (!p.measure || exists(base + "_measure.json")))
+    return SliceStatus{kSliceOk, ""};
+  golden::SliceInput in;
+  try {
+    in = golden::load_slice(w.path, 0, p.frame);
+  } catch (const std::exception& e) {
+    return SliceStatus{kSliceLoadError, e.what()};
+  }
+  if (p.min_dim > 0 && (in.w < p.min_dim || in.h < p.min_dim))
+    return SliceStatus{kSliceTooSmall, "Image dimensions too small: " + std::to_string(in.w) + "x" + std::to_string(in.h)};
+  try {
+    const golden::SliceResult r = golden::run(in, p, false);
+    const golden::SliceJpegs j = golden::export_jpegs(in, r, p, rp);
+    auto put = [&](const std::string& name, const void* data, size_t len) {
+      std::ofstream f(name, std::ios::binary | std::ios::trunc);
+      f.write((const char*)data, (std::streamsize)len);
+      if (!f) throw std::runtime_error("Write failed: " + name);
+    };
+    put(base + "_original.jpg", j.original.data(), j.original.size());
+    put(base + "_processed.jpg", j.processed.data(), j.processed.size());
+    if (rp.overlay) put(base + "_overlay.jpg", j.overlay.data(), j.overlay.size());
+    if (p.measure) {
+      const std::string js = golden::measure_json(golden::measure(r.dilated, r.region, in, p.measure_connectivity), in, p);
+      put(base + "_measure.json", js.data(), js.size());
+    }
+  } catch (const std::exception& e) {
+    return SliceStatus{kSliceExportError, std::string("Error in export stage: ") + e.what()};
+  }
+  return SliceStatus{kSliceOk, ""};
+}
+
+// A rank of the CPU cohort job: rank 0 plans as parallel_rank does, the work list is cut into the
+// same contiguous blocks, every rank runs its block through cpu_slice, rank 0 reports. No HIP call.
+int cohort_rank_cpu(const AppConfig& cfg, int rank, int size, Comm& comm, const char* mode_name) {
+  const std::string base = cohort::cohort_dir(cfg.data_root);
+  const double t_start = now_s();
+  int64_t total_ok = 0, total_slices = 0;
+  MeasureTotals measure_totals;
+  for (int rep = 0; rep < cfg.repeat; ++rep) {
+    std::vector<uint8_t> plan_bytes;
+    int64_t fatal = 0;
+    std::string fatal_msg;
+    if (rank == 0) {
+      std::vector<PatientPlan> plan;
+      try {
+        for (const auto& pid : cohort::find_patient_dirs(base)) {
+          PatientPlan p;
+          p.id = pid;
+          p.out_dir = cfg.out_dir + "/" + pid;
+          try {
+            if (cfg.engine.resume)
+              cohort::make_dirs(p.out_dir);
+            else
+              cohort::setup_output_dir(p.out_dir);
+            p.setup_ok = true;
+            cohort::Series sr = cohort::list_patient_series(base, pid);
+            p.series_dir = sr.series_dir;
+            p.files = std::move(sr.files);
+            p.listed = true;
+          } catch (const std::exception& e) {
+            p.error = p.setup_ok ? e.what() : std::string("Error setting up output directory: ") + e.what();
+          }
+          plan.push_back(std::move(p));
+        }
+      } catch (const std::exception& e) {
+        fatal = 1;
+        fatal_msg = e.what();
+      }
+      plan_bytes = encode_plan(plan);
+    }
+    comm.allreduce_sum_i64(&fatal, 1);
+    if (fatal) {
+      if (rank == 0) std::cerr << "Fatal error: " << fatal_msg << std::endl;
+      return 1;
+    }
+    comm.broadcast_bytes(plan_bytes, 0);
+    const std::vector<PatientPlan> plan = decode_plan(plan_bytes);
+    std::vector<WorkItem> items;
+    for (const auto& p : plan)
+      for (const auto& f : p.files) items.push_back({f, p.out_dir});
+    const size_t n = items.size();
+    const size_t lo = n * rank / size, hi = n * (rank + 1) / size;
+    ByteWriter w;
+    w.u32((uint32_t)(hi - lo));
+    for (size_t i = lo; i < hi; ++i) {
+      const SliceStatus st = cpu_slice(cfg, items[i]);
+      w.i32(st.code);
+      w.str(st.message);
+    }
+    comm.barrier();  // every rank's files are on disk
+    auto all = comm.allgather_bytes(w.b);
+    if (rank != 0) continue;
+    std::vector<SliceStatus> gst;
+    for (auto& b : all) {
+      ByteReader r(b.data(), b.size());
+      const uint32_t k = r.u32();
+      for (uint32_t i = 0; i < k; ++i) {
+        SliceStatus st;
+        st.code = r.i32();
+        st.message = r.str();
+        gst.push_back(std::move(st));
+      }
+    }
+    size_t cursor = 0;
+    for (const auto& pp : plan) {
+      if (!pp.listed) {
+        std::cerr << "Error processing patient " << pp.id << ": " << pp.error << std::endl;
+        continue;
+      }
+      int ok = 0;
+      for (size_t i = 0; i < pp.files.size(); ++i, ++cursor) {
+        const SliceStatus& st = gst[cursor];
+        if (st.code == kSliceOk)
+          ++ok;
+        else
+          std::cerr << "Error processing file " << pp.files[i] << ":\n"
+                    << "Detailed error: " << st.message << std::endl;
+      }
+      total_ok += ok;
+      total_slices += (int64_t)pp.files.size();
+      std::cout << "\nPatient " << pp.id << " completed. Successfully processed " << ok << "/" << pp.files.size()
+                << " images." << std::endl;
+    }
+    if (cfg.engine.pipe.measure) write_measure_table(cfg, plan, gst, &measure_totals);
+  }
+  if (rank == 0) {
+    const double wall = now_s() - t_start;
+    write_json(cfg.json, std::string("{\"mode\": \"") + mode_name + "\", \"backend\": \"cpu\", \"gpus\": " +
+                             std::to_string(size) + ", \"wall_s\": " + fmt(wall) + ", \"slices\": " +
+                             std::to_string(total_slices) + ", \"slices_ok\": " + std::to_string(total_ok) +
+                             ", \"slices_per_s\": " + fmt(total_ok / std::max(wall, 1e-9)) +
+                             (cfg.engine.pipe.measure ? ", \"measure\": " + measure_totals_json(measure_totals) : std::string()) +
+                             "}");
+  }
+  return 0;
+}
+
+int run_cohort_cpu(const AppConfig& cfg, int ranks, const char* mode_name) {
+  LaunchOptions lo = LaunchOptions::from_env();
+  lo.comm = "host";  // CPU processes over the shared-memory control plane
+  return launch_ranks(std::max(1, ranks), [&](int rank, int size, Comm& comm) {
+    return cohort_rank_cpu(cfg, rank, size, comm, mode_name);
+  }, lo);
 }
 
 }  // namespace
@@ -1078,6 +1306,7 @@ int run_parallel(const AppConfig& cfg) {
       apply_copy_engine(cfg, -1);  // auto keeps the DMA engines for volumes (32 MB per 256³ upload)
       return run_volume_cohort(cfg);
     }
+    if (cfg.cpu) return run_cohort_cpu(cfg, cfg.gpus, "parallel");  // golden model; --gpus N CPU ranks (auto / all: 1)
     LaunchOptions lo = LaunchOptions::from_env();
     // auto: size the job to the cohort, counted from its directory listings before any fork
     const int64_t slices = count_cohort_slices(cfg);  // rank count, copy path and comm policy (≈ 1 ms of listings)
@@ -1113,13 +1342,15 @@ int run_test_pipeline(const AppConfig& cfg) {
     const PipelineParams& p = cfg.engine.pipe;
     const RenderParams& rp = cfg.engine.render;
     std::vector<std::vector<uint8_t>> canvases, jpegs;
+    std::string measure_json;  // --measure: the sidecar text
     // Stage arrays for --dump-mhd: sharpened f32 and the four masks (band, SRG, erosion, dilation).
     std::vector<float> d_sharp;
     std::vector<std::vector<uint8_t>> d_masks;
     const double t0 = now_s();
     if (cfg.cpu) {
       golden::SliceResult st;
-      golden::StageImages r = golden::test_pipeline_images(in, p, rp, cfg.dump_mhd.empty() ? nullptr : &st);
+      golden::StageImages r = golden::test_pipeline_images(in, p, rp, cfg.dump_mhd.empty() && !p.measure ? nullptr : &st);
+      if (p.measure) measure_json = golden::measure_json(golden::measure(st.dilated, st.region, in, p.measure_connectivity), in, p);
       canvases = std::move(r.canvases);
       jpegs = std::move(r.jpegs);
       d_sharp = std::move(st.sharpened);
@@ -1136,6 +1367,7 @@ int run_test_pipeline(const AppConfig& cfg) {
       canvases = std::move(r.canvases);
       jpegs = std::move(r.jpegs);
       if (rp.overlay) jpegs.push_back(std::move(r.jpeg_overlay));
+      measure_json = std::move(r.measure_json);
       d_sharp = std::move(r.sharpened);
       d_masks = {std::move(r.band), std::move(r.region), std::move(r.eroded), std::move(r.dilated)};
     }
@@ -1161,6 +1393,10 @@ int run_test_pipeline(const AppConfig& cfg) {
     if (rp.overlay) {  // --overlay: the sixth stage image, the original with the dilated mask over it (colour)
       std::ofstream f(cfg.out_dir + "/overlay.jpg", std::ios::binary | std::ios::trunc);
       f.write((const char*)jpegs.at(5).data(), (std::streamsize)jpegs.at(5).size());
+    }
+    if (p.measure) {  // --measure: the measurements of the dilated mask
+      std::ofstream f(cfg.out_dir + "/measure.json", std::ios::binary | std::ios::trunc);
+      f.write(measure_json.data(), (std::streamsize)measure_json.size());
     }
     if (cfg.montage) {
       // Headless MultiViewWindow(5, Black, ...): the five views side by side.

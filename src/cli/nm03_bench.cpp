@@ -60,6 +60,8 @@ int main(int argc, char** argv) {
       ec.render.jpeg_sampling = s == "gray" ? 2 : s == "444" ? 1 : 0;
     }
     else if (a == "--overlay") ec.render.overlay = true;  // cohort: also the colour overlay per slice
+    else if (a == "--measure") ec.pipe.measure = true;    // cohort: also K7 and the measurement sidecar per slice
+    else if (a == "--measure-connectivity") ec.pipe.measure_connectivity = std::atoi(v().c_str()) == 4 ? 4 : 8;
     else if (a == "--se-shape") ec.pipe.se_shape = v() == "disc" ? nm03::kSeDisc : nm03::kSeSquare;
     else if (a == "--render-filter") ec.render.filter = v() == "nearest" ? nm03::kFilterNearest : nm03::kFilterBilinear;
     else {

@@ -312,8 +312,27 @@ void write_jpeg_file(const std::string& path, const std::vector<uint8_t>& header
   write_jpeg_at(AT_FDCWD, "", path, header, scan, scan_len);
 }
 
+namespace {
+void write_parts_at(int dirfd, const std::string& dir, const std::string& name, struct iovec* iov, int nparts,
+                    std::atomic<uint8_t>* creating);
+}
+
 void write_jpeg_at(int dirfd, const std::string& dir, const std::string& name, const std::vector<uint8_t>& header,
                    const uint8_t* scan, size_t scan_len, std::atomic<uint8_t>* creating) {
+  static const uint8_t eoi[2] = {0xFF, 0xD9};
+  struct iovec iov[3] = {{(void*)header.data(), header.size()}, {(void*)scan, scan_len}, {(void*)eoi, 2}};
+  write_parts_at(dirfd, dir, name, iov, 3, creating);
+}
+
+void write_bytes_at(int dirfd, const std::string& dir, const std::string& name, const void* data, size_t len,
+                    std::atomic<uint8_t>* creating) {
+  struct iovec iov[1] = {{(void*)data, len}};
+  write_parts_at(dirfd, dir, name, iov, 1, creating);
+}
+
+namespace {
+void write_parts_at(int dirfd, const std::string& dir, const std::string& name, struct iovec* iov, int nparts,
+                    std::atomic<uint8_t>* creating) {
   auto path = [&] { return dir.empty() ? name : dir + "/" + name; };
   // Overwrite in place instead of O_TRUNC: re-exporting a cohort rewrites files of (nearly) the
   // same size, and truncate + reallocate costs 4-12x more than pwrite on ext4/overlayfs. The old
@@ -335,13 +354,12 @@ void write_jpeg_at(int dirfd, const std::string& dir, const std::string& name, c
   }
   if (fd < 0) fd = ::openat(dirfd, name.c_str(), O_WRONLY | O_CREAT | O_CLOEXEC, 0644);
   if (fd < 0) throw std::runtime_error("Cannot create " + path() + ": " + std::strerror(errno));
-  static const uint8_t eoi[2] = {0xFF, 0xD9};
-  struct iovec iov[3] = {{(void*)header.data(), header.size()}, {(void*)scan, scan_len}, {(void*)eoi, 2}};
-  const size_t total = header.size() + scan_len + 2;
+  size_t total = 0;
+  for (int k = 0; k < nparts; ++k) total += iov[k].iov_len;
   size_t done = 0;
   int idx = 0;
   while (done < total) {
-    ssize_t w = ::pwritev(fd, iov + idx, 3 - idx, (off_t)done);
+    ssize_t w = ::pwritev(fd, iov + idx, nparts - idx, (off_t)done);
     if (w < 0 && errno == EINTR) continue;
     if (w <= 0) {
       ::close(fd);
@@ -349,11 +367,11 @@ void write_jpeg_at(int dirfd, const std::string& dir, const std::string& name, c
     }
     done += (size_t)w;
     size_t adv = (size_t)w;
-    while (idx < 3 && adv >= iov[idx].iov_len) {
+    while (idx < nparts && adv >= iov[idx].iov_len) {
       adv -= iov[idx].iov_len;
       ++idx;
     }
-    if (idx < 3) {
+    if (idx < nparts) {
       iov[idx].iov_base = (uint8_t*)iov[idx].iov_base + adv;
       iov[idx].iov_len -= adv;
     }
@@ -367,5 +385,6 @@ void write_jpeg_at(int dirfd, const std::string& dir, const std::string& name, c
   }
   ::close(fd);
 }
+}  // namespace
 
 }  // namespace nm03::jpeg

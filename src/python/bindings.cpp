@@ -209,6 +209,45 @@ gpu::PipeConsts consts_from(const PipelineParams& p, int border_radius) {
   return pc;
 }
 
+// The integers of a measurement record (nm03/measure.h) as a dict.
+py::dict measure_dict(const SliceMeasure& m) {
+  py::dict d;
+  d["area_px"] = m.area_px;
+  d["region_px"] = m.region_px;
+  py::list bb;
+  for (int k = 0; k < 4; ++k) bb.append(m.bbox[k]);
+  d["bbox"] = bb;
+  d["sum_x"] = m.sum_x;
+  d["sum_y"] = m.sum_y;
+  d["perimeter_edges"] = m.perimeter_edges;
+  d["components"] = m.components;
+  d["largest_px"] = m.largest_px;
+  d["holes"] = m.holes;
+  d["raw_sum"] = m.raw_sum;
+  d["raw_min"] = m.raw_min;
+  d["raw_max"] = m.raw_max;
+  return d;
+}
+
+SliceMeasure measure_from(const py::dict& d) {
+  SliceMeasure m{};
+  m.area_px = d["area_px"].cast<uint32_t>();
+  m.region_px = d["region_px"].cast<uint32_t>();
+  const std::vector<int> bb = d["bbox"].cast<std::vector<int>>();
+  if (bb.size() != 4) throw std::invalid_argument("bbox must have four values");
+  for (int k = 0; k < 4; ++k) m.bbox[k] = bb[(size_t)k];
+  m.sum_x = d["sum_x"].cast<uint64_t>();
+  m.sum_y = d["sum_y"].cast<uint64_t>();
+  m.perimeter_edges = d["perimeter_edges"].cast<uint32_t>();
+  m.components = d["components"].cast<uint32_t>();
+  m.largest_px = d["largest_px"].cast<uint32_t>();
+  m.holes = d["holes"].cast<uint32_t>();
+  m.raw_sum = d["raw_sum"].cast<int64_t>();
+  m.raw_min = d["raw_min"].cast<int32_t>();
+  m.raw_max = d["raw_max"].cast<int32_t>();
+  return m;
+}
+
 }  // namespace
 
 template <class Fn>
@@ -263,7 +302,14 @@ PYBIND11_MODULE(_nm03, m) {
       .def_readwrite("min_dim", &PipelineParams::min_dim)
       .def_readwrite("apply_rescale", &PipelineParams::apply_rescale)
       .def_readwrite("frame", &PipelineParams::frame)
-      .def_readwrite("se_shape", &PipelineParams::se_shape);
+      .def_readwrite("se_shape", &PipelineParams::se_shape)
+      .def_readwrite("measure", &PipelineParams::measure)
+      .def_property(
+          "measure_connectivity", [](const PipelineParams& p) { return (int)p.measure_connectivity; },
+          [](PipelineParams& p, int v) {
+            if (v != 4 && v != 8) throw std::invalid_argument("measure_connectivity must be 4 or 8");
+            p.measure_connectivity = (uint8_t)v;
+          });
   py::class_<RenderParams>(m, "RenderParams")
       .def(py::init<>())
       .def_readwrite("out_width", &RenderParams::out_width)
@@ -594,6 +640,11 @@ PYBIND11_MODULE(_nm03, m) {
           d["overlay"] = to_np<uint8_t>(j.overlay_canvas, {rp.out_height, rp.out_width, 3});
           d["jpeg_overlay"] = py::bytes((const char*)j.overlay.data(), j.overlay.size());
         }
+        if (p.measure) {
+          const SliceMeasure sm = golden::measure(r.dilated, r.region, s, p.measure_connectivity);
+          d["measure"] = measure_dict(sm);
+          d["measure_json"] = golden::measure_json(sm, s, p);
+        }
         return d;
       },
       py::arg("raw"), py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f,
@@ -691,6 +742,45 @@ PYBIND11_MODULE(_nm03, m) {
       py::arg("sy") = 1.f, py::arg("out_w") = 512, py::arg("out_h") = 512, py::arg("nearest") = false,
       py::arg("fill_a") = 153, py::arg("border_a") = 255, py::arg("color") = std::vector<int>{0, 255, 0});
   m.def("opacity_u8", &opacity_u8);
+
+  // ---- measurements (nm03/measure.h) -----------------------------------------------------------------
+  m.def(
+      "golden_measure",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+         py::array_t<uint8_t, py::array::c_style | py::array::forcecast> reg,
+         py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, const std::string& type, int stored_bits,
+         int connectivity) {
+        if (dil.ndim() != 2 || reg.ndim() != 2 || raw.ndim() != 2 || reg.shape(0) != dil.shape(0) ||
+            reg.shape(1) != dil.shape(1) || raw.shape(0) != dil.shape(0) || raw.shape(1) != dil.shape(1))
+          throw std::invalid_argument("dilated, region and raw must be [H, W] of one shape");
+        golden::SliceInput s = slice_from(raw, type, stored_bits, 1.f, 0.f, 1.f, 1.f);
+        return measure_dict(golden::measure(from_np<uint8_t>(dil), from_np<uint8_t>(reg), s, connectivity));
+      },
+      py::arg("dilated"), py::arg("region"), py::arg("raw"), py::arg("type") = "u16", py::arg("stored_bits") = 16,
+      py::arg("connectivity") = 8);
+  // Euler number (components − holes) of a mask [H, W] from the bit-quad counts the K7 kernel uses.
+  m.def(
+      "measure_euler",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> mask, int connectivity) {
+        if (mask.ndim() != 2) throw std::invalid_argument("mask must be [H, W]");
+        if (connectivity != 4 && connectivity != 8) throw std::invalid_argument("connectivity must be 4 or 8");
+        const int h = (int)mask.shape(0), w = (int)mask.shape(1), wpr = (w + 63) / 64;
+        std::vector<uint64_t> plane((size_t)h * wpr, 0ull);
+        auto a = mask.unchecked<2>();
+        for (int y = 0; y < h; ++y)
+          for (int x = 0; x < w; ++x)
+            if (a(y, x)) plane[(size_t)y * wpr + (x >> 6)] |= 1ull << (x & 63);
+        return measure::euler_plane(plane.data(), w, h, wpr, connectivity);
+      },
+      py::arg("mask"), py::arg("connectivity") = 8);
+  m.def(
+      "measure_to_json",
+      [](const py::dict& rec, int w, int h, float sx, float sy, float slope, float intercept, bool apply_rescale,
+         int connectivity) {
+        return measure::to_json(measure_from(rec), w, h, sx, sy, slope, intercept, apply_rescale, connectivity);
+      },
+      py::arg("record"), py::arg("w"), py::arg("h"), py::arg("spacing_x") = 1.f, py::arg("spacing_y") = 1.f,
+      py::arg("slope") = 1.f, py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 8);
 
   // ---- JPEG --------------------------------------------------------------------------------------
   m.def("jpeg_encode_gray420", [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> g, int quality) {
@@ -878,6 +968,10 @@ PYBIND11_MODULE(_nm03, m) {
              if (e.config().render.overlay) {
                d["overlay"] = to_np<uint8_t>(r.overlay, {ch, cw, 3});
                d["jpeg_overlay"] = py::bytes((const char*)r.jpeg_overlay.data(), r.jpeg_overlay.size());
+             }
+             if (e.config().pipe.measure) {
+               d["measure"] = measure_dict(r.measure);
+               d["measure_json"] = r.measure_json;
              }
              return d;
            },
@@ -1369,6 +1463,68 @@ PYBIND11_MODULE(_nm03, m) {
                                (const gpu::RenderDesc*)(dev + o_rd), 0, n, 1, n, out_w, out_h, col, (uint8_t*)rgb, st);
     gpu::check_hip(hipStreamSynchronize(st), "k_render_overlay");
   });
+
+  // K7 on a batch of slices of ANY sizes in one launch: planes = the dilated planes of every slice
+  // back to back (slice i: hs[i] × ceil(ws[i] / 64) words), then the region planes in the same layout;
+  // raw = the slices' u16 samples back to back. Returns one record dict per slice.
+  m.def("k_measure", [](uintptr_t planes, uintptr_t raw, const std::vector<int>& hs, const std::vector<int>& ws,
+                        const std::string& type, int stored_bits, int connectivity, uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    const int n = (int)hs.size();
+    if (n <= 0 || ws.size() != hs.size()) throw std::invalid_argument("one height and one width per slice");
+    if (connectivity != 4 && connectivity != 8) throw std::invalid_argument("connectivity must be 4 or 8");
+    if (stored_bits < 1 || stored_bits > 16) throw std::invalid_argument("stored_bits must be 1..16");
+    const PixelType pt = parse_type(type);
+    {
+      // K7's code object, loaded on the current device before this op's first launch there.
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_measure();
+        preloaded.push_back(dev);
+      }
+    }
+    std::vector<gpu::SliceDesc> d((size_t)n);
+    size_t raw_off = 0, mask_off = 0;
+    int max_w = 0, max_h = 0;
+    for (int i = 0; i < n; ++i) {
+      const int h = hs[(size_t)i], w = ws[(size_t)i];
+      if (w <= 0 || h <= 0 || w > gpu::kMaxSliceDim || h > gpu::kMaxSliceDim) throw std::invalid_argument("bad slice size");
+      gpu::SliceDesc& s = d[(size_t)i];
+      std::memset(&s, 0, sizeof(s));
+      s.raw_off = (uint32_t)raw_off;
+      s.mask_off = (uint32_t)mask_off;
+      s.w = (uint16_t)w;
+      s.h = (uint16_t)h;
+      s.wpr = (uint16_t)((w + 63) / 64);
+      s.type = pt == kU8 ? kU16 : pt;
+      s.stored_bits = (uint8_t)stored_bits;
+      raw_off += (size_t)h * w;
+      mask_off += (size_t)h * s.wpr;
+      max_w = std::max(max_w, w);
+      max_h = std::max(max_h, h);
+    }
+    if (raw_off > 0xFFFFFFFFull) throw std::invalid_argument("batch exceeds 2^32 samples");
+    const size_t per = gpu::measure_scratch_words(max_w, max_h);
+    const size_t o_desc = 0, o_out = (sizeof(gpu::SliceDesc) * n + 255) / 256 * 256,
+                 o_par = (o_out + sizeof(SliceMeasure) * n + 255) / 256 * 256, total = o_par + per * n * sizeof(uint32_t);
+    uint8_t* dev = (uint8_t*)scratch().get(total);
+    gpu::check_hip(hipMemcpyAsync(dev + o_desc, d.data(), sizeof(gpu::SliceDesc) * n, hipMemcpyHostToDevice, st), "H2D descriptors");
+    gpu::check_hip(hipStreamSynchronize(st), "sync descriptors");
+    const uint64_t* pl = (const uint64_t*)planes;
+    gpu::launch_measure(pl, pl + mask_off, (const uint16_t*)raw, (const gpu::SliceDesc*)(dev + o_desc), n, connectivity,
+                        (SliceMeasure*)(dev + o_out), (uint32_t*)(dev + o_par), max_w, max_h, st);
+    std::vector<SliceMeasure> res((size_t)n);
+    gpu::check_hip(hipMemcpyAsync(res.data(), dev + o_out, sizeof(SliceMeasure) * n, hipMemcpyDeviceToHost, st), "D2H records");
+    gpu::check_hip(hipStreamSynchronize(st), "k_measure");
+    py::list out;
+    for (auto& r : res) out.append(measure_dict(r));
+    return out;
+  }, py::arg("planes"), py::arg("raw"), py::arg("hs"), py::arg("ws"), py::arg("type") = "u16", py::arg("stored_bits") = 16,
+     py::arg("connectivity") = 8, py::arg("stream") = 0);
 
   // ---- comm self-tests (CPU) ------------------------------------------------------------------------
   m.def("loopback_selftest", [](int n) {

@@ -163,6 +163,11 @@ struct Slot {
   int32_t* h_ov_sizes = nullptr;
   int32_t* d_ov_sizes = nullptr;
   JpegDesc* d_ov_jd = nullptr;
+  // Measurements (PipelineParams::measure; all null without it): K7's labelling scratch and the
+  // host-mapped records, slice c of the batch at index c.
+  uint32_t* d_ms_scratch = nullptr;
+  SliceMeasure* h_measure = nullptr;
+  SliceMeasure* d_measure = nullptr;
 };
 
 // Private fd tables for the host pool's workers. Every open and
@@ -233,6 +238,8 @@ void hip_free_all(Slot& s) {
   if (s.h_single) (void)hipHostFree(s.h_single);
   if (s.h_ov_out) (void)hipHostFree(s.h_ov_out);
   if (s.h_ov_sizes) (void)hipHostFree(s.h_ov_sizes);
+  if (s.h_measure) (void)hipHostFree(s.h_measure);
+  if (s.d_ms_scratch) (void)hipFree(s.d_ms_scratch);
   for (void* p : {(void*)s.d_rgb, (void*)s.ov_jw.look, (void*)s.ov_jw.ticket, (void*)s.ov_jw.spill, (void*)s.d_ov_jd})
     if (p) (void)hipFree(p);
   for (void* p : {(void*)s.d_blob, (void*)s.d_raw_x, (void*)s.d_med, (void*)s.d_tile_mm, (void*)s.d_f32, (void*)s.d_bits, (void*)s.d_srg_scratch, (void*)s.d_canvas,
@@ -314,6 +321,11 @@ struct Engine::Impl {
     ov_cap_ = cfg.jpeg_out_cap ? out_cap_ : (2 * (out_cap_ - 64) + 64 + 15u) & ~15u;
     ov_color_ = (uint32_t)cfg.render.overlay_color[0] | ((uint32_t)cfg.render.overlay_color[1] << 8) |
                 ((uint32_t)cfg.render.overlay_color[2] << 16);
+    measure_ = cfg.pipe.measure;
+    if (measure_ && cfg.host_only)
+      throw std::invalid_argument("measure runs on the GPU (the K7 kernel): not available with host_only");
+    if (measure_ && cfg.pipe.measure_connectivity != 4 && cfg.pipe.measure_connectivity != 8)
+      throw std::invalid_argument("measure_connectivity must be 4 or 8");
     upload_chunk_ = cfg.upload_chunk_kb < 0 ? (size_t)2 << 20 : (size_t)cfg.upload_chunk_kb << 10;
     host_only_ = cfg.host_only;
     if (host_only_) upload_chunk_ = 0;  // nothing to upload
@@ -366,6 +378,7 @@ struct Engine::Impl {
       // The colour encoder's code object only when this engine will launch it (a default run never
       // loads it), and here — never lazily from a slot thread.
       if (overlay_) preload_jpeg_rgb();
+      if (measure_) preload_measure();  // likewise: only an engine that will launch K7 loads it
       d_lut_ = dmalloc<float>(kLutArenaFloats, "hipMalloc norm tables");
     }
     const double t1 = now_s();
@@ -714,6 +727,13 @@ struct Engine::Impl {
         check_hip(hipMemcpy(s.d_ov_jd, jd.data(), sizeof(JpegDesc) * n, hipMemcpyHostToDevice), "H2D overlay descriptors");
         mark("overlay");
       }
+      if (measure_) {
+        const int n = s.cap_slices;
+        s.d_ms_scratch = dmalloc<uint32_t>((size_t)n * measure_scratch_words(md, md), "hipMalloc measure scratch");
+        check_hip(hipHostMalloc((void**)&s.h_measure, sizeof(SliceMeasure) * n, hipHostMallocMapped), "hipHostMalloc measure");
+        check_hip(hipHostGetDevicePointer((void**)&s.d_measure, s.h_measure, 0), "hipHostGetDevicePointer measure");
+        mark("measure");
+      }
     } catch (...) {
       hip_free_all(s);
       throw;
@@ -962,7 +982,8 @@ struct Engine::Impl {
   bool outputs_exist(const WorkItem& w) const {
     const std::string base = cohort::with_slash(w.out_dir) + cohort::stem(w.path);
     return access((base + "_original.jpg").c_str(), F_OK) == 0 && access((base + "_processed.jpg").c_str(), F_OK) == 0 &&
-           (!overlay_ || access((base + "_overlay.jpg").c_str(), F_OK) == 0);
+           (!overlay_ || access((base + "_overlay.jpg").c_str(), F_OK) == 0) &&
+           (!measure_ || access((base + "_measure.json").c_str(), F_OK) == 0);
   }
 
   // ---- descriptor build + GPU enqueue --------------------------------------------------------
@@ -1153,6 +1174,7 @@ struct Engine::Impl {
     o.scratch = s.d_srg_scratch;
     o.dilated = plane(kPDilated);
     o.border_dilated = plane(kPBorderD);
+    if (measure_) o.region = plane(kPRegion);  // K7 counts the region's pixels too
     if (mode == 1) {
       o.region = plane(kPRegion);
       o.eroded = plane(kPEroded);
@@ -1160,6 +1182,9 @@ struct Engine::Impl {
       o.border_eroded = plane(kPBorderE);
     }
     launch_srg_morph(plane(kPBand), d_desc, nl, d_seeds, pc, o, s.max_w, s.max_h, s.stream);
+    if (measure_)
+      launch_measure(plane(kPDilated), plane(kPRegion), d_raw, d_desc, nl, cfg.pipe.measure_connectivity, s.d_measure,
+                     s.d_ms_scratch, s.max_w, s.max_h, s.stream);
     if (s.any_canvas) launch_render(d_raw, s.d_f32, s.d_bits, d_stats, d_rd, ncanv, cw, ch, s.d_canvas, s.stream);
     JpegRenderSrc rsrc;
     rsrc.raw = d_raw;
@@ -1229,6 +1254,15 @@ struct Engine::Impl {
     fallback = jpeg::encode_scan_rgb(rgb.data(), cw, ch, 3 * cw, t, (jpeg::Sampling)cfg.render.jpeg_sampling);
     if (fallbacks) ++*fallbacks;
     return false;
+  }
+
+  // Sidecar text of the batch's slice c from its K7 record (valid once the batch's kernels are done).
+  std::string measure_text(const Slot& s, int c) const {
+    const LoadedSlice& L = s.loaded[(size_t)s.live[(size_t)c]];
+    const SliceMeasure& m = s.h_measure[c];
+    if (m.components == 0xFFFFFFFFu) throw DeviceError("measure: slice exceeds the measurement scratch");
+    return measure::to_json(m, L.w, L.h, L.sx, L.sy, L.slope, L.intercept, cfg.pipe.apply_rescale,
+                            cfg.pipe.measure_connectivity);
   }
 
   // A slot thread waiting for a small batch's loads or exports spins up to 200 µs before sleeping:
@@ -1404,6 +1438,12 @@ struct Engine::Impl {
                 jpeg::write_jpeg_at(AT_FDCWD, std::string(), base + "_overlay.jpg", jpeg_header, seg, len,
                                     &dirs.creating[dirs.out_dir[item]]);
                 bytes_out += (int64_t)(jpeg_header.size() + len + 2);
+              }
+              if (measure_) {
+                const std::string js = measure_text(s, (int)c);
+                jpeg::write_bytes_at(AT_FDCWD, std::string(), base + "_measure.json", js.data(), js.size(),
+                                     &dirs.creating[dirs.out_dir[item]]);
+                bytes_out += (int64_t)js.size();
               }
             } catch (const std::exception& e) {
               status[item] = SliceStatus{kSliceExportError, std::string("Error in export stage: ") + e.what()};
@@ -1752,6 +1792,10 @@ struct Engine::Impl {
       r.jpeg_overlay.push_back(0xFF);
       r.jpeg_overlay.push_back(0xD9);
     }
+    if (measure_) {
+      r.measure = s.h_measure[0];
+      r.measure_json = measure_text(s, 0);
+    }
     return r;
   }
 
@@ -1763,6 +1807,8 @@ struct Engine::Impl {
   uint32_t ov_cap_ = 0;
   int32_t divs_chroma_[64] = {};
   uint32_t ov_color_ = 0;
+  // Measurements (PipelineParams::measure): K7 after K2 on every batch, a sidecar per slice.
+  bool measure_ = false;
 };
 
 Engine::Engine(const EngineConfig& cfg) : impl_(std::make_unique<Impl>(cfg)) {}
