@@ -26,8 +26,28 @@ def _check(t, dtypes, name):
 _U16 = (torch.int16, torch.uint16)
 
 
+# The limits the engine's constructor enforces (engine.cpp): the kernels have no instance, tap table
+# or shift width beyond them, so the wrappers reject such a configuration before any launch.
+def _check_median(k):
+    if int(k) not in (3, 5, 7, 9):
+        raise ValueError(f"median window must be 3, 5, 7 or 9 (got {k})")
+
+
+def _check_sharpen(cfg):
+    if not 1 <= int(cfg.sharpen_mask) <= 15 or int(cfg.sharpen_mask) % 2 == 0:
+        raise ValueError(f"sharpen mask must be odd and ≤ 15 (got {cfg.sharpen_mask})")
+
+
+def _check_morph(cfg):
+    if not (1 <= int(cfg.dilation_size) <= 63 and 1 <= int(cfg.erosion_size) <= 63):
+        raise ValueError(f"morphology sizes must be in [1, 63] (got {cfg.dilation_size}, {cfg.erosion_size})")
+    if not 0 <= int(cfg.border_radius) <= 31:
+        raise ValueError(f"border radius must be in [0, 31] (got {cfg.border_radius})")
+
+
 def median2d(raw, k=7, pixel_type="u16", stored_bits=16):
     """k×k median (clamp-to-edge) of raw 16-bit keys → same-shape tensor of median keys."""
+    _check_median(k)
     x = _as3d(raw)
     _check(x, _U16, "raw")
     n, h, w = x.shape
@@ -68,6 +88,7 @@ def sharpen_band(median_keys, config: PipelineConfig = None, pixel_type="u16", s
     """normalise+clip(median keys) → 9×9 Gaussian unsharp mask → SRG band test.
     Returns (sharpened f32 [N,H,W] or None, band bool [N,H,W])."""
     cfg = config or PipelineConfig()
+    _check_sharpen(cfg)
     x = _as3d(median_keys)
     _check(x, _U16, "median_keys")
     n, h, w = x.shape
@@ -87,6 +108,7 @@ def region_grow(band, seeds=None, config: PipelineConfig = None):
     """Seeded region growing on bool band [N,H,W] (LDS-resident ≤ 512², global-memory planes above) + dilation, erosion and the
     renderer border. Returns dict of bool tensors: region, dilated, eroded, border_region."""
     cfg = config or PipelineConfig()
+    _check_morph(cfg)
     b = _as3d(band)
     if not b.is_cuda:
         raise ValueError("band must be a CUDA tensor")

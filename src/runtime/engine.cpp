@@ -340,6 +340,9 @@ struct Engine::Impl {
       throw DeviceError("sharpen mask must be odd and ≤ 15");
     if (p.dilation_size < 1 || p.dilation_size > 63 || p.erosion_size < 1 || p.erosion_size > 63)
       throw DeviceError("morphology sizes must be in [1, 63]");
+    // The border erodes with a (2r + 1)-wide square, under the same size limit.
+    if (cfg.render.border_radius < 0 || cfg.render.border_radius > 31)
+      throw DeviceError("border radius must be in [0, 31]");
     pc.nmin = p.norm_min;
     pc.nmax = p.norm_max;
     pc.nlow = p.norm_low;

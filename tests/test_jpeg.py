@@ -72,6 +72,14 @@ def test_quality_tables(native, q):
     assert native.jpeg_encode_gray420(g, q) == _pil_bytes(g, q)
 
 
+# The reference of the GPU quality tests (tests/test_gpu_params.py), pinned for every layout.
+@pytest.mark.parametrize("sampling", [0, 1, 2])
+@pytest.mark.parametrize("q", [1, 10, 25, 50, 90, 95, 100])
+def test_quality_tables_every_sampling(native, q, sampling):
+    g = np.random.default_rng(q).integers(0, 256, size=(48, 80), dtype=np.uint8)
+    assert native.jpeg_encode_gray(g, q, sampling) == _pil_bytes(g, q, sampling)
+
+
 def test_decodes_and_psnr(native):
     raw = native.phantom_slice(256, 256, 1, 12, 25, 1).astype(np.float32)
     c = native.golden_render_gray(raw, float(raw.min()), float(raw.max()), 1.0, 1.0, 512, 512)

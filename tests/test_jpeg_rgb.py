@@ -22,7 +22,7 @@ def test_encode_rgb_matches_pillow(native, shape, kind, sampling):
 
 
 @pytest.mark.parametrize("sampling", [0, 1], ids=["420", "444"])
-@pytest.mark.parametrize("quality", [10, 50, 90, 100])
+@pytest.mark.parametrize("quality", [1, 10, 25, 50, 90, 95, 100])
 def test_encode_rgb_quality_matches_pillow(native, quality, sampling):
     rgb = rgb_image("noise", 64, 64, seed=quality)
     assert native.jpeg_encode_rgb(rgb, quality, sampling) == pillow_jpeg(rgb, quality, sampling)
