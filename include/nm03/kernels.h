@@ -85,7 +85,8 @@ void launch_srg_morph(const uint64_t* band, const SliceDesc* descs, int nslices,
 // ONE cooperative launch that decides convergence on the device (k5_volume.hip): no host
 // synchronisation. seeds_xyz: device int32 triples. d_ctl: kSrg3dCtlWords device words; h_ctl
 // (optional): pinned host words receiving them at the end of the launch — srg_volume_result(h_ctl)
-// after the stream is synchronised gives the sweep count (or throws). Planes too large for LDS
+// after the stream is synchronised gives the sweep count, or throws: the region is the fixpoint or
+// the call fails (the sweeps are bounded by the voxel count, a true bound). Planes too large for LDS
 // (a side > 512) need `scratch` of srg3d_scratch_words(w, h, d) words. reset = false continues from
 // the region already in `region` (⊆ band): the z-slab decomposition (volume_slabs.h) re-grows a slab
 // after neighbouring slabs contributed boundary voxels.
@@ -97,6 +98,9 @@ void srg_volume(const uint64_t* band, uint64_t* region, int w, int h, int d, con
 int srg_volume_result(const uint32_t* h_ctl);
 // Scratch for border_volume / dilate_volume when a plane does not fit LDS (else 0).
 size_t morph3d_scratch_words(int w, int h, int d);
+// Largest structuring-element size of the 3D morphology (the 2D engine's limit): the row shifts
+// combine a word with one neighbour on each side, so a radius stays below 64. Sizes are odd.
+constexpr int kMorph3dMaxSize = 63;
 // Per-plane renderer border of a bit volume: label ∧ ¬erode_{(2r+1)²}(label) (2D, every plane).
 void border_volume(const uint64_t* src, uint64_t* dst, int w, int h, int d, int radius, hipStream_t stream,
                    uint64_t* scratch = nullptr);

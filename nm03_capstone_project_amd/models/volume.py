@@ -1,5 +1,7 @@
 """3D mode (BASELINE config 5): a series as one volume, per-slice median/sharpen/band, 6- or
-26-connected seeded region growing by LDS plane sweeps, and separable cube dilation."""
+26-connected seeded region growing by LDS plane sweeps, and separable cube dilation (size odd, in
+[1, 63]). `run` raises ValueError for a connectivity other than 6 / 26 or a size outside that range
+(the native runner checks them before any launch)."""
 import numpy as np
 
 from .._native import native

@@ -126,13 +126,28 @@ def region_grow(band, seeds=None, config: PipelineConfig = None):
     return res
 
 
+# 3D mode (K5): the cube / ball size is odd and within the 2D engine's [1, 63] (the row shifts combine
+# a word with one neighbour on each side), the connectivity is 6 or 26.
+def _check_size3d(size):
+    if not 1 <= int(size) <= 63 or int(size) % 2 == 0:
+        raise ValueError(f"3D dilation size must be odd and in [1, 63] (got {size})")
+
+
+def _check_conn3d(connectivity):
+    if int(connectivity) not in (6, 26):
+        raise ValueError(f"3D connectivity must be 6 or 26 (got {connectivity})")
+
+
 def region_grow3d(band, seeds=(), connectivity=6, region=None):
-    """3D seeded region growing (K5 plane sweeps) on a bool band [D, H, W] (CUDA, H, W ≤ 512).
+    """3D seeded region growing (K5 plane sweeps; `connectivity` 6 or 26) on a bool band [D, H, W]
+    (CUDA, every side ≤ 4096; planes that do not fit LDS run on global-memory scratch).
     `seeds` are (x, y, z) voxels; `region` (bool [D, H, W], ⊆ band) is grown further instead of
     starting from nothing — the z-slab decomposition re-grows a slab after its neighbours added
-    boundary voxels. Returns (region bool [D, H, W], sweeps)."""
+    boundary voxels. Returns (region bool [D, H, W], sweeps): the region is the fixpoint — the sweeps
+    are bounded by the voxel count only, and a run that exhausted them would raise."""
     if band.dim() != 3 or not band.is_cuda:
         raise ValueError("band must be a CUDA tensor [D, H, W]")
+    _check_conn3d(connectivity)
     d, h, w = band.shape
     bw = pack_bits(band.bool()).contiguous()
     rw = pack_bits(region.bool() & band.bool()).contiguous() if region is not None else torch.zeros_like(bw)
@@ -143,13 +158,28 @@ def region_grow3d(band, seeds=(), connectivity=6, region=None):
 
 def dilate3d(mask, size=7, ball=False):
     """Cube dilation (size×size×size; `ball`: the digital ball of radius size//2) of a bool
-    [D, H, W] CUDA mask, out-of-volume samples ignored."""
+    [D, H, W] CUDA mask, out-of-volume samples ignored. `size` is odd and in [1, 63]."""
     if mask.dim() != 3 or not mask.is_cuda:
         raise ValueError("mask must be a CUDA tensor [D, H, W]")
+    _check_size3d(size)
     d, h, w = mask.shape
     src = pack_bits(mask.bool()).contiguous()
     dst, tmp = torch.empty_like(src), torch.empty_like(src)
     native().k_dilate3d(src.data_ptr(), dst.data_ptr(), tmp.data_ptr(), w, h, d, int(size), _stream(), bool(ball))
+    return unpack_bits(dst, w)
+
+
+def border3d(mask, radius=2):
+    """Renderer border of every plane of a bool [D, H, W] CUDA mask: mask ∧ ¬erode of the
+    (2·radius + 1)² square, in 2D per plane (out-of-plane samples ignored); radius in [0, 31]."""
+    if mask.dim() != 3 or not mask.is_cuda:
+        raise ValueError("mask must be a CUDA tensor [D, H, W]")
+    if not 0 <= int(radius) <= 31:
+        raise ValueError(f"border radius must be in [0, 31] (got {radius})")
+    d, h, w = mask.shape
+    src = pack_bits(mask.bool()).contiguous()
+    dst = torch.empty_like(src)
+    native().k_border3d(src.data_ptr(), dst.data_ptr(), w, h, d, int(radius), _stream())
     return unpack_bits(dst, w)
 
 

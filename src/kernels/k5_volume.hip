@@ -6,9 +6,11 @@
 // region bits, seeds from the two neighbouring planes (26-connectivity dilates them in-plane
 // first), and runs the same on-chip 2D fixpoint as K2 (srg_core.h: row run fills + transposed
 // column run fills). Because xz sweeps fill whole z-runs at once, the sweep count is ≈ the number
-// of direction turns of the region, not its z extent. Planes read neighbours while those are being
-// rewritten — harmless: the iteration is monotone (bits are only added, 64-bit words are written
-// atomically); a sweep that changes nothing proves the fixpoint.
+// of direction turns of the region, not its z extent — a path that turns between y and z at every
+// cell needs about one sweep per segment, so the only bound on the sweeps is the voxel count (see
+// srg_volume). Planes read neighbours while those are being rewritten — harmless: the iteration is
+// monotone (bits are only added, 64-bit words are written atomically); a sweep that changes
+// nothing proves the fixpoint.
 //
 // Convergence is decided ON THE DEVICE (FAST polls a stop flag from the host): ONE
 // cooperative launch of a persistent kernel runs every sweep; workgroups stride over the planes of
@@ -19,8 +21,12 @@
 //
 // Planes larger than LDS holds (any side > 512) run the same code on per-workgroup global scratch
 // (as K2 does for large 2D slices). Cube dilation is separable: in-plane square dilation (row
-// shifts + row ORs), then an OR over z. Out-of-volume samples are ignored (App. A.7).
+// shifts + row ORs), then an OR over z. Out-of-volume samples are ignored (App. A.7). Sizes are odd
+// and ≤ kMorph3dMaxSize: the row shifts look one word to each side, as in the 2D engine.
 #include <hip/hip_runtime.h>
+
+#include <climits>
+#include <string>
 
 #include "device_util.h"
 #include "nm03/gpu_types.h"
@@ -33,6 +39,8 @@ constexpr int kSrg3dThreads = 512;
 constexpr size_t kLdsBudget = 160 * 1024;  // LDS per workgroup on gfx950
 // Control words (kSrg3dCtlWords, zeroed before every launch).
 enum : int { kCtlBarCount = 0, kCtlBarGen = 1, kCtlChanged = 2 /* 3 words */, kCtlSweeps = 5, kCtlError = 6 };
+// Bits of the error word: the grid barrier's spin ran out; the sweeps ran out before the fixpoint.
+enum : uint32_t { kErrBarrier = 1u, kErrSweepCap = 2u };
 
 __global__ void srg3d_seed_kernel(const uint64_t* __restrict__ band, uint64_t* __restrict__ region, int w, int h,
                                   int d, const int32_t* __restrict__ seeds, int nseeds) {
@@ -116,7 +124,7 @@ __device__ bool grid_barrier(uint32_t* ctl, uint32_t nblocks) {
       while (__hip_atomic_load(&ctl[kCtlBarGen], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g) {
         if (++spins > (1u << 25) ||
             __hip_atomic_load(&ctl[kCtlError], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-          atomicOr(&ctl[kCtlError], 1u);
+          atomicOr(&ctl[kCtlError], kErrBarrier);
           ok = 0;
           break;
         }
@@ -140,6 +148,7 @@ __global__ __launch_bounds__(kSrg3dThreads) void srg3d_kernel(const uint64_t* __
   __shared__ int flag[2];  // srg_fixpoint's two alternating change words
   uint64_t* const planes = kGlobal ? scratch + (size_t)blockIdx.x * 4 * plane_words : lds_planes;
   int sweep = 0;
+  bool fixpoint = false;
   for (; sweep < max_sweeps; ++sweep) {
     const int axis = sweep & 1;
     const int nplanes = axis == 0 ? d : h;
@@ -155,10 +164,15 @@ __global__ __launch_bounds__(kSrg3dThreads) void srg3d_kernel(const uint64_t* __
     const uint32_t c = __hip_atomic_load(&ctl[kCtlChanged + sweep % 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (c == 0u) {  // nothing changed anywhere: the fixpoint
       ++sweep;
+      fixpoint = true;
       break;
     }
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) ctl[kCtlSweeps] = (uint32_t)sweep;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ctl[kCtlSweeps] = (uint32_t)sweep;
+    // Out of sweeps while the last one still added voxels: the region is not the fixpoint.
+    if (!fixpoint) atomicOr(&ctl[kCtlError], kErrSweepCap);
+  }
 }
 
 namespace {
@@ -225,7 +239,11 @@ void srg_volume(const uint64_t* band, uint64_t* region, int w, int h, int d, con
     check_launch("srg3d_seed_kernel");
   }
   const int grid = srg3d_grid(s, w, h, d);
-  int max_sweeps = 4 * (w + h + d);
+  // A true bound: every sweep but the last adds at least one voxel, so w·h·d + 1 sweeps always
+  // reach the fixpoint (a thin path that turns at every cell needs about one sweep per segment,
+  // far more than a multiple of w + h + d). Running out sets kErrSweepCap: srg_volume_result throws.
+  const long long vox = (long long)w * h * d + 1;
+  int max_sweeps = vox > INT_MAX ? INT_MAX : (int)vox;
   int plane_words = s.plane_words;
   void* args[] = {(void*)&band, (void*)&region, (void*)&w, (void*)&h, (void*)&d, (void*)&connectivity,
                   (void*)&plane_words, (void*)&d_ctl, (void*)&max_sweeps, (void*)&scratch};
@@ -239,7 +257,11 @@ void srg_volume(const uint64_t* band, uint64_t* region, int w, int h, int d, con
 }
 
 int srg_volume_result(const uint32_t* h_ctl) {
-  if (h_ctl[kCtlError]) throw DeviceError("3D region growing: grid barrier timed out (workgroups not co-resident)");
+  if (h_ctl[kCtlError] & kErrBarrier)
+    throw DeviceError("3D region growing: grid barrier timed out (workgroups not co-resident)");
+  if (h_ctl[kCtlError])
+    throw DeviceError("3D region growing: sweep limit reached before the fixpoint (" +
+                      std::to_string(h_ctl[kCtlSweeps]) + " sweeps)");
   return (int)h_ctl[kCtlSweeps];
 }
 
@@ -328,6 +350,8 @@ size_t morph3d_scratch_words(int w, int h, int d) {
 
 void border_volume(const uint64_t* src, uint64_t* dst, int w, int h, int d, int radius, hipStream_t stream,
                    uint64_t* scratch) {
+  if (radius < 0 || 2 * radius + 1 > kMorph3dMaxSize)
+    throw DeviceError("border_volume: radius must be in [0, " + std::to_string(kMorph3dMaxSize / 2) + "]");
   const int plane_words = morph_plane_words(w, h);
   if (morph_global(w, h)) {
     if (!scratch) throw DeviceError("border_volume: planes above the LDS size need scratch (morph3d_scratch_words)");
@@ -341,6 +365,8 @@ void border_volume(const uint64_t* src, uint64_t* dst, int w, int h, int d, int 
 
 void dilate_volume(const uint64_t* src, uint64_t* dst, uint64_t* tmp, int w, int h, int d, int size, hipStream_t stream,
                    uint64_t* scratch, bool ball) {
+  if (size < 1 || size > kMorph3dMaxSize || !(size & 1))
+    throw DeviceError("dilate_volume: size must be odd and in [1, " + std::to_string(kMorph3dMaxSize) + "]");
   const int n = (w + 63) / 64;
   const int words = h * n;
   if (ball) {

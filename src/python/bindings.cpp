@@ -1272,7 +1272,8 @@ PYBIND11_MODULE(_nm03, m) {
   m.def("k_dilate3d", [](uintptr_t src, uintptr_t dst, uintptr_t tmp, int w, int h, int d, int size, uintptr_t stream,
                          bool ball) {
     hipStream_t st = as_stream(stream);
-    if (size < 1 || !(size & 1)) throw std::invalid_argument("dilation size must be odd and >= 1");
+    if (size < 1 || size > gpu::kMorph3dMaxSize || !(size & 1))
+      throw std::invalid_argument("dilation size must be odd and in [1, " + std::to_string(gpu::kMorph3dMaxSize) + "]");
     void* scr = nullptr;
     if (const size_t sw = gpu::morph3d_scratch_words(w, h, d))
       gpu::check_hip(hipMalloc(&scr, sw * 8), "hipMalloc morph scratch");
@@ -1287,6 +1288,24 @@ PYBIND11_MODULE(_nm03, m) {
     if (scr) (void)hipFree(scr);
   }, py::arg("src"), py::arg("dst"), py::arg("tmp"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("size"),
      py::arg("stream"), py::arg("ball") = false);
+  // Per-plane renderer border (label ∧ ¬erode of the (2·radius + 1)² square) of a bit volume.
+  m.def("k_border3d", [](uintptr_t src, uintptr_t dst, int w, int h, int d, int radius, uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    if (radius < 0 || 2 * radius + 1 > gpu::kMorph3dMaxSize)
+      throw std::invalid_argument("border radius must be in [0, " + std::to_string(gpu::kMorph3dMaxSize / 2) + "]");
+    void* scr = nullptr;
+    if (const size_t sw = gpu::morph3d_scratch_words(w, h, d))
+      gpu::check_hip(hipMalloc(&scr, sw * 8), "hipMalloc morph scratch");
+    try {
+      gpu::border_volume((const uint64_t*)src, (uint64_t*)dst, w, h, d, radius, st, (uint64_t*)scr);
+      gpu::check_hip(hipStreamSynchronize(st), "k_border3d");
+    } catch (...) {
+      (void)hipStreamSynchronize(st);
+      if (scr) (void)hipFree(scr);
+      throw;
+    }
+    if (scr) (void)hipFree(scr);
+  });
   m.def("k_jpeg", [](uintptr_t canvas, int n, int h, int w, int quality, uintptr_t stream, int sampling) {
     hipStream_t st = as_stream(stream);
     const int blocks = (w / 8) * (h / 8);

@@ -11,6 +11,8 @@
 #include <fstream>
 #include <iostream>
 #include <sstream>
+#include <stdexcept>
+#include <string>
 
 #include "nm03/cohort.h"
 #include "nm03/comm.h"
@@ -135,6 +137,16 @@ struct VolumeDevice {
   }
 };
 
+// The 3D kernels' parameter limits, checked before anything is launched: the cube / ball size is odd
+// and at most kMorph3dMaxSize (the 2D engine's limit), the connectivity is 6 or 26.
+void check_volume_params(int connectivity, int dilation_size) {
+  if (connectivity != 6 && connectivity != 26)
+    throw std::invalid_argument("3D connectivity must be 6 or 26 (got " + std::to_string(connectivity) + ")");
+  if (dilation_size < 1 || dilation_size > kMorph3dMaxSize || !(dilation_size & 1))
+    throw std::invalid_argument("3D dilation size must be odd and in [1, " + std::to_string(kMorph3dMaxSize) +
+                                "] (got " + std::to_string(dilation_size) + ")");
+}
+
 }  // namespace
 
 static void volume_preprocess(VolumeDevice& V, const VolumeInput& v, const PipelineParams& p, const PipeConsts& pc) {
@@ -198,7 +210,7 @@ static void volume_segment(VolumeDevice& V, const VolumeInput& v, const VolumePa
   }
   check_hip(hipMemcpyAsync(V.seeds.p, sx.data(), sx.size() * 4, hipMemcpyHostToDevice, V.stream), "H2D seeds");
   srg_volume(V.band.as<uint64_t>(), V.region.as<uint64_t>(), v.w, v.h, v.d, V.seeds.as<int32_t>(),
-             (int)(sx.size() / 3), p.connectivity == 26 ? 26 : 6, V.flag.as<uint32_t>(), V.h_flag,
+             (int)(sx.size() / 3), p.connectivity, V.flag.as<uint32_t>(), V.h_flag,
              V.srg_scratch.as<uint64_t>(), V.stream);
   dilate_volume(V.region.as<uint64_t>(), V.dil.as<uint64_t>(), V.tmp.as<uint64_t>(), v.w, v.h, v.d, p.dilation_size,
                 V.stream, V.morph_scratch.as<uint64_t>(), p.pipe.se_shape == kSeDisc);
@@ -290,6 +302,7 @@ VolumeRunner::~VolumeRunner() = default;
 
 VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool want_masks) {
   if (v.d < 1 || v.w < 1 || v.h < 1) throw SliceError("empty volume");
+  check_volume_params(p.connectivity, p.dilation_size);
   Impl& I = *impl_;
   check_hip(hipSetDevice(I.device), "hipSetDevice");
   if (!I.V || I.V->w != v.w || I.V->h != v.h || I.V->d != v.d) {
@@ -451,6 +464,7 @@ static SlabStats slab_grow_dilate_gpu(Comm& comm, VolumeDevice& V, int nseeds, i
 VolumeResult VolumeRunner::run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p,
                                     bool want_masks, SlabStats* stats) {
   if (slab.d < 1 || slab.w < 1 || slab.h < 1) throw SliceError("empty slab");
+  check_volume_params(p.connectivity, p.dilation_size);
   Impl& I = *impl_;
   check_hip(hipSetDevice(I.device), "hipSetDevice");
   if (!I.V || I.V->w != slab.w || I.V->h != slab.h || I.V->d != slab.d) {
@@ -472,7 +486,7 @@ VolumeResult VolumeRunner::run_slab(Comm& comm, const VolumeInput& slab, int z0,
     }
   if (!sx.empty())
     check_hip(hipMemcpyAsync(V.seeds.p, sx.data(), sx.size() * 4, hipMemcpyHostToDevice, V.stream), "H2D seeds");
-  const int conn = p.connectivity == 26 ? 26 : 6;
+  const int conn = p.connectivity;
   if (depth < comm.size())
     throw std::runtime_error("z-slabs: volume depth " + std::to_string(depth) + " < " + std::to_string(comm.size()) +
                              " ranks leaves empty slabs");
@@ -761,6 +775,8 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
   const std::string base = cohort::cohort_dir(cfg.data_root);
   VolumeParams vp;
   vp.pipe = cfg.engine.pipe;
+  // --srg-connectivity defaults to the 2D value 4, which stands for 6 here (run_volume_cohort
+  // rejected everything but 4, 6 and 26).
   vp.connectivity = cfg.engine.pipe.srg_connectivity == 26 ? 26 : 6;
   // BASELINE config 5: 7×7×7 cube dilation unless --dilation-size was given.
   vp.dilation_size = cfg.dilation_set ? cfg.engine.pipe.dilation_size : 7;
@@ -1033,6 +1049,14 @@ int run_volume_cohort(const AppConfig& cfg) {
   // 3D variant of the cohort run (BASELINE config 5): each patient's series becomes one volume
   // (3D SRG + cube dilation on the GPU), exported per plane like the 2D run; patients are sharded
   // over the ranks (one process per MI355X) like the 2D work list.
+  // Both backends take the GPU kernels' limits, so --cpu stays the oracle of the same command.
+  try {
+    const int c = cfg.engine.pipe.srg_connectivity;
+    check_volume_params(c == 4 ? 6 : c, cfg.dilation_set ? cfg.engine.pipe.dilation_size : 7);
+  } catch (const std::invalid_argument& e) {
+    std::cerr << "--mode 3d: " << e.what() << std::endl;
+    return 2;
+  }
   LaunchOptions lo = LaunchOptions::from_env();
   int n = 1;
   if (cfg.cpu) {  // golden model: the ranks are CPU processes over the host comm (default 1)
