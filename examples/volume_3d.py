@@ -1,7 +1,7 @@
 """One DICOM series as a 3D volume on the MI355X: per-slice preprocessing, 6-connected 3D region
 growing and a 7×7×7 dilation (BASELINE config 5), checked against the golden 3D model.
 
-    python examples/volume_3d.py --series path/to/series_dir [--ball]
+    python examples/volume_3d.py --series path/to/series_dir [--ball] [--measure]
 """
 import argparse
 import os
@@ -17,14 +17,22 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--series", required=True)
     ap.add_argument("--ball", action="store_true", help="digital ball instead of the 7x7x7 cube")
+    ap.add_argument("--measure", action="store_true",
+                    help="also print the volumetry of the dilated volume (K8: mm3, components, cavities, tunnels)")
     a = ap.parse_args(argv)
-    vp = nm.VolumePipeline(nm.PipelineConfig(se_shape=int(a.ball)), connectivity=6, dilation=7)
+    vp = nm.VolumePipeline(nm.PipelineConfig(se_shape=int(a.ball)), connectivity=6, dilation=7, measure=a.measure)
     res = vp.run_series(a.series)
     band = res["band"]
     region, dil = vp.golden(band, vp.default_seeds(band))
     same = np.array_equal(res["region"], region) and np.array_equal(res["dilated"], dil)
     print(f"volume {tuple(band.shape)}: region {int(res['region'].sum())} voxels, dilated "
           f"{int(res['dilated'].sum())} voxels, GPU == golden: {same}")
+    if a.measure:
+        import json
+        m = json.loads(res["measure_json"])
+        print(f"volume {m['volume_ml']:.3f} ml ({m['volume_vox']} voxels, spacing_z {m['spacing_z']} mm from "
+              f"{m['spacing_z_source']}), surface {m['surface_mm2']:.1f} mm2, {m['components']} component(s), "
+              f"{m['cavities']} cavities, {m['tunnels']} tunnels")
     return 0 if same else 1
 
 

@@ -88,6 +88,10 @@ struct AppConfig {
   // --mode 3d --split-volume: every patient's volume is decomposed into z-slabs over all ranks
   // (volume_slabs.h) instead of sharding whole patients over the ranks.
   bool split_volume = false;
+  // --mode 3d --measure-volume: one volume_measure.json per patient and <out>/volumes.csv
+  // (nm03/measure.h VolumeMeasure); components at measure_volume_connectivity (6 | 26).
+  bool measure_volume = false;
+  int measure_volume_connectivity = 26;
   // CLOCK_REALTIME when parse_args began (the --json record's "main_unix_s"): with the launcher's
   // own clock it splits a cold run's wall into process start-up (exec → main) and the rest.
   double main_unix_s = 0;
@@ -143,6 +147,22 @@ struct MeasureTotals {
 MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients);
 std::string measure_totals_json(const MeasureTotals& t);  // the --json record's "measure" object
 const char* slice_status_name(int code);
+
+// --measure-volume (measurements.cpp): <out_root>/volumes.csv from the sidecar texts the ranks sent
+// with their outcomes, in plan order: a header, then one row per patient (patient, status, then the
+// volume sidecar's fields with bbox flattened; a failed patient has its status and empty fields).
+struct VolumePatientRow {
+  std::string id;
+  bool ok = false;
+  std::string sidecar;  // measure::volume_to_json text
+};
+struct VolumeTotals {
+  int64_t volumes = 0;  // patients with a sidecar
+  uint64_t volume_vox = 0;
+  double volume_mm3 = 0;
+};
+VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows);
+std::string volume_totals_json(const VolumeTotals& t);  // the --json record's "measure_volume" object
 
 // Number of GPUs visible to this process, counted WITHOUT initialising HIP (KFD topology +
 // HIP/ROCR_VISIBLE_DEVICES), so the launcher can still fork safely afterwards.

@@ -49,6 +49,8 @@ struct Header {
   bool has_position = false;
   double position[3] = {0, 0, 0};
   double slice_location = 0;
+  double slice_thickness = 0;          // SliceThickness (0018,0050), mm; 0 = absent
+  double spacing_between_slices = 0;   // SpacingBetweenSlices (0018,0088), mm; 0 = absent
   std::string photometric, transfer_syntax, sop_instance_uid, series_uid, patient_id, modality;
   Syntax syntax = Syntax::kExplicitLE;
   size_t pixel_offset = 0;  // byte offset of (7FE0,0010) value in the buffer (in *decoded when set)
@@ -173,9 +175,11 @@ struct WriteSpec {
   bool write_rescale = false;
   float slope = 1.f, intercept = 0.f;
   float spacing_x = 1.f, spacing_y = 1.f;
-  double slice_thickness = 1.0;
+  double slice_thickness = 1.0;          // ≤ 0: SliceThickness is not written
+  double spacing_between_slices = 0;     // > 0: SpacingBetweenSlices (0018,0088) is written
   int instance_number = 1;
   double position[3] = {0, 0, 0};
+  bool write_position = true;            // false: no ImagePositionPatient / SliceLocation
   std::string patient_id = "PGBM-000";
   std::string study_uid = "1.2.826.0.1.3680043.10.1", series_uid = "1.2.826.0.1.3680043.10.2",
               sop_uid = "1.2.826.0.1.3680043.10.3";

@@ -20,6 +20,10 @@
 #include "nm03/params.h"
 #include "nm03/pixel_math.h"
 
+namespace nm03 {
+struct VolumeInput;  // nm03/volume.h
+}
+
 namespace nm03::golden {
 
 struct SliceInput {
@@ -95,6 +99,16 @@ SliceMeasure measure(const std::vector<uint8_t>& dilated, const std::vector<uint
                      int connectivity);
 // The sidecar text of a record for slice `s` under `p` (measure::to_json with the slice's fields).
 std::string measure_json(const SliceMeasure& m, const SliceInput& s, const PipelineParams& p);
+
+// Measurements of a volume (VolumeParams::measure, nm03/measure.h VolumeMeasure): the record on the
+// `dilated` volume plus popcount(`region`) (0/1 per voxel, d planes of h × w), intensities from v.raw.
+// Plain per-voxel code that shares nothing with the K8 kernels' word arithmetic: components by flood
+// fill at `connectivity` (6 | 26), cavities by labelling the complement of the 1-voxel-padded mask at
+// the dual connectivity, the Euler number by per-voxel loops over the padded array.
+VolumeMeasure measure_volume(const std::vector<uint8_t>& dilated, const std::vector<uint8_t>& region, const VolumeInput& v,
+                             int connectivity);
+// The sidecar text of a record for volume `v` (measure::volume_to_json with the volume's fields).
+std::string measure_volume_json(const VolumeMeasure& m, const VolumeInput& v, bool apply_rescale, int connectivity);
 
 struct SliceResult {
   std::vector<float> clipped, median, sharpened;

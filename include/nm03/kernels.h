@@ -188,6 +188,24 @@ void launch_measure(const uint64_t* dilated, const uint64_t* region, const uint1
 // so a default run never pays for it — and no slot thread ever loads it lazily.
 void preload_measure();
 
+// K8 (k8_volume_measure.hip): the VolumeMeasure record (nm03/measure.h) of the `dilated` bit volume
+// (d planes of h rows of ceil(w / 64) words) plus popcount(`region`), the intensities from `raw`
+// (plane z at raw + z · raw_plane_stride). Twelve small launches on `stream` (multi-workgroup phases
+// separated by kernel boundaries; no host round trip, no allocation). `scratch`:
+// volume_measure_scratch_words(w, h, d) u32, no initialisation needed; `acc`: kVolumeMeasureAccWords
+// u64 of device memory; `out`: one record, written with plain vector stores (device, pinned or
+// host-mapped memory). Throws DeviceError before any launch for a volume whose (w + 1)·h·d + 1 slots
+// do not fit 32 bits, and for a connectivity other than 6 / 26.
+using nm03::volume_measure_scratch_words;
+constexpr int kVolumeMeasureAccWords = 32;
+void launch_volume_measure(const uint64_t* dilated, const uint64_t* region, const uint16_t* raw, size_t raw_plane_stride,
+                           int w, int h, int d, uint8_t type, uint8_t stored_bits, int connectivity, uint32_t* scratch,
+                           uint64_t* acc, VolumeMeasure* out, hipStream_t stream);
+// Loads K8's code object on the current device. Not part of preload_kernels: only a VolumeRunner's
+// first measuring run (before that run's first launch, while its stream is idle) and the Python op
+// (before its first launch) load it, so a run without --measure-volume never pays for it.
+void preload_volume_measure();
+
 // K6: binary threshold lo ≤ x ≤ hi → u8 0/1 (in 16-byte aligned, out 4-byte aligned).
 void launch_threshold(const float* in, uint8_t* out, size_t n, float lo, float hi, hipStream_t stream);
 

@@ -78,7 +78,106 @@ NM03_HD int32_t stored_sample(uint16_t raw_bits, uint8_t type, uint8_t stored_bi
   return (int32_t)(raw_bits & (uint16_t)(0xFFFFu >> sh));
 }
 
+// ---------------------------------------------------------------------------------------------
+// 3D volumetry (--measure-volume): the record the K8 kernels write for one volume. Exact integers,
+// measured on the DILATED volume (the mask the `_processed.jpg` planes show) plus the popcount of the
+// region volume; the derived doubles (mm³, mm², centroid, mean) exist only in measure::volume_to_json.
+// ---------------------------------------------------------------------------------------------
+struct alignas(64) VolumeMeasure {
+  uint64_t volume_vox;       // popcount(dilated)
+  uint64_t region_vox;       // popcount(region)
+  int32_t bbox[6];           // x0, y0, z0, x1, y1, z1 inclusive; all −1 for an empty mask
+  uint32_t components;       // connected components at the measurement connectivity (6 | 26)
+  uint32_t cavities;         // background components that reach no frame face, at the dual connectivity
+  uint64_t sum_x, sum_y, sum_z;        // coordinate sums over mask voxels
+  uint64_t faces_x, faces_y, faces_z;  // voxel faces normal to each axis between mask and non-mask / frame
+  uint64_t largest_vox;      // voxels of the largest component
+  int64_t euler;             // Euler number at the measurement connectivity (components − tunnels + cavities)
+  int64_t raw_sum;           // over the stored sample values under the mask (0 / 0 / 0 when empty)
+  int32_t raw_min, raw_max;
+};
+static_assert(sizeof(VolumeMeasure) == 128, "VolumeMeasure layout");
+
+// Euler number of a bit volume from window counts over the zero-padded volume: n3 = set voxels,
+// n2 = pairs of face-adjacent positions, n1 = 2×2 windows (three orientations), n0 = 2×2×2 windows.
+// At 26-connectivity a pair or window counts when ANY of its voxels is set and
+// euler = n0 − n1 + n2 − n3; at 6-connectivity when ALL are set and euler = n3 − n2 + n1 − n0.
+// The window whose highest corner is voxel (x, y, z) sits at bit x of word (y, z), as in 2D.
+struct EulerCounts {
+  uint64_t n2 = 0, n1 = 0, n0 = 0;
+};
+
+// 64 window positions at once. a[0..3]: the word of row (y, z), (y − 1, z), (y, z − 1), (y − 1, z − 1);
+// s[0..3]: the same rows one voxel to the left (bit x = voxel x − 1).
+NM03_HD void euler_accumulate(bool all, const uint64_t a[4], const uint64_t s[4], EulerCounts& e) {
+  uint64_t px, py, pz, wxy, wxz, wyz, cube;
+  if (all) {
+    px = a[0] & s[0], py = a[0] & a[1], pz = a[0] & a[2];
+    wxy = px & a[1] & s[1], wxz = px & a[2] & s[2], wyz = py & a[2] & a[3];
+    cube = wxy & a[2] & s[2] & a[3] & s[3];
+  } else {
+    px = a[0] | s[0], py = a[0] | a[1], pz = a[0] | a[2];
+    wxy = px | a[1] | s[1], wxz = px | a[2] | s[2], wyz = py | a[2] | a[3];
+    cube = wxy | a[2] | s[2] | a[3] | s[3];
+  }
+  e.n2 += (uint64_t)(__builtin_popcountll(px) + __builtin_popcountll(py) + __builtin_popcountll(pz));
+  e.n1 += (uint64_t)(__builtin_popcountll(wxy) + __builtin_popcountll(wxz) + __builtin_popcountll(wyz));
+  e.n0 += (uint64_t)__builtin_popcountll(cube);
+}
+
+// The windows of word k at position (y, z): `cur` / `prev` hold word k / k − 1 (0 for k = 0) of the
+// four rows in euler_accumulate's order, masked to the width and 0 outside the volume — so y = h and
+// z = d (the padding row and plane past the last voxel) are positions like any other. `closes_row`:
+// k is the last word and the width is a multiple of 64, so the windows right of the last voxel (bit 0
+// of a word that does not exist) are counted here.
+NM03_HD void euler_word(bool all, const uint64_t cur[4], const uint64_t prev[4], bool closes_row, EulerCounts& e) {
+  uint64_t s[4];
+  for (int r = 0; r < 4; ++r) s[r] = (cur[r] << 1) | (prev[r] >> 63);
+  euler_accumulate(all, cur, s, e);
+  if (closes_row) {
+    const uint64_t zero[4] = {0ull, 0ull, 0ull, 0ull};
+    for (int r = 0; r < 4; ++r) s[r] = cur[r] >> 63;
+    euler_accumulate(all, zero, s, e);
+  }
+}
+
+NM03_HD int64_t euler_from_counts(const EulerCounts& e, uint64_t n3, int connectivity) {
+  const int64_t v = (int64_t)n3 - (int64_t)e.n2 + (int64_t)e.n1 - (int64_t)e.n0;
+  return connectivity == 6 ? v : -v;
+}
+
+// Words of K8's labelling scratch: one slot per voxel plus one per row (rows are w + 1 slots apart),
+// one more for the last area slot. 0 when the slots cannot be named by 32-bit indices.
+inline size_t volume_measure_scratch_words(int w, int h, int d) {
+  if (w <= 0 || h <= 0 || d <= 0) return 0;
+  const uint64_t row_slots = ((uint64_t)w + 1) * (uint64_t)h;  // < 2^63
+  if (row_slots > (0xFFFFFFFFull - 1) / (uint64_t)d) return 0;  // (w + 1)·h·d + 1 ≥ 2^32
+  return (size_t)(row_slots * (uint64_t)d + 1);
+}
+
 namespace measure {
+
+// The sidecar text of a volume record (volume_measure.json): one JSON object on one line plus '\n',
+// keys in fixed order — width, height, depth, connectivity, the record's integers (bbox as
+// [x0, y0, z0, x1, y1, z1]), tunnels = components + cavities − euler, then spacing_x / _y / _z,
+// spacing_z_source and the derived doubles, each printed with %.9g:
+//   volume_mm3 = volume_vox · sx · sy · sz, volume_ml = volume_mm3 / 1000
+//   surface_mm2 = faces_x · sy · sz + faces_y · sx · sz + faces_z · sx · sy
+//   centroid_x / _y / _z = sum / volume_vox (voxel indices), centroid_*_mm = centroid · spacing
+//   mean = raw_sum / volume_vox, mapped through slope · v + intercept when apply_rescale
+// Centroids and mean are null for an empty mask. The GPU path, the --cpu path and the Python
+// bindings all call this one function.
+std::string volume_to_json(const VolumeMeasure& m, int w, int h, int d, double spacing_x, double spacing_y,
+                           double spacing_z, const std::string& spacing_z_source, float slope, float intercept,
+                           bool apply_rescale, int connectivity);
+
+// The record of a bit volume (d planes of h rows of wpr words) computed on the host with the word
+// arithmetic and the run union-find that the K8 kernels use (nm03/volume_measure_core.h), one word
+// after the other: what the kernels compute, without a GPU.
+VolumeMeasure volume_words(const uint64_t* dilated, const uint64_t* region, const uint16_t* raw, size_t raw_plane_stride,
+                           int w, int h, int d, int wpr, uint8_t type, uint8_t stored_bits, int connectivity);
+
+inline const char* volume_sidecar_name() { return "volume_measure.json"; }
 
 // Euler number of a bit plane (h rows of wpr words, bits past w ignored) from the quad counts above.
 int64_t euler_plane(const uint64_t* plane, int w, int h, int wpr, int connectivity);

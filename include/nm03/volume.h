@@ -11,6 +11,7 @@
 #include "nm03/app.h"
 #include "nm03/comm.h"
 #include "nm03/engine.h"
+#include "nm03/measure.h"
 
 namespace nm03 {
 
@@ -19,8 +20,33 @@ struct VolumeInput {
   PixelType type = kU16;
   int stored_bits = 16;
   float slope = 1.f, intercept = 0.f, spacing_x = 1.f, spacing_y = 1.f;
+  // Distance between consecutive planes (mm) and where it came from (series_spacing_z).
+  double spacing_z = 1.0;
+  std::string spacing_z_source = "default";
   std::vector<uint16_t> raw;  // d planes of h×w
 };
+
+// The plane spacing of a series from the headers of its first two planes' files (`second`: nullptr
+// when the first two planes come from one file, or there is one plane), by this rule, in order:
+//   "position"                both files have ImagePositionPatient and the Euclidean distance between
+//                             the two positions is > 0: that distance
+//   "spacing_between_slices"  SpacingBetweenSlices (0018,0088) > 0
+//   "slice_thickness"         SliceThickness (0018,0050) > 0
+//   "default"                 1.0
+// Whether the spacing is uniform over the series is not checked.
+namespace dicom {
+struct Header;
+}
+double series_spacing_z(const dicom::Header& first, const dicom::Header* second, std::string* source);
+
+// Geometry of a series without its pixels (the first two files' headers): PixelSpacing and the plane
+// spacing with its source, as load_volume sets them.
+struct SeriesGeometry {
+  float spacing_x = 1.f, spacing_y = 1.f;
+  double spacing_z = 1.0;
+  std::string spacing_z_source = "default";
+};
+SeriesGeometry series_geometry(const std::vector<std::string>& files);
 
 // Load a series directory's slices (ordered like the 2D path) as a volume; all slices must share
 // dimensions and pixel format.
@@ -31,6 +57,8 @@ struct VolumeResult {
   int sweeps = 0;
   std::vector<uint8_t> band, region, dilated;  // 0/1 per voxel (when requested)
   double kernels_s = 0;
+  VolumeMeasure measure = {};  // VolumeParams::measure: the K8 record of the dilated volume
+  double measure_s = 0;        // GPU time of the K8 launches (outside kernels_s)
 };
 
 struct VolumeExportStats {
@@ -44,6 +72,8 @@ struct VolumeParams {
   int dilation_size = 7;      // cube edge (7×7×7 in config 5)
   bool preprocess = true;     // median + sharpen per slice before the band test
   std::vector<Seed> seeds;    // empty → reference seed pattern on the middle slice
+  bool measure = false;           // also measure the dilated volume (K8, nm03/measure.h VolumeMeasure)
+  int measure_connectivity = 26;  // 6 | 26: components; cavities use the dual
 };
 
 // Runs the 3D pipeline on `device`; copies masks back when `want_masks`. A VolumeRunner keeps
@@ -55,6 +85,8 @@ class VolumeRunner {
   ~VolumeRunner();
   VolumeRunner(const VolumeRunner&) = delete;
   VolumeRunner& operator=(const VolumeRunner&) = delete;
+  // With p.measure the K8 kernels run after the segmentation (first use loads their code object and
+  // allocates their scratch, kept like the other buffers); without it nothing of K8 is touched.
   VolumeResult run(const VolumeInput& v, const VolumeParams& p, bool want_masks);
   // After run() on the same volume: the 2·d exported JPEG files of the 3D cohort mode, in plane
   // order (original, processed), rendered and encoded on the GPU (K3/K4) from the volume still on
@@ -66,6 +98,7 @@ class VolumeRunner {
   // coordinates. Preprocesses the slab's planes, runs the global region-growing fixpoint and the
   // halo cube dilation with the other ranks of `comm` (collective), leaving the slab on the device:
   // export_jpegs(slab, ...) then exports its planes. Masks (when requested) are the slab's.
+  // p.measure throws std::invalid_argument: components that cross slabs would need a collective.
   VolumeResult run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p, bool want_masks,
                         struct SlabStats* stats = nullptr);
 

@@ -1,39 +1,66 @@
 """3D mode (BASELINE config 5): a series as one volume, per-slice median/sharpen/band, 6- or
 26-connected seeded region growing by LDS plane sweeps, and separable cube dilation (size odd, in
 [1, 63]). `run` raises ValueError for a connectivity other than 6 / 26 or a size outside that range
-(the native runner checks them before any launch)."""
+(the native runner checks them before any launch).
+
+With `measure=True` every run also measures the dilated volume on the GPU (K8, nm03/measure.h
+VolumeMeasure): the result gains `measure` (the record's integers) and `measure_json` (the text of the
+CLI's volume_measure.json, from the one native volume_to_json)."""
 import numpy as np
 
 from .._native import native
 from .pipeline import PipelineConfig
 
 
+def _meta_args(meta):
+    meta = meta or {}
+    return dict(type=str(meta.get("type", "u16")), stored_bits=int(meta.get("stored_bits", 16)),
+                slope=float(meta.get("slope", 1.0)), intercept=float(meta.get("intercept", 0.0)))
+
+
 class VolumePipeline:
-    def __init__(self, config: PipelineConfig = None, connectivity: int = 6, dilation: int = 7):
+    def __init__(self, config: PipelineConfig = None, connectivity: int = 6, dilation: int = 7, measure: bool = False,
+                 measure_connectivity: int = 26):
         self.config = config or PipelineConfig()
         self.connectivity = connectivity
         self.dilation = dilation
+        self.measure = bool(measure)
+        self.measure_connectivity = int(measure_connectivity)
+        if self.measure_connectivity not in (6, 26):
+            raise ValueError(f"3D measurement connectivity must be 6 or 26 (got {measure_connectivity})")
         self._runners = {}  # device -> native VolumeRunner (buffers/stream reused across volumes)
 
     def default_seeds(self, volume):
         d, h, w = volume.shape
         return [(x, y, d // 2) for (x, y) in native().reference_seeds(w, h)]
 
-    def run(self, volume, seeds=None, device=None):
+    def run(self, volume, seeds=None, device=None, spacing=(1.0, 1.0, 1.0), spacing_z_source="default", meta=None):
+        """`spacing` = (sx, sy, sz) in mm and `spacing_z_source` only enter `measure_json`. `meta`
+        (type, stored_bits, slope, intercept as utils.read_slice gives them; default: unsigned 16-bit
+        samples, no rescale) says how the samples are stored."""
         vol = np.ascontiguousarray(volume, dtype=np.uint16)
         s = list(seeds) if seeds is not None else self.default_seeds(vol)
         dev = self.config.device if device is None else device
         runner = self._runners.get(dev)
         if runner is None:
             runner = self._runners[dev] = native().VolumeRunner(dev)
-        return runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s)
+        if not self.measure and meta is None:
+            return runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s)
+        return runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s, measure=self.measure,
+                          measure_connectivity=self.measure_connectivity, spacing=[float(v) for v in spacing],
+                          spacing_z_source=str(spacing_z_source), **_meta_args(meta))
 
     def run_series(self, series_dir, seeds=None, device=None):
         """A DICOM series directory as one volume (utils.read_series: the reference's file-number
-        order, every slice of one shape) through `run`."""
-        from ..utils.dicom import read_series
-        vol, _ = read_series(series_dir)
-        return self.run(vol, seeds=seeds, device=device)
+        order, every slice of one shape) through `run`. When measuring, the series' geometry
+        (utils.series_geometry) and the first slice's storage format go with it."""
+        from ..utils.dicom import read_series, series_geometry
+        vol, slices = read_series(series_dir)
+        if not self.measure:
+            return self.run(vol, seeds=seeds, device=device)
+        g = series_geometry(series_dir)
+        return self.run(vol, seeds=seeds, device=device, spacing=(g["spacing_x"], g["spacing_y"], g["spacing_z"]),
+                        spacing_z_source=g["spacing_z_source"], meta=slices[0].meta)
 
     def run_slabs(self, volume=None, comm=None, seeds=None, band=None, backend="gpu", gather=True, device=None):
         """The same pipeline on a volume split into z-slabs over the ranks of the native `comm` (one
@@ -54,3 +81,19 @@ class VolumePipeline:
         n = native()
         region = n.golden_region_grow3d(band, list(seeds), self.connectivity)
         return region, n.golden_dilate3d(region, self.dilation, self.config.se_shape == 1)
+
+    def golden_measure(self, dilated, region, raw, spacing=(1.0, 1.0, 1.0), spacing_z_source="default", meta=None):
+        """The golden model's record of `dilated` (+ popcount of `region`) over the samples `raw`
+        ([D, H, W] each) at this pipeline's measure_connectivity → (measure dict, measure_json text):
+        what `run` returns under those keys when measuring."""
+        n = native()
+        a = _meta_args(meta)
+        d, h, w = np.asarray(dilated).shape
+        rec = n.golden_measure_volume(np.ascontiguousarray(dilated, dtype=np.uint8),
+                                      np.ascontiguousarray(region, dtype=np.uint8),
+                                      np.ascontiguousarray(raw, dtype=np.uint16), a["type"], a["stored_bits"],
+                                      self.measure_connectivity)
+        text = n.volume_measure_to_json(rec, w, h, d, float(spacing[0]), float(spacing[1]), float(spacing[2]),
+                                        str(spacing_z_source), a["slope"], a["intercept"],
+                                        bool(self.config.pipeline_params().apply_rescale), self.measure_connectivity)
+        return rec, text

@@ -282,3 +282,28 @@ def measure_mask(dilated, region, raw, connectivity=8, pixel_type="u16", stored_
     samples = torch.cat(xs).contiguous()
     return native().k_measure(planes.data_ptr(), samples.data_ptr(), hs, ws, pixel_type, int(stored_bits),
                               int(connectivity), _stream())
+
+
+def measure_volume(dilated, region, raw, connectivity=26, pixel_type="u16", stored_bits=16):
+    """Measurements of a volume mask (K8, nm03/measure.h VolumeMeasure) → dict of the record's integers:
+    volume_vox, region_vox, bbox [x0, y0, z0, x1, y1, z1], sum_x / _y / _z, faces_x / _y / _z, components,
+    largest_vox, cavities, euler (on `dilated`, components at `connectivity` 6 | 26, cavities at its
+    dual), raw_sum / raw_min / raw_max (the stored samples of `raw` under `dilated`) and region_vox =
+    popcount(`region`).
+
+    `dilated`, `region` (bool) and `raw` (16-bit storage) are CUDA tensors [D, H, W] of one shape. The
+    phases are separate launches of many workgroups; a volume with (W + 1)·H·D + 1 ≥ 2³² raises."""
+    _check_conn3d(connectivity)
+    if dilated.dim() != 3 or region.shape != dilated.shape or raw.shape != dilated.shape:
+        raise ValueError("dilated, region and raw must be [D, H, W] of one shape")
+    if not (dilated.is_cuda and region.is_cuda):
+        raise ValueError("masks must be CUDA (HIP) tensors")
+    x = raw.contiguous()
+    _check(x, _U16, "raw")
+    d, h, w = (int(v) for v in dilated.shape)
+    if d < 1 or h < 1 or w < 1:
+        raise ValueError("empty volume")
+    dw = pack_bits(dilated.bool()).contiguous()
+    rw = pack_bits(region.bool()).contiguous()
+    return native().k_measure_volume(dw.data_ptr(), rw.data_ptr(), x.data_ptr(), w, h, d, pixel_type, int(stored_bits),
+                                     int(connectivity), _stream())

@@ -255,6 +255,84 @@ def measure(dilated, region, raw, connectivity=8, pixel_type="u16", stored_bits=
     }
 
 
+def measure_volume(dilated, region, raw, connectivity=26, pixel_type="u16", stored_bits=16):
+    """The volume record (nm03/measure.h VolumeMeasure) in NumPy + scipy.ndimage.label: a third
+    implementation beside the golden model's flood fill and the K8 kernels' union-find. `dilated`,
+    `region`: [D, H, W] masks (torch or NumPy, any device); `raw`: [D, H, W] 16-bit storage. Components
+    are labelled at `connectivity` (6 | 26: generate_binary_structure(3, 1 | 3)); cavities are the
+    components of the COMPLEMENT of the 1-voxel-padded mask at the dual connectivity, minus the outer
+    one. The Euler number comes from the window counts over the zero-padded volume: n3 voxels, n2
+    face-adjacent pairs, n1 2×2 windows (three orientations), n0 2×2×2 windows, a pair or window
+    counting when ANY of its voxels is set at 26-connectivity (euler = n0 − n1 + n2 − n3) and when ALL
+    are at 6-connectivity (euler = n3 − n2 + n1 − n0). Returns the dict ops.measure_volume gives."""
+    import numpy as np
+    from scipy import ndimage  # imported lazily: only this reference needs SciPy
+
+    def to_np(t):
+        return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+    if connectivity not in (6, 26):
+        raise ValueError("connectivity must be 6 or 26")
+    m = to_np(dilated).astype(bool)
+    if m.ndim != 3:
+        raise ValueError("dilated must be [D, H, W]")
+    s6, s26 = ndimage.generate_binary_structure(3, 1), ndimage.generate_binary_structure(3, 3)
+    lab, ncomp = ndimage.label(m, structure=s26 if connectivity == 26 else s6)
+    sizes = np.bincount(lab.ravel())[1:] if ncomp else np.zeros(0, dtype=np.int64)
+    _, nbg = ndimage.label(~np.pad(m, 1), structure=s6 if connectivity == 26 else s26)
+    zs, ys, xs = np.nonzero(m)
+    p = np.pad(m, 1)
+    core = p[1:-1, 1:-1, 1:-1]
+    faces = [int((core & ~lo).sum()) + int((core & ~hi).sum())
+             for lo, hi in ((p[1:-1, 1:-1, :-2], p[1:-1, 1:-1, 2:]), (p[1:-1, :-2, 1:-1], p[1:-1, 2:, 1:-1]),
+                            (p[:-2, 1:-1, 1:-1], p[2:, 1:-1, 1:-1]))]
+    # Windows of the padded volume, named by their highest corner: q[z, y, x] ↔ voxels z − 1 … z etc.
+    hi, lo = slice(1, None), slice(None, -1)
+    comb = np.logical_and if connectivity == 6 else np.logical_or
+
+    def count(*parts):
+        acc = parts[0]
+        for q in parts[1:]:
+            acc = comb(acc, q)
+        return int(acc.sum())
+
+    v = {(dz, dy, dx): p[(lo if dz else hi), (lo if dy else hi), (lo if dx else hi)]
+         for dz in (0, 1) for dy in (0, 1) for dx in (0, 1)}
+    n3 = int(m.sum())
+    n2 = count(v[0, 0, 0], v[0, 0, 1]) + count(v[0, 0, 0], v[0, 1, 0]) + count(v[0, 0, 0], v[1, 0, 0])
+    n1 = (count(v[0, 0, 0], v[0, 0, 1], v[0, 1, 0], v[0, 1, 1]) + count(v[0, 0, 0], v[0, 0, 1], v[1, 0, 0], v[1, 0, 1]) +
+          count(v[0, 0, 0], v[0, 1, 0], v[1, 0, 0], v[1, 1, 0]))
+    n0 = count(*v.values())
+    euler = n3 - n2 + n1 - n0 if connectivity == 6 else n0 - n1 + n2 - n3
+    raw_v = to_np(raw).view(np.uint16).astype(np.int64)
+    sh = 16 - int(stored_bits)
+    if pixel_type == "i16":
+        raw_v = ((raw_v << sh) & 0xFFFF).astype(np.uint16).view(np.int16).astype(np.int64) >> sh
+    else:
+        raw_v = raw_v & (0xFFFF >> sh)
+    under = raw_v[m]
+    any_vox = bool(m.any())
+    return {
+        "volume_vox": n3,
+        "region_vox": int(to_np(region).astype(bool).sum()),
+        "bbox": ([int(xs.min()), int(ys.min()), int(zs.min()), int(xs.max()), int(ys.max()), int(zs.max())]
+                 if any_vox else [-1] * 6),
+        "sum_x": int(xs.sum()),
+        "sum_y": int(ys.sum()),
+        "sum_z": int(zs.sum()),
+        "faces_x": faces[0],
+        "faces_y": faces[1],
+        "faces_z": faces[2],
+        "components": int(ncomp),
+        "largest_vox": int(sizes.max()) if ncomp else 0,
+        "cavities": int(nbg) - 1,
+        "euler": int(euler),
+        "raw_sum": int(under.sum()) if any_vox else 0,
+        "raw_min": int(under.min()) if any_vox else 0,
+        "raw_max": int(under.max()) if any_vox else 0,
+    }
+
+
 def psnr(a, b):
     mse = ((a.double() - b.double()) ** 2).mean().item()
     return math.inf if mse == 0 else 10 * math.log10(255.0 ** 2 / mse)

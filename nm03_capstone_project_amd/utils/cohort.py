@@ -112,3 +112,20 @@ def read_measurements(out_dir):
             rows.append({k: v if k in text else None if v == "" else float(v) if k in floats else int(v)
                          for k, v in r.items()})
     return rows
+
+
+def read_volume_measurements(out_dir):
+    """Rows of <out_dir>/volumes.csv (written by the 3D CLI with --measure-volume) as dicts keyed by
+    the header: one per patient in plan order (`status` "ok", or "failed" and then empty fields).
+    Integer columns come back as int, spacings and the derived ones as float, empty fields as None."""
+    import csv
+    import os
+    floats = {"spacing_x", "spacing_y", "spacing_z", "volume_mm3", "volume_ml", "surface_mm2", "centroid_x",
+              "centroid_y", "centroid_z", "centroid_x_mm", "centroid_y_mm", "centroid_z_mm", "mean"}
+    text = {"patient", "status", "spacing_z_source"}
+    rows = []
+    with open(os.path.join(out_dir, "volumes.csv"), newline="") as f:
+        for r in csv.DictReader(f):
+            rows.append({k: v if k in text else None if v == "" else float(v) if k in floats else int(v)
+                         for k, v in r.items()})
+    return rows

@@ -72,6 +72,18 @@ def series_files(series_dir):
     return [os.path.join(series_dir, f) for f in names]
 
 
+def series_geometry(series_dir):
+    """Geometry of a series directory from the headers of its first two slices: dict with spacing_x,
+    spacing_y (PixelSpacing), spacing_z (mm between consecutive planes) and spacing_z_source — how
+    spacing_z was found, in this order: "position" (distance between the first two slices'
+    ImagePositionPatient, when both have one and it is > 0), "spacing_between_slices",
+    "slice_thickness", or "default" (1.0). This is what the 3D CLI's load gives its volume."""
+    files = series_files(series_dir)
+    if not files:
+        raise ValueError(f"no .dcm files in {series_dir}")
+    return dict(native().series_geometry(files))
+
+
 def read_series(series_dir, min_dim=0):
     """→ (uint16 [D, H, W] volume of stored samples, [Slice] without pixel copies kept twice).
 

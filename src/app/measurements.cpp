@@ -37,7 +37,7 @@ constexpr size_t kColAreaPx = 3, kColAreaMm2 = 18;
 // The values of one sidecar line in column order ("" for null). The text is this program's own
 // (one flat object, one array of four integers): values are what stands between ':' or ',' and the
 // next ',' / ']' / '}'.
-bool parse_sidecar(const std::string& text, std::vector<std::string>& out) {
+bool parse_sidecar(const std::string& text, std::vector<std::string>& out, size_t columns = kNumColumns) {
   out.clear();
   size_t i = text.find('{');
   if (i == std::string::npos) return false;
@@ -63,10 +63,55 @@ bool parse_sidecar(const std::string& text, std::vector<std::string>& out) {
       i = vend;
     }
   }
-  return out.size() == kNumColumns;
+  return out.size() == columns;
 }
 
+// --measure-volume: the columns after patient, status — the volume sidecar's keys in its order, bbox flattened.
+const char* const kVolumeColumns[] = {
+    "width",      "height",      "depth",      "connectivity", "volume_vox", "region_vox",  "bbox_x0",       "bbox_y0",
+    "bbox_z0",    "bbox_x1",     "bbox_y1",    "bbox_z1",      "sum_x",      "sum_y",       "sum_z",         "faces_x",
+    "faces_y",    "faces_z",     "components", "largest_vox",  "cavities",   "euler",       "raw_sum",       "raw_min",
+    "raw_max",    "tunnels",     "spacing_x",  "spacing_y",    "spacing_z",  "spacing_z_source", "volume_mm3", "volume_ml",
+    "surface_mm2", "centroid_x", "centroid_y", "centroid_z",   "centroid_x_mm", "centroid_y_mm", "centroid_z_mm", "mean"};
+constexpr size_t kNumVolumeColumns = sizeof(kVolumeColumns) / sizeof(kVolumeColumns[0]);
+constexpr size_t kVolColVox = 4, kVolColMm3 = 30;
+
 }  // namespace
+
+VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows) {
+  VolumeTotals tot;
+  std::ostringstream o;
+  o << "patient,status";
+  for (const char* c : kVolumeColumns) o << "," << c;
+  o << "\n";
+  for (const auto& r : rows) {
+    std::vector<std::string> v;
+    const bool have = r.ok && parse_sidecar(r.sidecar, v, kNumVolumeColumns);
+    o << r.id << "," << (r.ok ? (have ? "ok" : "no_sidecar") : "failed");
+    for (size_t c = 0; c < kNumVolumeColumns; ++c) {
+      std::string x = have ? v[c] : std::string();
+      if (x.size() >= 2 && x.front() == '"' && x.back() == '"') x = x.substr(1, x.size() - 2);
+      o << "," << x;
+    }
+    o << "\n";
+    if (!have) continue;
+    ++tot.volumes;
+    tot.volume_vox += std::strtoull(v[kVolColVox].c_str(), nullptr, 10);
+    tot.volume_mm3 += std::strtod(v[kVolColMm3].c_str(), nullptr);
+  }
+  const std::string text = o.str();
+  std::ofstream f(cohort::with_slash(out_root) + "volumes.csv", std::ios::binary | std::ios::trunc);
+  f.write(text.data(), (std::streamsize)text.size());
+  if (!f) throw std::runtime_error("Cannot write " + cohort::with_slash(out_root) + "volumes.csv");
+  return tot;
+}
+
+std::string volume_totals_json(const VolumeTotals& t) {
+  char buf[200];
+  std::snprintf(buf, sizeof buf, "{\"volumes\": %lld, \"volume_vox_total\": %llu, \"volume_mm3_total\": %.9g}",
+                (long long)t.volumes, (unsigned long long)t.volume_vox, t.volume_mm3);
+  return buf;
+}
 
 MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients) {
   MeasureTotals tot;

@@ -62,6 +62,10 @@ void usage(const std::string& which) {
             << "  --measure              also write per-slice measurements of the dilated mask: <stem>_measure.json and\n"
             << "                         <out>/measurements.csv; test_pipeline: measure.json (2D only)\n"
             << "  --measure-connectivity 4|8  connectivity of the component count (default 8; holes use the dual)\n"
+            << "  --measure-volume       3d: also write the volumetry of each patient's dilated volume (voxels, mm3,\n"
+            << "                         surface, components, cavities, tunnels): <patient>/volume_measure.json and\n"
+            << "                         <out>/volumes.csv (needs --mode 3d; not with --split-volume)\n"
+            << "  --measure-volume-connectivity 6|26  connectivity of the 3D component count (default 26; cavities use the dual)\n"
             << "  --mode 2d|3d           3d: whole series as a volume (SRG 6-conn + cube dilation)\n"
             << "  --split-volume         3d: each volume split into z-slabs over all ranks (halo exchange)\n"
             << "  --input FILE           test_pipeline: slice to process\n"
@@ -246,6 +250,15 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
     else if (a == "--split-volume") c.split_volume = true;
     else if (a == "--overlay") c.engine.render.overlay = true;
     else if (a == "--measure") c.engine.pipe.measure = true;
+    else if (a == "--measure-volume") c.measure_volume = true;
+    else if (a == "--measure-volume-connectivity") {
+      const std::string v = val();
+      if (v != "6" && v != "26") {
+        std::cerr << "--measure-volume-connectivity must be 6 or 26" << std::endl;
+        std::exit(2);
+      }
+      c.measure_volume_connectivity = v == "6" ? 6 : 26;
+    }
     else if (a == "--measure-connectivity") {
       const std::string v = val();
       if (v != "4" && v != "8") {
@@ -288,7 +301,15 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
     std::exit(2);
   }
   if (c.engine.pipe.measure && c.mode == "3d") {
-    std::cerr << "--measure is not available with --mode 3d" << std::endl;
+    std::cerr << "--measure is not available with --mode 3d (use --measure-volume)" << std::endl;
+    std::exit(2);
+  }
+  if (c.measure_volume && c.mode != "3d") {
+    std::cerr << "--measure-volume needs --mode 3d (per-slice measurements: --measure)" << std::endl;
+    std::exit(2);
+  }
+  if (c.measure_volume && c.split_volume) {
+    std::cerr << "--measure-volume is not available with --split-volume" << std::endl;
     std::exit(2);
   }
   if (c.engine.render.overlay && c.mode == "3d") {

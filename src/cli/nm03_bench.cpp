@@ -38,6 +38,8 @@ int main(int argc, char** argv) {
   int steps = 10, warmup = 2;
   nm03::EngineConfig ec;
   int dil3d = 7;
+  bool measure_volume = false;  // volume: also K8 (the volumetry of the dilated volume) per run
+  int measure_volume_conn = 26;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto v = [&] { return std::string(argv[++i]); };
@@ -62,6 +64,8 @@ int main(int argc, char** argv) {
     else if (a == "--overlay") ec.render.overlay = true;  // cohort: also the colour overlay per slice
     else if (a == "--measure") ec.pipe.measure = true;    // cohort: also K7 and the measurement sidecar per slice
     else if (a == "--measure-connectivity") ec.pipe.measure_connectivity = std::atoi(v().c_str()) == 4 ? 4 : 8;
+    else if (a == "--measure-volume") measure_volume = true;
+    else if (a == "--measure-volume-connectivity") measure_volume_conn = std::atoi(v().c_str()) == 6 ? 6 : 26;
     else if (a == "--se-shape") ec.pipe.se_shape = v() == "disc" ? nm03::kSeDisc : nm03::kSeSquare;
     else if (a == "--render-filter") ec.render.filter = v() == "nearest" ? nm03::kFilterNearest : nm03::kFilterBilinear;
     else {
@@ -155,15 +159,20 @@ int main(int argc, char** argv) {
       nm03::VolumeParams vp;
       vp.pipe = ec.pipe;
       vp.dilation_size = dil3d;
+      vp.measure = measure_volume;
+      vp.measure_connectivity = measure_volume_conn;
       nm03::VolumeRunner runner(ec.device);
       for (int w = 0; w < warmup; ++w) runner.run(v, vp, false);
-      double ks = 0;
+      double ks = 0, ms = 0;
       int sweeps = 0;
+      nm03::VolumeMeasure vm = {};
       const double t0 = now_s();
       for (int k = 0; k < steps; ++k) {
         auto r = runner.run(v, vp, false);
         ks += r.kernels_s;
+        ms += r.measure_s;
         sweeps = r.sweeps;
+        vm = r.measure;
       }
       const double dt = now_s() - t0;
       // + the GPU export of every plane (render + JPEG, both images), as the 3D CLI does
@@ -178,7 +187,11 @@ int main(int argc, char** argv) {
       std::cout << "{\"config\": \"volume\", \"dims\": [" << v.w << ", " << v.h << ", " << v.d << "], \"steps\": " << steps
                 << ", \"ms_per_volume\": " << dt * 1e3 / steps << ", \"gpu_ms_per_volume\": " << ks * 1e3 / steps
                 << ", \"sweeps\": " << sweeps << ", \"ms_per_volume_with_export\": " << dt2 * 1e3 / steps
-                << ", \"export_ms_per_volume\": " << xs.export_s * 1e3 / steps << "}" << std::endl;
+                << ", \"export_ms_per_volume\": " << xs.export_s * 1e3 / steps;
+      if (measure_volume)
+        std::cout << ", \"measure_ms_per_volume\": " << ms * 1e3 / steps << ", \"volume_vox\": " << vm.volume_vox
+                  << ", \"components\": " << vm.components << ", \"cavities\": " << vm.cavities;
+      std::cout << "}" << std::endl;
     } else if (config == "volume-cpu") {
       if (pids.empty()) throw std::runtime_error("no patients");
       auto s = nm03::cohort::list_patient_series(base, pids[0]);

@@ -446,6 +446,16 @@ Header parse_prefix(const uint8_t* data, size_t avail, size_t size) {
       case 0x00080018: h.sop_instance_uid = str_value(c, e); break;
       case 0x00080060: h.modality = str_value(c, e); break;
       case 0x00100020: h.patient_id = str_value(c, e); break;
+      case 0x00180050: {
+        auto v = ds_values(str_value(c, e));
+        if (!v.empty() && v[0] > 0) h.slice_thickness = v[0];
+        break;
+      }
+      case 0x00180088: {
+        auto v = ds_values(str_value(c, e));
+        if (!v.empty() && v[0] > 0) h.spacing_between_slices = v[0];
+        break;
+      }
       case 0x0020000E: h.series_uid = str_value(c, e); break;
       case 0x00200013: h.instance_number = std::atoi(str_value(c, e).c_str()); break;
       case 0x00200032: {
@@ -923,14 +933,16 @@ std::vector<uint8_t> write(const WriteSpec& s) {
   out.str(0x0008, 0x0060, "CS", s.modality, ex);
   out.str(0x0010, 0x0010, "PN", "SYNTHETIC^" + s.patient_id, ex);
   out.str(0x0010, 0x0020, "LO", s.patient_id, ex);
-  out.str(0x0018, 0x0050, "DS", fmt_ds(s.slice_thickness), ex);
+  if (s.slice_thickness > 0) out.str(0x0018, 0x0050, "DS", fmt_ds(s.slice_thickness), ex);
+  if (s.spacing_between_slices > 0) out.str(0x0018, 0x0088, "DS", fmt_ds(s.spacing_between_slices), ex);
   out.str(0x0020, 0x000D, "UI", s.study_uid, ex);
   out.str(0x0020, 0x000E, "UI", s.series_uid, ex);
   out.str(0x0020, 0x0013, "IS", std::to_string(s.instance_number), ex);
-  out.str(0x0020, 0x0032, "DS",
-          fmt_ds(s.position[0]) + "\\" + fmt_ds(s.position[1]) + "\\" + fmt_ds(s.position[2]), ex);
+  if (s.write_position)
+    out.str(0x0020, 0x0032, "DS",
+            fmt_ds(s.position[0]) + "\\" + fmt_ds(s.position[1]) + "\\" + fmt_ds(s.position[2]), ex);
   out.str(0x0020, 0x0037, "DS", "1\\0\\0\\0\\1\\0", ex);
-  out.str(0x0020, 0x1041, "DS", fmt_ds(s.position[2]), ex);
+  if (s.write_position) out.str(0x0020, 0x1041, "DS", fmt_ds(s.position[2]), ex);
   out.us(0x0028, 0x0002, 1, ex);
   out.str(0x0028, 0x0004, "CS", s.photometric, ex);
   if (frames > 1) out.str(0x0028, 0x0008, "IS", std::to_string(frames), ex);

@@ -248,11 +248,96 @@ SliceMeasure measure_from(const py::dict& d) {
   return m;
 }
 
+// The integers of a volume record (nm03/measure.h VolumeMeasure) as a dict.
+py::dict volume_measure_dict(const VolumeMeasure& m) {
+  py::dict d;
+  d["volume_vox"] = m.volume_vox;
+  d["region_vox"] = m.region_vox;
+  py::list bb;
+  for (int k = 0; k < 6; ++k) bb.append(m.bbox[k]);
+  d["bbox"] = bb;
+  d["sum_x"] = m.sum_x;
+  d["sum_y"] = m.sum_y;
+  d["sum_z"] = m.sum_z;
+  d["faces_x"] = m.faces_x;
+  d["faces_y"] = m.faces_y;
+  d["faces_z"] = m.faces_z;
+  d["components"] = m.components;
+  d["largest_vox"] = m.largest_vox;
+  d["cavities"] = m.cavities;
+  d["euler"] = m.euler;
+  d["raw_sum"] = m.raw_sum;
+  d["raw_min"] = m.raw_min;
+  d["raw_max"] = m.raw_max;
+  return d;
+}
+
+VolumeMeasure volume_measure_from(const py::dict& d) {
+  VolumeMeasure m{};
+  m.volume_vox = d["volume_vox"].cast<uint64_t>();
+  m.region_vox = d["region_vox"].cast<uint64_t>();
+  const std::vector<int> bb = d["bbox"].cast<std::vector<int>>();
+  if (bb.size() != 6) throw std::invalid_argument("bbox must have six values");
+  for (int k = 0; k < 6; ++k) m.bbox[k] = bb[(size_t)k];
+  m.sum_x = d["sum_x"].cast<uint64_t>();
+  m.sum_y = d["sum_y"].cast<uint64_t>();
+  m.sum_z = d["sum_z"].cast<uint64_t>();
+  m.faces_x = d["faces_x"].cast<uint64_t>();
+  m.faces_y = d["faces_y"].cast<uint64_t>();
+  m.faces_z = d["faces_z"].cast<uint64_t>();
+  m.components = d["components"].cast<uint32_t>();
+  m.largest_vox = d["largest_vox"].cast<uint64_t>();
+  m.cavities = d["cavities"].cast<uint32_t>();
+  m.euler = d["euler"].cast<int64_t>();
+  m.raw_sum = d["raw_sum"].cast<int64_t>();
+  m.raw_min = d["raw_min"].cast<int32_t>();
+  m.raw_max = d["raw_max"].cast<int32_t>();
+  return m;
+}
+
+// [D, H, W] 0/1 bytes → bit volume (d planes of h rows of ceil(w / 64) words, LSB = left-most voxel).
+std::vector<uint64_t> pack_volume(const py::array_t<uint8_t, py::array::c_style | py::array::forcecast>& a) {
+  const int d = (int)a.shape(0), h = (int)a.shape(1), w = (int)a.shape(2), wpr = (w + 63) / 64;
+  std::vector<uint64_t> words((size_t)d * h * wpr, 0ull);
+  const uint8_t* p = a.data();
+  for (int z = 0; z < d; ++z)
+    for (int y = 0; y < h; ++y)
+      for (int x = 0; x < w; ++x)
+        if (p[((size_t)z * h + y) * w + x]) words[((size_t)z * h + y) * wpr + (x >> 6)] |= 1ull << (x & 63);
+  return words;
+}
+
+// The fields of a volume beyond its samples that the Python surface passes to the 3D runner.
+struct VolumeMeta {
+  std::string type = "u16";
+  int stored_bits = 16;
+  float slope = 1.f, intercept = 0.f;
+  std::vector<double> spacing = {1.0, 1.0, 1.0};  // x, y, z (mm)
+  std::string spacing_z_source = "default";
+  bool measure = false;
+  int measure_connectivity = 26;
+};
+
+void apply_meta(const VolumeMeta& mt, VolumeInput& v) {
+  if (mt.spacing.size() != 3) throw std::invalid_argument("spacing must be (sx, sy, sz)");
+  const PixelType t = parse_type(mt.type);
+  v.type = t == kU8 ? kU16 : t;
+  if (mt.stored_bits < 1 || mt.stored_bits > 16) throw std::invalid_argument("stored_bits must be 1..16");
+  v.stored_bits = mt.stored_bits;
+  v.slope = mt.slope;
+  v.intercept = mt.intercept;
+  v.spacing_x = (float)mt.spacing[0];
+  v.spacing_y = (float)mt.spacing[1];
+  v.spacing_z = mt.spacing[2];
+  v.spacing_z_source = mt.spacing_z_source;
+}
+
 }  // namespace
 
 template <class Fn>
 py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::forcecast> vol, const PipelineParams& p,
-                     int connectivity, int dilation, const std::vector<std::tuple<int, int, int>>& seeds, Fn&& fn) {
+                     int connectivity, int dilation, const std::vector<std::tuple<int, int, int>>& seeds, Fn&& fn,
+                     const VolumeMeta* meta = nullptr) {
   if (vol.ndim() != 3) throw std::invalid_argument("volume must be (depth, height, width)");
   VolumeInput v;
   v.d = (int)vol.shape(0);
@@ -264,6 +349,11 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
   vp.connectivity = connectivity;
   vp.dilation_size = dilation;
   vp.seeds = seeds_from(seeds);
+  if (meta) {
+    apply_meta(*meta, v);
+    vp.measure = meta->measure;
+    vp.measure_connectivity = meta->measure_connectivity;
+  }
   VolumeResult r;
   {
     py::gil_scoped_release nogil;
@@ -275,6 +365,11 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
   d["dilated"] = to_np<uint8_t>(r.dilated, {v.d, v.h, v.w});
   d["sweeps"] = r.sweeps;
   d["kernels_s"] = r.kernels_s;
+  if (vp.measure) {
+    d["measure"] = volume_measure_dict(r.measure);
+    d["measure_json"] = golden::measure_volume_json(r.measure, v, vp.pipe.apply_rescale, vp.measure_connectivity);
+    d["measure_s"] = r.measure_s;
+  }
   return d;
 }
 
@@ -383,8 +478,14 @@ PYBIND11_MODULE(_nm03, m) {
       [](py::array_t<uint16_t, py::array::c_style | py::array::forcecast> px, const std::string& type, int bits_stored,
          bool write_rescale, float slope, float intercept, float sx, float sy, int instance, const std::string& patient_id,
          const std::string& syntax, bool preamble, const std::string& photometric, int jpeg_predictor,
-         int jpeg_restart_rows, int jpeg_fragments, int jpeg_quality) {
+         int jpeg_restart_rows, int jpeg_fragments, int jpeg_quality, double slice_thickness,
+         double spacing_between_slices, const std::vector<double>& position, bool write_position) {
         dicom::WriteSpec w;
+        w.slice_thickness = slice_thickness;
+        w.spacing_between_slices = spacing_between_slices;
+        if (position.size() != 3) throw std::invalid_argument("position must be (x, y, z)");
+        for (int k = 0; k < 3; ++k) w.position[k] = position[(size_t)k];
+        w.write_position = write_position;
         w.jpeg_quality = jpeg_quality;
         w.jpeg_predictor = jpeg_predictor;
         w.jpeg_restart_rows = jpeg_restart_rows;
@@ -423,7 +524,20 @@ PYBIND11_MODULE(_nm03, m) {
       py::arg("slope") = 1.f, py::arg("intercept") = 0.f, py::arg("spacing_x") = 1.f, py::arg("spacing_y") = 1.f,
       py::arg("instance") = 1, py::arg("patient_id") = "PGBM-000", py::arg("syntax") = "explicit",
       py::arg("preamble") = true, py::arg("photometric") = "MONOCHROME2", py::arg("jpeg_predictor") = 1,
-      py::arg("jpeg_restart_rows") = 0, py::arg("jpeg_fragments") = 1, py::arg("jpeg_quality") = 90);
+      py::arg("jpeg_restart_rows") = 0, py::arg("jpeg_fragments") = 1, py::arg("jpeg_quality") = 90,
+      py::arg("slice_thickness") = 1.0, py::arg("spacing_between_slices") = 0.0,
+      py::arg("position") = std::vector<double>{0.0, 0.0, 0.0}, py::arg("write_position") = true);
+  // Geometry of a series from the headers of its first two files: PixelSpacing and the plane spacing
+  // with its source (position | spacing_between_slices | slice_thickness | default), as load_volume sets them.
+  m.def("series_geometry", [](const std::vector<std::string>& files) {
+    const SeriesGeometry g = series_geometry(files);
+    py::dict d;
+    d["spacing_x"] = g.spacing_x;
+    d["spacing_y"] = g.spacing_y;
+    d["spacing_z"] = g.spacing_z;
+    d["spacing_z_source"] = g.spacing_z_source;
+    return d;
+  }, py::arg("files"));
   m.def("jpeg_dct_decode", [](py::bytes b) {
     const std::string s = b;
     std::vector<uint16_t> px;
@@ -782,6 +896,73 @@ PYBIND11_MODULE(_nm03, m) {
       py::arg("record"), py::arg("w"), py::arg("h"), py::arg("spacing_x") = 1.f, py::arg("spacing_y") = 1.f,
       py::arg("slope") = 1.f, py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 8);
 
+  // ---- volume measurements (nm03/measure.h VolumeMeasure) ----------------------------------------------
+  auto volume_arrays = [](const py::array_t<uint8_t, py::array::c_style | py::array::forcecast>& dil,
+                          const py::array_t<uint8_t, py::array::c_style | py::array::forcecast>& reg,
+                          const py::array_t<uint16_t, py::array::c_style | py::array::forcecast>& raw, const std::string& type,
+                          int stored_bits) {
+    if (dil.ndim() != 3 || reg.ndim() != 3 || raw.ndim() != 3)
+      throw std::invalid_argument("dilated, region and raw must be [D, H, W] of one shape");
+    for (int k = 0; k < 3; ++k)
+      if (reg.shape(k) != dil.shape(k) || raw.shape(k) != dil.shape(k))
+        throw std::invalid_argument("dilated, region and raw must be [D, H, W] of one shape");
+    VolumeInput v;
+    v.d = (int)dil.shape(0);
+    v.h = (int)dil.shape(1);
+    v.w = (int)dil.shape(2);
+    VolumeMeta mt;
+    mt.type = type;
+    mt.stored_bits = stored_bits;
+    apply_meta(mt, v);
+    v.raw = from_np<uint16_t>(raw);
+    return v;
+  };
+  m.def(
+      "golden_measure_volume",
+      [volume_arrays](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+                      py::array_t<uint8_t, py::array::c_style | py::array::forcecast> reg,
+                      py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, const std::string& type,
+                      int stored_bits, int connectivity) {
+        const VolumeInput v = volume_arrays(dil, reg, raw, type, stored_bits);
+        const std::vector<uint8_t> dv = from_np<uint8_t>(dil), rv = from_np<uint8_t>(reg);
+        VolumeMeasure r;
+        {
+          py::gil_scoped_release nogil;
+          r = golden::measure_volume(dv, rv, v, connectivity);
+        }
+        return volume_measure_dict(r);
+      },
+      py::arg("dilated"), py::arg("region"), py::arg("raw"), py::arg("type") = "u16", py::arg("stored_bits") = 16,
+      py::arg("connectivity") = 26);
+  // The same record from the K8 kernels' word arithmetic and run union-find, run on the host one word
+  // after the other (measure::volume_words): what the kernels compute, without a GPU.
+  m.def(
+      "measure_volume_words",
+      [volume_arrays](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+                      py::array_t<uint8_t, py::array::c_style | py::array::forcecast> reg,
+                      py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, const std::string& type,
+                      int stored_bits, int connectivity) {
+        const VolumeInput v = volume_arrays(dil, reg, raw, type, stored_bits);
+        const std::vector<uint64_t> dw = pack_volume(dil), rw = pack_volume(reg);
+        return volume_measure_dict(measure::volume_words(dw.data(), rw.data(), v.raw.data(), (size_t)v.w * v.h, v.w, v.h, v.d,
+                                                         (v.w + 63) / 64, (uint8_t)v.type, (uint8_t)v.stored_bits, connectivity));
+      },
+      py::arg("dilated"), py::arg("region"), py::arg("raw"), py::arg("type") = "u16", py::arg("stored_bits") = 16,
+      py::arg("connectivity") = 26);
+  // Words of K8's labelling scratch, (w + 1)·h·d + 1; 0 for a volume too large to measure (≥ 2^32).
+  m.def("volume_measure_scratch_words", [](int w, int h, int d) { return volume_measure_scratch_words(w, h, d); });
+  m.def(
+      "volume_measure_to_json",
+      [](const py::dict& rec, int w, int h, int d, double sx, double sy, double sz, const std::string& source, float slope,
+         float intercept, bool apply_rescale, int connectivity) {
+        // Pixel spacings pass through float, as VolumeInput holds them.
+        return measure::volume_to_json(volume_measure_from(rec), w, h, d, (double)(float)sx, (double)(float)sy, sz, source,
+                                       slope, intercept, apply_rescale, connectivity);
+      },
+      py::arg("record"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_x") = 1.0, py::arg("spacing_y") = 1.0,
+      py::arg("spacing_z") = 1.0, py::arg("spacing_z_source") = "default", py::arg("slope") = 1.f,
+      py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 26);
+
   // ---- JPEG --------------------------------------------------------------------------------------
   m.def("jpeg_encode_gray420", [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> g, int quality) {
     const int h = (int)g.shape(0), w = (int)g.shape(1);
@@ -1002,12 +1183,26 @@ PYBIND11_MODULE(_nm03, m) {
           "run",
           [](VolumeRunner& self, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> vol,
              const PipelineParams& p, int connectivity, int dilation,
-             const std::vector<std::tuple<int, int, int>>& seeds) {
+             const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_connectivity,
+             const std::vector<double>& spacing, const std::string& spacing_z_source, const std::string& type,
+             int stored_bits, float slope, float intercept) {
+            VolumeMeta mt;
+            mt.type = type;
+            mt.stored_bits = stored_bits;
+            mt.slope = slope;
+            mt.intercept = intercept;
+            mt.spacing = spacing;
+            mt.spacing_z_source = spacing_z_source;
+            mt.measure = measure;
+            mt.measure_connectivity = measure_connectivity;
             return volume_call(vol, p, connectivity, dilation, seeds,
-                               [&self](const VolumeInput& v, const VolumeParams& vp) { return self.run(v, vp, true); });
+                               [&self](const VolumeInput& v, const VolumeParams& vp) { return self.run(v, vp, true); }, &mt);
           },
           py::arg("volume"), py::arg("params") = PipelineParams(), py::arg("connectivity") = 6,
-          py::arg("dilation") = 7, py::arg("seeds") = std::vector<std::tuple<int, int, int>>{})
+          py::arg("dilation") = 7, py::arg("seeds") = std::vector<std::tuple<int, int, int>>{},
+          py::arg("measure") = false, py::arg("measure_connectivity") = 26,
+          py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0}, py::arg("spacing_z_source") = "default",
+          py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f, py::arg("intercept") = 0.f)
       .def(
           "run_slab",
           // One rank's z-slab (planes [z0, z0 + slab depth) of a `depth`-deep volume) through the
@@ -1015,19 +1210,21 @@ PYBIND11_MODULE(_nm03, m) {
           // coordinates. Returns the slab's masks plus rounds / exchanged bytes.
           [](VolumeRunner& self, Comm& comm, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> slab,
              int z0, int depth, const PipelineParams& p, int connectivity, int dilation,
-             const std::vector<std::tuple<int, int, int>>& seeds) {
+             const std::vector<std::tuple<int, int, int>>& seeds, bool measure) {
             SlabStats st;
+            VolumeMeta mt;
+            mt.measure = measure;  // refused by run_slab (std::invalid_argument) before anything is launched
             py::dict d = volume_call(slab, p, connectivity, dilation, seeds,
                                      [&](const VolumeInput& v, const VolumeParams& vp) {
                                        return self.run_slab(comm, v, z0, depth, vp, true, &st);
-                                     });
+                                     }, &mt);
             d["rounds"] = st.rounds;
             d["exchanged_bytes"] = st.exchanged_bytes;
             return d;
           },
           py::arg("comm"), py::arg("slab"), py::arg("z0"), py::arg("depth"), py::arg("params") = PipelineParams(),
           py::arg("connectivity") = 6, py::arg("dilation") = 7,
-          py::arg("seeds") = std::vector<std::tuple<int, int, int>>{});
+          py::arg("seeds") = std::vector<std::tuple<int, int, int>>{}, py::arg("measure") = false);
 
   // One-process rehearsal of the z-slab decomposition: `nranks` threads, each with its own
   // VolumeRunner (stream) on `device`, talking over loopback comms — the device-resident exchange
@@ -1544,6 +1741,41 @@ PYBIND11_MODULE(_nm03, m) {
     return out;
   }, py::arg("planes"), py::arg("raw"), py::arg("hs"), py::arg("ws"), py::arg("type") = "u16", py::arg("stored_bits") = 16,
      py::arg("connectivity") = 8, py::arg("stream") = 0);
+
+  // K8 on bit volumes [d][h][ceil(w/64)] (int64 words): `dilated` and `region`, the 16-bit samples
+  // `raw` [d][h][w]. Returns the record dict. Synchronous on `stream`; the scratch is kept across calls.
+  m.def("k_measure_volume", [](uintptr_t dilated, uintptr_t region, uintptr_t raw, int w, int h, int d,
+                               const std::string& type, int stored_bits, int connectivity, uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    if (connectivity != 6 && connectivity != 26) throw std::invalid_argument("connectivity must be 6 or 26");
+    if (stored_bits < 1 || stored_bits > 16) throw std::invalid_argument("stored_bits must be 1..16");
+    if (w <= 0 || h <= 0 || d <= 0) throw std::invalid_argument("empty volume");
+    const size_t slots = gpu::volume_measure_scratch_words(w, h, d);
+    if (slots == 0) throw std::invalid_argument("volume too large to measure: (w + 1) * h * d + 1 must stay below 2^32");
+    const PixelType pt = parse_type(type);
+    {
+      // K8's code object, loaded on the current device before this op's first launch there.
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_volume_measure();
+        preloaded.push_back(dev);
+      }
+    }
+    const size_t o_acc = 0, o_out = 256, o_par = 512, total = o_par + slots * sizeof(uint32_t);
+    uint8_t* dev = (uint8_t*)scratch().get(total);
+    gpu::launch_volume_measure((const uint64_t*)dilated, (const uint64_t*)region, (const uint16_t*)raw, (size_t)w * h, w, h,
+                               d, (uint8_t)(pt == kU8 ? kU16 : pt), (uint8_t)stored_bits, connectivity,
+                               (uint32_t*)(dev + o_par), (uint64_t*)(dev + o_acc), (VolumeMeasure*)(dev + o_out), st);
+    VolumeMeasure res;
+    gpu::check_hip(hipMemcpyAsync(&res, dev + o_out, sizeof(VolumeMeasure), hipMemcpyDeviceToHost, st), "D2H record");
+    gpu::check_hip(hipStreamSynchronize(st), "k_measure_volume");
+    return volume_measure_dict(res);
+  }, py::arg("dilated"), py::arg("region"), py::arg("raw"), py::arg("w"), py::arg("h"), py::arg("d"),
+     py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("connectivity") = 26, py::arg("stream") = 0);
 
   // ---- comm self-tests (CPU) ------------------------------------------------------------------------
   m.def("loopback_selftest", [](int n) {

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <fstream>
@@ -30,13 +31,57 @@ using namespace nm03::gpu;
 
 // Every frame of every file, stacked in file order: a series of single-frame slices, or a
 // multi-frame file (one file = one volume), or a mix of both.
+double series_spacing_z(const dicom::Header& first, const dicom::Header* second, std::string* source) {
+  if (second && first.has_position && second->has_position) {
+    double s2 = 0;
+    for (int k = 0; k < 3; ++k) s2 += (second->position[k] - first.position[k]) * (second->position[k] - first.position[k]);
+    if (s2 > 0) {
+      *source = "position";
+      return std::sqrt(s2);
+    }
+  }
+  if (first.spacing_between_slices > 0) {
+    *source = "spacing_between_slices";
+    return first.spacing_between_slices;
+  }
+  if (first.slice_thickness > 0) {
+    *source = "slice_thickness";
+    return first.slice_thickness;
+  }
+  *source = "default";
+  return 1.0;
+}
+
+SeriesGeometry series_geometry(const std::vector<std::string>& files) {
+  if (files.empty()) throw SliceError("series_geometry: no files");
+  SeriesGeometry g;
+  std::vector<uint8_t> buf;
+  size_t n = dicom::read_file_into(files[0], buf);
+  const dicom::Header h0 = dicom::parse(buf.data(), n);
+  g.spacing_x = h0.spacing_x;
+  g.spacing_y = h0.spacing_y;
+  dicom::Header h1;
+  const bool two = h0.frames == 1 && files.size() > 1;  // the first two planes come from different files
+  if (two) {
+    n = dicom::read_file_into(files[1], buf);
+    h1 = dicom::parse(buf.data(), n);
+  }
+  g.spacing_z = series_spacing_z(h0, two ? &h1 : nullptr, &g.spacing_z_source);
+  return g;
+}
+
 VolumeInput load_volume(const std::vector<std::string>& files) {
   VolumeInput v;
   std::vector<uint8_t> buf;
+  dicom::Header first;
   for (size_t z = 0; z < files.size(); ++z) {
     const size_t n = dicom::read_file_into(files[z], buf);
     dicom::Header h = dicom::parse(buf.data(), n);
+    if (z == 0 || (z == 1 && first.frames == 1))
+      v.spacing_z = series_spacing_z(z == 0 ? h : first, z == 0 ? nullptr : &h, &v.spacing_z_source);
     if (z == 0) {
+      first = h;
+      first.decoded.reset();
       v.w = h.cols;
       v.h = h.rows;
       v.type = h.type == kU8 ? kU16 : h.type;
@@ -111,6 +156,10 @@ struct VolumeDevice {
   // and the halo-extended dilation buffers, allocated on first use and kept.
   std::unique_ptr<DevBuf> slab_nb, slab_added, ext, ext_dil, ext_tmp, ext_scr;
   int ext_planes = 0;
+  // K8 (VolumeParams::measure): the labelling scratch, the accumulators and the pinned record,
+  // allocated by the first measuring run and kept.
+  std::unique_ptr<DevBuf> vm_scratch, vm_acc;
+  VolumeMeasure* h_measure = nullptr;
   VolumeDevice(const VolumeInput& v)
       : w(v.w), h(v.h), d(v.d), wpr((v.w + 63) / 64), words((size_t)v.h * ((v.w + 63) / 64)),
         ps(((size_t)v.w * v.h + 7) / 8 * 8),
@@ -131,6 +180,7 @@ struct VolumeDevice {
     return sizeof(SliceDesc) * d + sizeof(TileDesc) * (n_medt + n_shpt) + sizeof(SliceStats) * d;
   }
   ~VolumeDevice() {
+    if (h_measure) (void)hipHostFree(h_measure);
     if (h_tables) (void)hipHostFree(h_tables);
     if (h_flag) (void)hipHostFree(h_flag);
     if (stream) (void)hipStreamDestroy(stream);
@@ -281,12 +331,14 @@ struct VolumeRunner::Impl {
   int device;
   std::unique_ptr<VolumeDevice> V;
   std::unique_ptr<ExportBufs> X;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+  bool measure_loaded = false;  // K8's code object (first measuring run)
   explicit Impl(int dev) : device(dev) {
     check_hip(hipSetDevice(device), "hipSetDevice");
     preload_kernels();  // every code object, before the first launch (kernels.h)
     check_hip(hipEventCreate(&e0), "event");
     check_hip(hipEventCreate(&e1), "event");
+    check_hip(hipEventCreate(&e2), "event");
   }
   ~Impl() {
     (void)hipSetDevice(device);
@@ -294,6 +346,7 @@ struct VolumeRunner::Impl {
     V.reset();
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
+    if (e2) (void)hipEventDestroy(e2);
   }
 };
 
@@ -311,6 +364,26 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
     I.V = std::make_unique<VolumeDevice>(v);
   }
   VolumeDevice& V = *I.V;
+  if (p.measure) {
+    if (p.measure_connectivity != 6 && p.measure_connectivity != 26)
+      throw std::invalid_argument("3D measurement connectivity must be 6 or 26 (got " +
+                                  std::to_string(p.measure_connectivity) + ")");
+    const size_t slots = volume_measure_scratch_words(v.w, v.h, v.d);
+    if (slots == 0 || V.ps * (size_t)v.d > 0xFFFFFFFFull)
+      throw std::invalid_argument("volume too large to measure: (w + 1) * h * d + 1 must stay below 2^32 (got " +
+                                  std::to_string(v.w) + " x " + std::to_string(v.h) + " x " + std::to_string(v.d) + ")");
+    // First use: K8's code object, before this run's first launch, while the stream is idle (the
+    // previous run ended with a synchronisation); then its buffers, kept like the others.
+    if (!I.measure_loaded) {
+      preload_volume_measure();
+      I.measure_loaded = true;
+    }
+    if (!V.vm_scratch) {
+      V.vm_scratch = std::make_unique<DevBuf>(slots * sizeof(uint32_t));
+      V.vm_acc = std::make_unique<DevBuf>(kVolumeMeasureAccWords * sizeof(uint64_t));
+      check_hip(hipHostMalloc((void**)&V.h_measure, sizeof(VolumeMeasure), hipHostMallocDefault), "hipHostMalloc measure");
+    }
+  }
   const PipeConsts pc = make_consts(p.pipe, 2);
   check_hip(hipEventRecord(I.e0, V.stream), "event");
   VolumeResult r;
@@ -320,6 +393,17 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
   volume_preprocess(V, v, p.pipe, pc);
   volume_segment(V, v, p);
   check_hip(hipEventRecord(I.e1, V.stream), "event");
+  if (p.measure) {  // timed outside the e0–e1 pair: kernels_s stays what it is
+    launch_volume_measure(V.dil.as<uint64_t>(), V.region.as<uint64_t>(), V.raw.as<uint16_t>(), V.ps, v.w, v.h, v.d,
+                          (uint8_t)v.type, (uint8_t)v.stored_bits, p.measure_connectivity, V.vm_scratch->as<uint32_t>(),
+                          V.vm_acc->as<uint64_t>(), V.h_measure, V.stream);
+    check_hip(hipEventRecord(I.e2, V.stream), "event");
+    check_hip(hipEventSynchronize(I.e2), "sync");
+    r.measure = *V.h_measure;
+    float mms = 0;
+    (void)hipEventElapsedTime(&mms, I.e1, I.e2);
+    r.measure_s = mms * 1e-3;
+  }
   check_hip(hipEventSynchronize(I.e1), "sync");
   r.sweeps = srg_volume_result(V.h_flag);
   float ms = 0;
@@ -464,6 +548,9 @@ static SlabStats slab_grow_dilate_gpu(Comm& comm, VolumeDevice& V, int nseeds, i
 VolumeResult VolumeRunner::run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p,
                                     bool want_masks, SlabStats* stats) {
   if (slab.d < 1 || slab.w < 1 || slab.h < 1) throw SliceError("empty slab");
+  if (p.measure)
+    throw std::invalid_argument("run_slab: measuring a volume split into slabs is not supported "
+                                "(components that cross slabs need a collective)");
   check_volume_params(p.connectivity, p.dilation_size);
   Impl& I = *impl_;
   check_hip(hipSetDevice(I.device), "hipSetDevice");
@@ -653,6 +740,8 @@ struct VolOutcome {
   int64_t slices = 0, fallbacks = 0;
   int32_t rounds = 0;         // --split-volume: grow/exchange rounds
   int64_t exchanged = 0;      // --split-volume: boundary + halo bytes sent
+  std::string measure_json;   // --measure-volume: the sidecar text (measure::volume_to_json)
+  double measure_s = 0;       // --measure-volume: GPU time of K8
 };
 
 std::vector<uint8_t> encode(const std::vector<VolPatient>& pl) {
@@ -746,8 +835,9 @@ std::vector<std::vector<uint8_t>> golden_export(const VolumeInput& v, const std:
   return files;
 }
 
+// `measured` (optional): the record of the dilated volume by the golden model (--measure-volume).
 std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, const VolumeParams& vp,
-                                                      const RenderParams& rp) {
+                                                      const RenderParams& rp, VolumeMeasure* measured = nullptr) {
   const GoldenPlanes gp = golden_preprocess(v, vp);
   std::vector<Seed> seeds = vp.seeds;
   if (seeds.empty()) {
@@ -756,6 +846,7 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
   }
   const auto region = golden::region_grow3d(gp.band, v.w, v.h, v.d, seeds, vp.connectivity);
   const auto dil = golden::dilate3d(region, v.w, v.h, v.d, vp.dilation_size, vp.pipe.se_shape == kSeDisc);
+  if (measured) *measured = golden::measure_volume(dil, region, v, vp.measure_connectivity);
   return golden_export(v, gp.vals, dil, rp);
 }
 
@@ -780,6 +871,8 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
   vp.connectivity = cfg.engine.pipe.srg_connectivity == 26 ? 26 : 6;
   // BASELINE config 5: 7×7×7 cube dilation unless --dilation-size was given.
   vp.dilation_size = cfg.dilation_set ? cfg.engine.pipe.dilation_size : 7;
+  vp.measure = cfg.measure_volume;
+  vp.measure_connectivity = cfg.measure_volume_connectivity;
   const RenderParams& rp = cfg.engine.render;
   const double t_start = wall_now();
   // ---- plan on rank 0 -----------------------------------------------------------------------
@@ -911,18 +1004,28 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       VolumeInput v = load_volume(pp.files);
       o.slices = v.d;
       std::vector<std::vector<uint8_t>> files;
+      VolumeMeasure measured = {};
       if (cfg.cpu) {
-        files = golden_volume_jpegs(v, vp, rp);
+        files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr);
       } else {
         VolumeResult r = runner->run(v, vp, false);
         o.sweeps = r.sweeps;
         o.gpu_s = r.kernels_s;
+        o.measure_s = r.measure_s;
+        measured = r.measure;
         VolumeExportStats xs;
         files = runner->export_jpegs(v, vp, rp, &xs);
         o.export_s = xs.export_s;
         o.fallbacks = xs.jpeg_fallbacks;
       }
       write_planes(pp, 0, v.d, files);
+      if (vp.measure) {  // the sidecar next to the planes; its text travels to rank 0 for the table
+        o.measure_json = golden::measure_volume_json(measured, v, vp.pipe.apply_rescale, vp.measure_connectivity);
+        const std::string path = pp.out_dir + "/" + measure::volume_sidecar_name();
+        std::ofstream f(path, std::ios::binary | std::ios::trunc);
+        f.write(o.measure_json.data(), (std::streamsize)o.measure_json.size());
+        if (!f) throw std::runtime_error("Cannot write " + path);
+      }
       o.ok = 1;
     } catch (const std::exception& e) {
       o.message = e.what();
@@ -945,6 +1048,8 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
     w.u64((uint64_t)o.fallbacks);
     w.i32(o.rounds);
     w.u64((uint64_t)o.exchanged);
+    w.str(o.measure_json);
+    w.f64(o.measure_s);
   }
   auto all = comm.allgather_bytes(w.b);
   double tot = wall_now() - t_start;
@@ -968,6 +1073,8 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       o.fallbacks = (int64_t)r.u64();
       o.rounds = r.i32();
       o.exchanged = (int64_t)r.u64();
+      o.measure_json = r.str();
+      o.measure_s = r.f64();
       outs.push_back(std::move(o));
     }
   }
@@ -1026,10 +1133,22 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
     pj << (i ? ", " : "") << "{\"id\": \"" << pp.id << "\", \"ok\": " << (o.ok ? "true" : "false")
        << ", \"slices\": " << o.slices << ", \"sweeps\": " << o.sweeps << ", \"gpu_s\": " << o.gpu_s
        << ", \"export_s\": " << o.export_s << ", \"wall_s\": " << o.wall_s << ", \"rounds\": " << o.rounds
-       << ", \"exchanged_bytes\": " << o.exchanged << "}";
+       << ", \"exchanged_bytes\": " << o.exchanged;
+    if (cfg.measure_volume) pj << ", \"measure_s\": " << o.measure_s;
+    pj << "}";
   }
   std::cout << "\n=== All Processing Completed ===\n" << std::endl;
   std::cout << "Successfully processed " << successful << "/" << plan.size() << " patients." << std::endl;
+  VolumeTotals volume_totals;
+  if (cfg.measure_volume) {  // the cohort table, in plan order (an error is reported, not fatal)
+    std::vector<VolumePatientRow> rows;
+    for (size_t i = 0; i < plan.size(); ++i) rows.push_back({plan[i].id, outs[i].ok != 0, outs[i].measure_json});
+    try {
+      volume_totals = write_volumes_csv(cfg.out_dir, rows);
+    } catch (const std::exception& e) {
+      std::cerr << "Error writing volumes.csv: " << e.what() << std::endl;
+    }
+  }
   if (!cfg.json.empty()) {
     std::ofstream f(cfg.json, std::ios::trunc);
     f << "{\"mode\": \"3d\", \"backend\": \"" << (cfg.cpu ? "cpu" : "gpu") << "\", \"gpus\": " << size
@@ -1038,7 +1157,9 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       << ", \"wall_s\": " << tot << ", \"slices\": " << slices
       << ", \"jpeg_fallbacks\": " << fallbacks << ", \"per_rank_wall_s\": [";
     for (int r = 0; r < size; ++r) f << (r ? ", " : "") << walls[r];
-    f << "], \"patients\": [" << pj.str() << "]}\n";
+    f << "], \"patients\": [" << pj.str() << "]";
+    if (cfg.measure_volume) f << ", \"measure_volume\": " << volume_totals_json(volume_totals);
+    f << "}\n";
   }
   return 0;
 }
