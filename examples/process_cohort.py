@@ -2,13 +2,14 @@
 
     python examples/process_cohort.py --data-root data/ --out out-py/ [--synth] [--host-only]
                                       [--se-shape disc] [--render-filter nearest] [--jpeg-sampling gray]
-                                      [--overlay] [--measure]
+                                      [--overlay] [--measure] [--measure-diameters]
 
 --synth writes the synthetic 20-patient cohort first; --host-only runs the host path alone (loads and
 JPEG writes with fixed segments, no GPU), which is what the CPU test of this example exercises.
 --overlay also writes <stem>_overlay.jpg per slice, the original with the dilated mask over it in colour
 (GPU only; not with --host-only or --jpeg-sampling gray).
 --measure also writes <stem>_measure.json per slice: area, components, holes and intensity of the dilated mask (GPU only).
+--measure-diameters adds the lesion's bidimensional diameters (major, perpendicular, product) to that sidecar.
 """
 import argparse
 import os
@@ -33,6 +34,8 @@ def main(argv=None):
     ap.add_argument("--jpeg-sampling", choices=tuple(SAMPLING), default="420")
     ap.add_argument("--overlay", action="store_true", help="also write the colour overlay per slice (GPU only)")
     ap.add_argument("--measure", action="store_true", help="also write the measurement sidecar per slice (GPU only)")
+    ap.add_argument("--measure-diameters", action="store_true",
+                    help="--measure plus the lesion's bidimensional diameters in the sidecar (GPU only)")
     a = ap.parse_args(argv)
     if a.synth:
         synth_cohort(a.data_root, patients=4, min_slices=5, max_slices=7)
@@ -40,7 +43,7 @@ def main(argv=None):
     items = cohort.work_items(a.out)
     cfg = nm.PipelineConfig(se_shape=int(a.se_shape == "disc"), render_filter=int(a.render_filter == "nearest"),
                             jpeg_sampling=SAMPLING[a.jpeg_sampling], host_only=a.host_only, overlay=a.overlay,
-                            measure=a.measure)
+                            measure=a.measure, measure_diameters=a.measure_diameters)
     pipe = nm.SlicePipeline(cfg)
     t0 = time.perf_counter()
     statuses, _ = pipe.process(items)

@@ -143,8 +143,16 @@ struct MeasureTotals {
   int64_t slices = 0;  // slices with a sidecar
   uint64_t area_px = 0;
   double area_mm2 = 0;
+  // --measure-diameters: the job's largest bidimensional_mm2 (0 when no slice has a lesion).
+  bool diameters = false;
+  double bidimensional_mm2_max = 0;
 };
-MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients);
+// `diameters` (--measure-diameters): the table also has the diameter keys' columns after `mean`
+// (lesion_first, major and perp flattened), and a patient's TOTAL row carries the patient's largest
+// bidimensional_mm2 with the major_mm and perp_mm of that slice (the first such slice; empty when no
+// slice has a lesion). A sidecar written earlier without the flag (--resume) leaves those columns empty.
+MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients,
+                                     bool diameters = false);
 std::string measure_totals_json(const MeasureTotals& t);  // the --json record's "measure" object
 const char* slice_status_name(int code);
 

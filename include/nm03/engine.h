@@ -125,6 +125,8 @@ struct SingleResult {
   // PipelineParams::measure only: the K7 record of the dilated mask and its sidecar text (measure::to_json).
   SliceMeasure measure{};
   std::string measure_json;
+  // PipelineParams::measure_diameters only: the K9 record of the lesion (measure_json then carries its keys too).
+  SliceDiameters diameters{};
 };
 
 struct RunHandle;  // a submitted run (Engine::submit)

@@ -100,6 +100,18 @@ SliceMeasure measure(const std::vector<uint8_t>& dilated, const std::vector<uint
 // The sidecar text of a record for slice `s` under `p` (measure::to_json with the slice's fields).
 std::string measure_json(const SliceMeasure& m, const SliceInput& s, const PipelineParams& p);
 
+// Bidimensional diameters of the lesion (PipelineParams::measure_diameters, nm03/measure.h
+// SliceDiameters) of a w × h mask (0/1 per pixel). Shares nothing with the K9 kernel's method: flood
+// fill in raster order (the first component of the largest area is the lesion), the top and bottom
+// lesion pixel of every COLUMN as candidates, plain double loops over them in (y, x) order.
+SliceDiameters measure_diameters(const std::vector<uint8_t>& dilated, int connectivity, int w, int h);
+// The sidecar text of a record pair (measure::to_json with the diameter keys).
+std::string measure_json(const SliceMeasure& m, const SliceDiameters& d, const SliceInput& s, const PipelineParams& p);
+// The sidecar text the --cpu paths write for slice `s`: measure() and, with p.measure_diameters,
+// measure_diameters() at p.measure_connectivity, through the matching measure_json.
+std::string measure_sidecar(const std::vector<uint8_t>& dilated, const std::vector<uint8_t>& region, const SliceInput& s,
+                            const PipelineParams& p);
+
 // Measurements of a volume (VolumeParams::measure, nm03/measure.h VolumeMeasure): the record on the
 // `dilated` volume plus popcount(`region`) (0/1 per voxel, d planes of h × w), intensities from v.raw.
 // Plain per-voxel code that shares nothing with the K8 kernels' word arithmetic: components by flood

@@ -188,6 +188,18 @@ void launch_measure(const uint64_t* dilated, const uint64_t* region, const uint1
 // so a default run never pays for it — and no slot thread ever loads it lazily.
 void preload_measure();
 
+// K9 (k9_diameters.hip): the SliceDiameters record (nm03/measure.h) of every slice's lesion, one
+// workgroup per slice, launched on the stream of a launch_measure call with the same `dilated`,
+// `descs`, `nslices`, `scratch`, `max_w` and `max_h`: it reads K7's labelling as that launch leaves it
+// (every run start points at its root, the component's area in the slot after the root) and writes
+// nothing but `out` (plain vector stores; device or host-mapped memory). A slice that K7 could not
+// measure reports lesion_px = kDiametersNotMeasured. No host round trip, no allocation.
+void launch_measure_diameters(const uint64_t* dilated, const SliceDesc* descs, int nslices, SliceDiameters* out,
+                              const uint32_t* scratch, int max_w, int max_h, hipStream_t stream);
+// Loads K9's code object on the current device: as preload_measure, only for an engine with
+// PipelineParams::measure_diameters and the Python op.
+void preload_measure_diameters();
+
 // K8 (k8_volume_measure.hip): the VolumeMeasure record (nm03/measure.h) of the `dilated` bit volume
 // (d planes of h rows of ceil(w / 64) words) plus popcount(`region`), the intensities from `raw`
 // (plane z at raw + z · raw_plane_stride). Twelve small launches on `stream` (multi-workgroup phases

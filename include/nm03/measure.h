@@ -29,6 +29,29 @@ struct alignas(64) SliceMeasure {
 };
 static_assert(sizeof(SliceMeasure) == 128, "SliceMeasure layout");
 
+// Bidimensional diameters of the lesion (--measure-diameters): the record the K9 kernel writes for one
+// slice. The lesion is the largest connected component of the dilated mask at the measurement
+// connectivity (a tie in area goes to the component whose first pixel in raster order comes first).
+// Everything is an exact integer in pixel index space, centre to centre:
+//   major: the pair (a, b) of lesion pixels that maximises major_px2 = (xb − xa)² + (yb − ya)²; a does
+//          not follow b in (y, x) order, a tie goes to the lexicographically smallest (ya, xa, yb, xb).
+//   perp:  with (dx, dy) = b − a every lesion pixel is projected on n = (−dy, dx): p = −dy·x + dx·y.
+//          perp_extent = max − min of p (the caliper width in pixels is perp_extent / √major_px2);
+//          c / d are the lexicographically smallest (y, x) lesion pixels at the minimum / maximum.
+// A one-pixel lesion has a = b = c = d and zeros; an empty mask has zero counts and −1 coordinates.
+// lesion_px = 0xFFFFFFFF marks a slice that was not measured (it did not fit the labelling scratch).
+// The derived doubles (mm, mm², degrees) exist only in measure::to_json.
+struct alignas(64) SliceDiameters {
+  uint32_t lesion_px;       // area of the lesion
+  int32_t lesion_first[2];  // x, y of the lesion's first pixel in raster order
+  uint32_t major_px2;       // squared major diameter
+  uint32_t perp_extent;     // extent of the projection on n
+  int32_t major[4];         // xa, ya, xb, yb
+  int32_t perp[4];          // xc, yc, xd, yd
+};
+static_assert(sizeof(SliceDiameters) == 64, "SliceDiameters layout");
+constexpr uint32_t kDiametersNotMeasured = 0xFFFFFFFFu;
+
 // ---------------------------------------------------------------------------------------------
 // Bit quads (Gray 1971). Over every 2×2 window of the zero-padded mask, Q1 / Q3 count the windows
 // with exactly one / three set pixels and QD the two diagonal patterns. The Euler number
@@ -191,6 +214,17 @@ int64_t euler_plane(const uint64_t* plane, int w, int h, int wpr, int connectivi
 // Centroids and mean are null for an empty mask.
 std::string to_json(const SliceMeasure& m, int w, int h, float spacing_x, float spacing_y, float slope, float intercept,
                     bool apply_rescale, int connectivity);
+
+// The sidecar text with --measure-diameters: the text above with the diameter record's keys after
+// `mean` — lesion_px, lesion_first [x, y], major_px2, major [xa, ya, xb, yb], perp_extent,
+// perp [xc, yc, xd, yd], then the derived doubles (%.9g), with u = ((xb − xa)·sx, (yb − ya)·sy) and
+// v = ((xd − xc)·sx, (yd − yc)·sy):
+//   major_mm = |u|, perp_mm = |u × v| / |u| (0 when |u| = 0), bidimensional_mm2 = major_mm · perp_mm,
+//   major_angle_deg = atan2(u.y, u.x) in degrees (null when |u| = 0)
+// All four are null for an empty mask. The pair (a, b) is maximal in PIXEL space: it is the mm-space
+// maximum when the spacing is isotropic.
+std::string to_json(const SliceMeasure& m, const SliceDiameters& d, int w, int h, float spacing_x, float spacing_y,
+                    float slope, float intercept, bool apply_rescale, int connectivity);
 
 // File name of a slice's sidecar next to its JPEGs.
 inline std::string sidecar_name(const std::string& stem) { return stem + "_measure.json"; }

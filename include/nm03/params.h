@@ -48,6 +48,10 @@ struct PipelineParams {
   // EngineConfig and the engine's state, keep their sizes and offsets.)
   bool measure = false;
   uint8_t measure_connectivity = 8;
+  // Bidimensional diameters of the lesion, the largest component of the dilated mask
+  // (--measure-diameters, nm03/measure.h SliceDiameters): further keys in the sidecar. Opt-in; implies
+  // `measure`. (The last byte of the same padding.)
+  bool measure_diameters = false;
   // Multi-frame files (dicom::select_frame): -1 rejects them (default), k ≥ 0 imports frame k.
   int frame = -1;
 };

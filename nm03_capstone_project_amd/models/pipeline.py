@@ -38,6 +38,9 @@ class PipelineConfig:
     frame: int = -1  # multi-frame DICOM: -1 rejects such files, k >= 0 imports frame k (dicom.h select_frame)
     measure: bool = False  # also write <stem>_measure.json per slice; run_array / golden gain "measure", "measure_json"
     measure_connectivity: int = 8  # components of the dilated mask counted 8- (default) or 4-connected; holes at the dual
+    # bidimensional diameters of the lesion (the largest component) in the sidecar; implies `measure`;
+    # run_array / golden gain "diameters"
+    measure_diameters: bool = False
     # render / export
     out_width: int = 512
     out_height: int = 512
@@ -62,7 +65,7 @@ class PipelineConfig:
     _PIPE = ("norm_low", "norm_high", "norm_min", "norm_max", "clip_min", "clip_max", "median_window",
              "sharpen_gain", "sharpen_sigma", "sharpen_mask", "srg_min", "srg_max", "srg_connectivity",
              "dilation_size", "erosion_size", "min_dim", "apply_rescale", "frame", "se_shape", "measure",
-             "measure_connectivity")
+             "measure_connectivity", "measure_diameters")
     _RENDER = ("out_width", "out_height", "label_opacity", "border_opacity", "border_radius", "jpeg_quality",
                "jpeg_sampling")
 
@@ -70,6 +73,7 @@ class PipelineConfig:
         p = native().PipelineParams()
         for k in self._PIPE:
             setattr(p, k, getattr(self, k))
+        p.measure = bool(self.measure or self.measure_diameters)
         return p
 
     def render_params(self):

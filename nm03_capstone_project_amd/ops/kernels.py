@@ -284,6 +284,34 @@ def measure_mask(dilated, region, raw, connectivity=8, pixel_type="u16", stored_
                               int(connectivity), _stream())
 
 
+def measure_diameters(dilated, connectivity=8):
+    """Bidimensional diameters of the lesion of masks (K7's labelling, then K9; nm03/measure.h
+    SliceDiameters) → list of dicts of the record's integers: lesion_px and lesion_first [x, y] (the
+    largest component at `connectivity` 4 | 8; a tie goes to the one whose first pixel in raster order
+    comes first), major_px2 and major [xa, ya, xb, yb] (the pair of lesion pixels at maximum distance),
+    perp_extent and perp [xc, yc, xd, yd] (the extent of the projection on the normal of b − a and the
+    pixels that attain its ends). An empty mask gives zero counts and −1 coordinates.
+
+    `dilated` is a bool CUDA tensor [N, H, W] or [H, W], or a list of [H, W] tensors of ANY sizes: the
+    whole batch is one launch of each kernel, one workgroup per mask."""
+    dl = list(dilated) if isinstance(dilated, (list, tuple)) else list(_as3d(dilated))
+    if not dl:
+        raise ValueError("no mask")
+    hs, ws, dw = [], [], []
+    for d in dl:
+        if d.dim() != 2:
+            raise ValueError("every mask must be [H, W]")
+        if not d.is_cuda:
+            raise ValueError("masks must be CUDA (HIP) tensors")
+        hs.append(int(d.shape[0]))
+        ws.append(int(d.shape[1]))
+        dw.append(pack_bits(d.bool().unsqueeze(0)).reshape(-1))
+    planes = torch.cat(dw).contiguous()
+    # K7 also reads the samples under the mask; their values do not enter the diameters
+    samples = torch.zeros(sum(h * w for h, w in zip(hs, ws)), dtype=torch.int16, device=planes.device)
+    return native().k_measure_diameters(planes.data_ptr(), samples.data_ptr(), hs, ws, int(connectivity), _stream())
+
+
 def measure_volume(dilated, region, raw, connectivity=26, pixel_type="u16", stored_bits=16):
     """Measurements of a volume mask (K8, nm03/measure.h VolumeMeasure) → dict of the record's integers:
     volume_vox, region_vox, bbox [x0, y0, z0, x1, y1, z1], sum_x / _y / _z, faces_x / _y / _z, components,

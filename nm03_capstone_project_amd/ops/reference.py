@@ -255,6 +255,60 @@ def measure(dilated, region, raw, connectivity=8, pixel_type="u16", stored_bits=
     }
 
 
+def measure_diameters(dilated, connectivity=8):
+    """The diameter record (nm03/measure.h SliceDiameters) of one mask [H, W] (torch or NumPy) in NumPy +
+    scipy.ndimage.label: a third method beside the golden model (column extremes) and the K9 kernel (row
+    extremes). The lesion is the label with the largest count (`argmax` of `bincount` takes the first,
+    and labels are numbered in raster order of their first pixel); the candidates are the vertices of
+    its convex hull (Andrew's monotone chain in exact integers, collinear points dropped); the pair and
+    the projection extremes are brute force over them with the record's tie-breaks."""
+    import numpy as np
+    from scipy import ndimage
+
+    m = (dilated.detach().cpu().numpy() if isinstance(dilated, torch.Tensor) else np.asarray(dilated)).astype(bool)
+    structure = ndimage.generate_binary_structure(2, 2 if connectivity == 8 else 1)
+    lab, ncomp = ndimage.label(m, structure=structure)
+    rec = {"lesion_px": 0, "lesion_first": [-1, -1], "major_px2": 0, "major": [-1] * 4, "perp_extent": 0, "perp": [-1] * 4}
+    if ncomp == 0:
+        return rec
+    sizes = np.bincount(lab.ravel())[1:]
+    k = int(np.argmax(sizes)) + 1
+    ys, xs = np.nonzero(lab == k)  # raster order
+    rec["lesion_px"] = int(sizes[k - 1])
+    rec["lesion_first"] = [int(xs[0]), int(ys[0])]
+    pts = sorted(set(zip(xs.tolist(), ys.tolist())))  # (x, y), sorted by x then y
+
+    def cross(o, a, b):
+        return (a[0] - o[0]) * (b[1] - o[1]) - (a[1] - o[1]) * (b[0] - o[0])
+
+    if len(pts) > 2:
+        lower, upper = [], []
+        for p in pts:
+            while len(lower) >= 2 and cross(lower[-2], lower[-1], p) <= 0:
+                lower.pop()
+            lower.append(p)
+        for p in reversed(pts):
+            while len(upper) >= 2 and cross(upper[-2], upper[-1], p) <= 0:
+                upper.pop()
+            upper.append(p)
+        pts = lower[:-1] + upper[:-1]
+    hull = sorted((y, x) for x, y in pts)  # (y, x) order
+    best = None
+    for i, (ya, xa) in enumerate(hull):
+        for yb, xb in hull[i:]:
+            d2 = (xb - xa) ** 2 + (yb - ya) ** 2
+            if best is None or d2 > best[0]:
+                best = (d2, xa, ya, xb, yb)
+    d2, xa, ya, xb, yb = best
+    dx, dy = xb - xa, yb - ya
+    proj = [(-dy * x + dx * y, y, x) for y, x in hull]
+    pmin, pmax = min(p[0] for p in proj), max(p[0] for p in proj)
+    _, yc, xc = min(p for p in proj if p[0] == pmin)
+    _, yd, xd = min(p for p in proj if p[0] == pmax)
+    rec.update(major_px2=int(d2), major=[xa, ya, xb, yb], perp_extent=int(pmax - pmin), perp=[xc, yc, xd, yd])
+    return rec
+
+
 def measure_volume(dilated, region, raw, connectivity=26, pixel_type="u16", stored_bits=16):
     """The volume record (nm03/measure.h VolumeMeasure) in NumPy + scipy.ndimage.label: a third
     implementation beside the golden model's flood fill and the K8 kernels' union-find. `dilated`,

@@ -100,11 +100,14 @@ class Cohort:
 def read_measurements(out_dir):
     """Rows of <out_dir>/measurements.csv (written by the CLIs with --measure) as dicts keyed by the
     header: one per slice (`status` "ok" or the failure's name, then empty fields) and one per patient
-    with file == "TOTAL" carrying the summed area_px and area_mm2. Integer columns come back as int,
-    the derived ones as float, empty fields as None."""
+    with file == "TOTAL" carrying the summed area_px and area_mm2. With --measure-diameters the rows also
+    have the diameter columns (lesion_px … major_angle_deg, arrays flattened), and a TOTAL row the
+    patient's largest bidimensional_mm2 with the major_mm and perp_mm of that slice. Integer columns
+    come back as int, the derived ones as float, empty fields as None."""
     import csv
     import os
-    floats = {"area_mm2", "centroid_x", "centroid_y", "centroid_x_mm", "centroid_y_mm", "mean"}
+    floats = {"area_mm2", "centroid_x", "centroid_y", "centroid_x_mm", "centroid_y_mm", "mean", "major_mm", "perp_mm",
+              "bidimensional_mm2", "major_angle_deg"}
     text = {"patient", "file", "status"}
     rows = []
     with open(os.path.join(out_dir, "measurements.csv"), newline="") as f:

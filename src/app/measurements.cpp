@@ -33,6 +33,12 @@ const char* const kColumns[] = {"width",      "height",        "connectivity",  
                                 "area_mm2",   "centroid_x",    "centroid_y",    "centroid_x_mm", "centroid_y_mm", "mean"};
 constexpr size_t kNumColumns = sizeof(kColumns) / sizeof(kColumns[0]);
 constexpr size_t kColAreaPx = 3, kColAreaMm2 = 18;
+// --measure-diameters: the columns after those — the diameter keys in their order, arrays flattened.
+const char* const kDiameterColumns[] = {"lesion_px", "lesion_first_x", "lesion_first_y", "major_px2", "major_xa", "major_ya",
+                                        "major_xb",  "major_yb",       "perp_extent",    "perp_xc",   "perp_yc",  "perp_xd",
+                                        "perp_yd",   "major_mm",       "perp_mm",        "bidimensional_mm2", "major_angle_deg"};
+constexpr size_t kNumDiameterColumns = sizeof(kDiameterColumns) / sizeof(kDiameterColumns[0]);
+constexpr size_t kColMajorMm = kNumColumns + 13, kColPerpMm = kNumColumns + 14, kColBidimensional = kNumColumns + 15;
 
 // The values of one sidecar line in column order ("" for null). The text is this program's own
 // (one flat object, one array of four integers): values are what stands between ':' or ',' and the
@@ -113,16 +119,25 @@ std::string volume_totals_json(const VolumeTotals& t) {
   return buf;
 }
 
-MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients) {
+MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients,
+                                     bool diameters) {
   MeasureTotals tot;
+  tot.diameters = diameters;
+  const size_t ncols = kNumColumns + (diameters ? kNumDiameterColumns : 0);
   std::ostringstream o;
   o << "patient,file,status";
   for (const char* c : kColumns) o << "," << c;
+  if (diameters)
+    for (const char* c : kDiameterColumns) o << "," << c;
   o << "\n";
   char buf[64];
   for (const auto& p : patients) {
     uint64_t area_px = 0;
     double area_mm2 = 0;
+    // The patient's slice of the largest bidimensional_mm2 (the first one of that value).
+    bool have_bidim = false;
+    double bidim = 0;
+    std::string bidim_text, major_text, perp_text;
     for (size_t i = 0; i < p.files.size(); ++i) {
       const std::string name = cohort::filename(p.files[i]);
       std::vector<std::string> v;
@@ -131,28 +146,40 @@ MeasureTotals write_measurements_csv(const std::string& out_root, const std::vec
         std::ifstream f(cohort::with_slash(p.out_dir) + measure::sidecar_name(cohort::stem(p.files[i])), std::ios::binary);
         std::stringstream ss;
         if (f) ss << f.rdbuf();
-        have = f && parse_sidecar(ss.str(), v);
+        // With `diameters` a sidecar without the diameter keys (written earlier without the flag) is read too.
+        const std::string text = ss.str();
+        have = f && (parse_sidecar(text, v, ncols) || (diameters && parse_sidecar(text, v, kNumColumns)));
+        if (have) v.resize(ncols);
       }
       o << p.id << "," << name << "," << (p.status[i] == kSliceOk && !have ? "no_sidecar" : slice_status_name(p.status[i]));
-      for (size_t c = 0; c < kNumColumns; ++c) o << "," << (have ? v[c] : std::string());
+      for (size_t c = 0; c < ncols; ++c) o << "," << (have ? v[c] : std::string());
       o << "\n";
       if (!have) continue;
       ++tot.slices;
       area_px += std::strtoull(v[kColAreaPx].c_str(), nullptr, 10);
       area_mm2 += std::strtod(v[kColAreaMm2].c_str(), nullptr);
+      if (diameters && !v[kColBidimensional].empty()) {
+        const double b = std::strtod(v[kColBidimensional].c_str(), nullptr);
+        if (!have_bidim || b > bidim)
+          have_bidim = true, bidim = b, bidim_text = v[kColBidimensional], major_text = v[kColMajorMm], perp_text = v[kColPerpMm];
+      }
     }
     o << p.id << ",TOTAL,";
-    for (size_t c = 0; c < kNumColumns; ++c) {
+    for (size_t c = 0; c < ncols; ++c) {
       o << ",";
       if (c == kColAreaPx) o << area_px;
       if (c == kColAreaMm2) {
         std::snprintf(buf, sizeof buf, "%.9g", area_mm2);
         o << buf;
       }
+      if (diameters && c == kColMajorMm) o << major_text;
+      if (diameters && c == kColPerpMm) o << perp_text;
+      if (diameters && c == kColBidimensional) o << bidim_text;
     }
     o << "\n";
     tot.area_px += area_px;
     tot.area_mm2 += area_mm2;
+    if (have_bidim && bidim > tot.bidimensional_mm2_max) tot.bidimensional_mm2_max = bidim;
   }
   const std::string text = o.str();
   std::ofstream f(cohort::with_slash(out_root) + "measurements.csv", std::ios::binary | std::ios::trunc);
@@ -162,9 +189,14 @@ MeasureTotals write_measurements_csv(const std::string& out_root, const std::vec
 }
 
 std::string measure_totals_json(const MeasureTotals& t) {
-  char buf[160];
-  std::snprintf(buf, sizeof buf, "{\"slices\": %lld, \"area_px_total\": %llu, \"area_mm2_total\": %.9g}", (long long)t.slices,
-                (unsigned long long)t.area_px, t.area_mm2);
+  char buf[240];
+  if (t.diameters)
+    std::snprintf(buf, sizeof buf,
+                  "{\"slices\": %lld, \"area_px_total\": %llu, \"area_mm2_total\": %.9g, \"bidimensional_mm2_max\": %.9g}",
+                  (long long)t.slices, (unsigned long long)t.area_px, t.area_mm2, t.bidimensional_mm2_max);
+  else
+    std::snprintf(buf, sizeof buf, "{\"slices\": %lld, \"area_px_total\": %llu, \"area_mm2_total\": %.9g}", (long long)t.slices,
+                  (unsigned long long)t.area_px, t.area_mm2);
   return buf;
 }
 

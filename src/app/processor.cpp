@@ -61,6 +61,8 @@ void usage(const std::string& which) {
             << "  --overlay-color R,G,B  label colour of the overlay, three values 0..255 (default 0,255,0)\n"
             << "  --measure              also write per-slice measurements of the dilated mask: <stem>_measure.json and\n"
             << "                         <out>/measurements.csv; test_pipeline: measure.json (2D only)\n"
+            << "  --measure-diameters    --measure plus the bidimensional diameters of the lesion (the largest component):\n"
+            << "                         major and perpendicular diameter and their product in the sidecar and the table\n"
             << "  --measure-connectivity 4|8  connectivity of the component count (default 8; holes use the dual)\n"
             << "  --measure-volume       3d: also write the volumetry of each patient's dilated volume (voxels, mm3,\n"
             << "                         surface, components, cavities, tunnels): <patient>/volume_measure.json and\n"
@@ -250,6 +252,7 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
     else if (a == "--split-volume") c.split_volume = true;
     else if (a == "--overlay") c.engine.render.overlay = true;
     else if (a == "--measure") c.engine.pipe.measure = true;
+    else if (a == "--measure-diameters") c.engine.pipe.measure = c.engine.pipe.measure_diameters = true;
     else if (a == "--measure-volume") c.measure_volume = true;
     else if (a == "--measure-volume-connectivity") {
       const std::string v = val();
@@ -298,6 +301,10 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
   }
   if (c.engine.render.overlay && c.engine.render.jpeg_sampling == jpeg::kSamplingGray) {
     std::cerr << "--overlay needs --jpeg-sampling 420 or 444: a one-component gray file cannot carry colour" << std::endl;
+    std::exit(2);
+  }
+  if (c.engine.pipe.measure_diameters && c.mode == "3d") {
+    std::cerr << "--measure-diameters is not available with --mode 3d" << std::endl;
     std::exit(2);
   }
   if (c.engine.pipe.measure && c.mode == "3d") {
@@ -468,7 +475,7 @@ int run_sequential(const AppConfig& cfg) {
       std::cout << "Successfully processed " << successful << "/" << patients.size() << " patients." << std::endl;  // :341
       if (cfg.engine.pipe.measure) {
         try {
-          measure_totals = write_measurements_csv(cfg.out_dir, measured);
+          measure_totals = write_measurements_csv(cfg.out_dir, measured, cfg.engine.pipe.measure_diameters);
         } catch (const std::exception& e) {
           std::cerr << "Error writing measurements.csv: " << e.what() << std::endl;
         }
@@ -618,7 +625,7 @@ std::vector<MeasurePatient> measure_patients(const std::vector<PatientPlan>& pla
 void write_measure_table(const AppConfig& cfg, const std::vector<PatientPlan>& plan, const std::vector<SliceStatus>& gst,
                          MeasureTotals* totals) {
   try {
-    *totals = write_measurements_csv(cfg.out_dir, measure_patients(plan, gst));
+    *totals = write_measurements_csv(cfg.out_dir, measure_patients(plan, gst), cfg.engine.pipe.measure_diameters);
   } catch (const std::exception& e) {
     std::cerr << "Error writing measurements.csv: " << e.what() << std::endl;
   }
@@ -1098,7 +1105,7 @@ SliceStatus cpu_slice(const AppConfig& cfg, const WorkItem& w) {
     put(base + "_processed.jpg", j.processed.data(), j.processed.size());
     if (rp.overlay) put(base + "_overlay.jpg", j.overlay.data(), j.overlay.size());
     if (p.measure) {
-      const std::string js = golden::measure_json(golden::measure(r.dilated, r.region, in, p.measure_connectivity), in, p);
+      const std::string js = golden::measure_sidecar(r.dilated, r.region, in, p);
       put(base + "_measure.json", js.data(), js.size());
     }
   } catch (const std::exception& e) {
@@ -1371,7 +1378,7 @@ int run_test_pipeline(const AppConfig& cfg) {
     if (cfg.cpu) {
       golden::SliceResult st;
       golden::StageImages r = golden::test_pipeline_images(in, p, rp, cfg.dump_mhd.empty() && !p.measure ? nullptr : &st);
-      if (p.measure) measure_json = golden::measure_json(golden::measure(st.dilated, st.region, in, p.measure_connectivity), in, p);
+      if (p.measure) measure_json = golden::measure_sidecar(st.dilated, st.region, in, p);
       canvases = std::move(r.canvases);
       jpegs = std::move(r.jpegs);
       d_sharp = std::move(st.sharpened);

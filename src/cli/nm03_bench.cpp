@@ -63,6 +63,7 @@ int main(int argc, char** argv) {
     }
     else if (a == "--overlay") ec.render.overlay = true;  // cohort: also the colour overlay per slice
     else if (a == "--measure") ec.pipe.measure = true;    // cohort: also K7 and the measurement sidecar per slice
+    else if (a == "--measure-diameters") ec.pipe.measure = ec.pipe.measure_diameters = true;  // cohort: K7, K9 and the extended sidecar
     else if (a == "--measure-connectivity") ec.pipe.measure_connectivity = std::atoi(v().c_str()) == 4 ? 4 : 8;
     else if (a == "--measure-volume") measure_volume = true;
     else if (a == "--measure-volume-connectivity") measure_volume_conn = std::atoi(v().c_str()) == 6 ? 6 : 26;

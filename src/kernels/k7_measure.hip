@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_util.h"
+#include "measure_util.h"
 #include "nm03/gpu_types.h"
 #include "nm03/kernels.h"
 #include "nm03/measure.h"
@@ -38,68 +39,12 @@ constexpr int kMeasureWaves = kMeasureThreads / 64;
 
 namespace {
 
-// Parents and areas are read and written by many threads between barriers: relaxed device-scope
-// accesses, which go to L2 where the atomics act (a plain load could be served a stale line).
-__device__ __forceinline__ uint32_t ld(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st(uint32_t* p, uint32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
-    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
-    v += ((uint64_t)hi << 32) | lo;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int32_t wave_min_i32(int32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int32_t wave_max_i32(int32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // Σ of the positions of the set bits of m: six masked popcounts (bit j of the position).
 __device__ __forceinline__ uint32_t bit_position_sum(uint64_t m) {
   return (uint32_t)__popcll(m & 0xAAAAAAAAAAAAAAAAull) + 2u * (uint32_t)__popcll(m & 0xCCCCCCCCCCCCCCCCull) +
          4u * (uint32_t)__popcll(m & 0xF0F0F0F0F0F0F0F0ull) + 8u * (uint32_t)__popcll(m & 0xFF00FF00FF00FF00ull) +
          16u * (uint32_t)__popcll(m & 0xFFFF0000FFFF0000ull) + 32u * (uint32_t)__popcll(m & 0xFFFFFFFF00000000ull);
 }
-
-// One slice's plane: word (y, k) masked to the width, 0 outside the plane.
-struct Plane {
-  const uint64_t* p;
-  int w, h, n;
-  __device__ __forceinline__ uint64_t at(int y, int k) const {
-    if (y < 0 || y >= h || k < 0 || k >= n) return 0ull;
-    return p[(size_t)y * n + k] & row_word_mask(k, w);
-  }
-  // Column of the first pixel of the run that contains the set pixel (y, x): the position after the
-  // highest clear bit below x, walking left through full words (at most n of them).
-  __device__ __forceinline__ int run_start(int y, int x) const {
-    int k = x >> 6;
-    const int b = x & 63;
-    uint64_t z = ~at(y, k) & ((b == 63) ? ~0ull : ((2ull << b) - 1ull));
-    while (z == 0ull && k > 0) {
-      --k;
-      z = ~at(y, k);
-    }
-    return z == 0ull ? 0 : (k << 6) + 64 - __clzll((long long)z);
-  }
-};
 
 // Root of x, halving the path on the way: a node passed over is pointed at its grandparent with an
 // atomicMin that returns nothing (no wait), so parents only ever decrease and stay ancestors.

@@ -248,6 +248,33 @@ SliceMeasure measure_from(const py::dict& d) {
   return m;
 }
 
+// The integers of a diameter record (nm03/measure.h SliceDiameters) as a dict.
+py::dict diameters_dict(const SliceDiameters& m) {
+  py::dict d;
+  d["lesion_px"] = m.lesion_px;
+  d["lesion_first"] = py::make_tuple(m.lesion_first[0], m.lesion_first[1]).cast<py::list>();
+  d["major_px2"] = m.major_px2;
+  py::list a, b;
+  for (int k = 0; k < 4; ++k) a.append(m.major[k]), b.append(m.perp[k]);
+  d["major"] = a;
+  d["perp_extent"] = m.perp_extent;
+  d["perp"] = b;
+  return d;
+}
+
+SliceDiameters diameters_from(const py::dict& d) {
+  SliceDiameters m{};
+  m.lesion_px = d["lesion_px"].cast<uint32_t>();
+  const std::vector<int> f = d["lesion_first"].cast<std::vector<int>>(), a = d["major"].cast<std::vector<int>>(),
+                         b = d["perp"].cast<std::vector<int>>();
+  if (f.size() != 2 || a.size() != 4 || b.size() != 4) throw std::invalid_argument("lesion_first needs two values, major and perp four");
+  m.lesion_first[0] = f[0], m.lesion_first[1] = f[1];
+  m.major_px2 = d["major_px2"].cast<uint32_t>();
+  m.perp_extent = d["perp_extent"].cast<uint32_t>();
+  for (int k = 0; k < 4; ++k) m.major[k] = a[(size_t)k], m.perp[k] = b[(size_t)k];
+  return m;
+}
+
 // The integers of a volume record (nm03/measure.h VolumeMeasure) as a dict.
 py::dict volume_measure_dict(const VolumeMeasure& m) {
   py::dict d;
@@ -399,6 +426,7 @@ PYBIND11_MODULE(_nm03, m) {
       .def_readwrite("frame", &PipelineParams::frame)
       .def_readwrite("se_shape", &PipelineParams::se_shape)
       .def_readwrite("measure", &PipelineParams::measure)
+      .def_readwrite("measure_diameters", &PipelineParams::measure_diameters)
       .def_property(
           "measure_connectivity", [](const PipelineParams& p) { return (int)p.measure_connectivity; },
           [](PipelineParams& p, int v) {
@@ -754,10 +782,16 @@ PYBIND11_MODULE(_nm03, m) {
           d["overlay"] = to_np<uint8_t>(j.overlay_canvas, {rp.out_height, rp.out_width, 3});
           d["jpeg_overlay"] = py::bytes((const char*)j.overlay.data(), j.overlay.size());
         }
-        if (p.measure) {
+        if (p.measure || p.measure_diameters) {
           const SliceMeasure sm = golden::measure(r.dilated, r.region, s, p.measure_connectivity);
           d["measure"] = measure_dict(sm);
-          d["measure_json"] = golden::measure_json(sm, s, p);
+          if (p.measure_diameters) {
+            const SliceDiameters sd = golden::measure_diameters(r.dilated, p.measure_connectivity, s.w, s.h);
+            d["diameters"] = diameters_dict(sd);
+            d["measure_json"] = golden::measure_json(sm, sd, s, p);
+          } else {
+            d["measure_json"] = golden::measure_json(sm, s, p);
+          }
         }
         return d;
       },
@@ -895,6 +929,26 @@ PYBIND11_MODULE(_nm03, m) {
       },
       py::arg("record"), py::arg("w"), py::arg("h"), py::arg("spacing_x") = 1.f, py::arg("spacing_y") = 1.f,
       py::arg("slope") = 1.f, py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 8);
+
+  // The diameter record (nm03/measure.h SliceDiameters) of a mask [H, W] from the golden model.
+  m.def(
+      "golden_measure_diameters",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> mask, int connectivity) {
+        if (mask.ndim() != 2) throw std::invalid_argument("mask must be [H, W]");
+        return diameters_dict(golden::measure_diameters(from_np<uint8_t>(mask), connectivity, (int)mask.shape(1), (int)mask.shape(0)));
+      },
+      py::arg("mask"), py::arg("connectivity") = 8);
+  // The sidecar text with the diameter keys (the one function every path calls).
+  m.def(
+      "measure_diameters_to_json",
+      [](const py::dict& rec, const py::dict& diam, int w, int h, float sx, float sy, float slope, float intercept,
+         bool apply_rescale, int connectivity) {
+        return measure::to_json(measure_from(rec), diameters_from(diam), w, h, sx, sy, slope, intercept, apply_rescale,
+                                connectivity);
+      },
+      py::arg("record"), py::arg("diameters"), py::arg("w"), py::arg("h"), py::arg("spacing_x") = 1.f,
+      py::arg("spacing_y") = 1.f, py::arg("slope") = 1.f, py::arg("intercept") = 0.f, py::arg("apply_rescale") = true,
+      py::arg("connectivity") = 8);
 
   // ---- volume measurements (nm03/measure.h VolumeMeasure) ----------------------------------------------
   auto volume_arrays = [](const py::array_t<uint8_t, py::array::c_style | py::array::forcecast>& dil,
@@ -1153,6 +1207,7 @@ PYBIND11_MODULE(_nm03, m) {
              if (e.config().pipe.measure) {
                d["measure"] = measure_dict(r.measure);
                d["measure_json"] = r.measure_json;
+               if (e.config().pipe.measure_diameters) d["diameters"] = diameters_dict(r.diameters);
              }
              return d;
            },
@@ -1741,6 +1796,72 @@ PYBIND11_MODULE(_nm03, m) {
     return out;
   }, py::arg("planes"), py::arg("raw"), py::arg("hs"), py::arg("ws"), py::arg("type") = "u16", py::arg("stored_bits") = 16,
      py::arg("connectivity") = 8, py::arg("stream") = 0);
+
+  // K7 then K9 on a batch of masks of ANY sizes, one launch each: planes = the masks' bit planes back to
+  // back (mask i: hs[i] × ceil(ws[i] / 64) words); raw = at least Σ hs[i] · ws[i] u16 samples for K7's
+  // intensity figures (their values do not matter here). Returns one diameter record dict per mask.
+  m.def("k_measure_diameters", [](uintptr_t planes, uintptr_t raw, const std::vector<int>& hs, const std::vector<int>& ws,
+                                  int connectivity, uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    const int n = (int)hs.size();
+    if (n <= 0 || ws.size() != hs.size()) throw std::invalid_argument("one height and one width per mask");
+    if (connectivity != 4 && connectivity != 8) throw std::invalid_argument("connectivity must be 4 or 8");
+    {
+      // K7's and K9's code objects, loaded on the current device before this op's first launch there.
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_measure();
+        gpu::preload_measure_diameters();
+        preloaded.push_back(dev);
+      }
+    }
+    std::vector<gpu::SliceDesc> d((size_t)n);
+    size_t raw_off = 0, mask_off = 0;
+    int max_w = 0, max_h = 0;
+    for (int i = 0; i < n; ++i) {
+      const int h = hs[(size_t)i], w = ws[(size_t)i];
+      if (w <= 0 || h <= 0 || w > gpu::kMaxSliceDim || h > gpu::kMaxSliceDim) throw std::invalid_argument("bad mask size");
+      gpu::SliceDesc& s = d[(size_t)i];
+      std::memset(&s, 0, sizeof(s));
+      s.raw_off = (uint32_t)raw_off;
+      s.mask_off = (uint32_t)mask_off;
+      s.w = (uint16_t)w;
+      s.h = (uint16_t)h;
+      s.wpr = (uint16_t)((w + 63) / 64);
+      s.type = kU16;
+      s.stored_bits = 16;
+      raw_off += (size_t)h * w;
+      mask_off += (size_t)h * s.wpr;
+      max_w = std::max(max_w, w);
+      max_h = std::max(max_h, h);
+    }
+    if (raw_off > 0xFFFFFFFFull) throw std::invalid_argument("batch exceeds 2^32 samples");
+    const size_t per = gpu::measure_scratch_words(max_w, max_h);
+    const size_t o_desc = 0, o_out = (sizeof(gpu::SliceDesc) * n + 255) / 256 * 256,
+                 o_dia = (o_out + sizeof(SliceMeasure) * n + 255) / 256 * 256,
+                 o_par = (o_dia + sizeof(SliceDiameters) * n + 255) / 256 * 256, total = o_par + per * n * sizeof(uint32_t);
+    uint8_t* dev = (uint8_t*)scratch().get(total);
+    gpu::check_hip(hipMemcpyAsync(dev + o_desc, d.data(), sizeof(gpu::SliceDesc) * n, hipMemcpyHostToDevice, st), "H2D descriptors");
+    gpu::check_hip(hipStreamSynchronize(st), "sync descriptors");
+    const uint64_t* pl = (const uint64_t*)planes;
+    gpu::launch_measure(pl, pl, (const uint16_t*)raw, (const gpu::SliceDesc*)(dev + o_desc), n, connectivity,
+                        (SliceMeasure*)(dev + o_out), (uint32_t*)(dev + o_par), max_w, max_h, st);
+    gpu::launch_measure_diameters(pl, (const gpu::SliceDesc*)(dev + o_desc), n, (SliceDiameters*)(dev + o_dia),
+                                  (const uint32_t*)(dev + o_par), max_w, max_h, st);
+    std::vector<SliceDiameters> res((size_t)n);
+    gpu::check_hip(hipMemcpyAsync(res.data(), dev + o_dia, sizeof(SliceDiameters) * n, hipMemcpyDeviceToHost, st), "D2H records");
+    gpu::check_hip(hipStreamSynchronize(st), "k_measure_diameters");
+    py::list out;
+    for (auto& r : res) {
+      if (r.lesion_px == kDiametersNotMeasured) throw std::runtime_error("k_measure_diameters: a mask was not measured");
+      out.append(diameters_dict(r));
+    }
+    return out;
+  }, py::arg("planes"), py::arg("raw"), py::arg("hs"), py::arg("ws"), py::arg("connectivity") = 8, py::arg("stream") = 0);
 
   // K8 on bit volumes [d][h][ceil(w/64)] (int64 words): `dilated` and `region`, the 16-bit samples
   // `raw` [d][h][w]. Returns the record dict. Synchronous on `stream`; the scratch is kept across calls.

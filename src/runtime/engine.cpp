@@ -168,6 +168,9 @@ struct Slot {
   uint32_t* d_ms_scratch = nullptr;
   SliceMeasure* h_measure = nullptr;
   SliceMeasure* d_measure = nullptr;
+  // Diameters (PipelineParams::measure_diameters; null without it): K9's host-mapped records.
+  SliceDiameters* h_diam = nullptr;
+  SliceDiameters* d_diam = nullptr;
 };
 
 // Private fd tables for the host pool's workers. Every open and
@@ -239,6 +242,7 @@ void hip_free_all(Slot& s) {
   if (s.h_ov_out) (void)hipHostFree(s.h_ov_out);
   if (s.h_ov_sizes) (void)hipHostFree(s.h_ov_sizes);
   if (s.h_measure) (void)hipHostFree(s.h_measure);
+  if (s.h_diam) (void)hipHostFree(s.h_diam);
   if (s.d_ms_scratch) (void)hipFree(s.d_ms_scratch);
   for (void* p : {(void*)s.d_rgb, (void*)s.ov_jw.look, (void*)s.ov_jw.ticket, (void*)s.ov_jw.spill, (void*)s.d_ov_jd})
     if (p) (void)hipFree(p);
@@ -321,6 +325,8 @@ struct Engine::Impl {
     ov_cap_ = cfg.jpeg_out_cap ? out_cap_ : (2 * (out_cap_ - 64) + 64 + 15u) & ~15u;
     ov_color_ = (uint32_t)cfg.render.overlay_color[0] | ((uint32_t)cfg.render.overlay_color[1] << 8) |
                 ((uint32_t)cfg.render.overlay_color[2] << 16);
+    diameters_ = cfg.pipe.measure_diameters;
+    if (diameters_) cfg.pipe.measure = true;  // the diameters are measured on K7's labelling
     measure_ = cfg.pipe.measure;
     if (measure_ && cfg.host_only)
       throw std::invalid_argument("measure runs on the GPU (the K7 kernel): not available with host_only");
@@ -382,6 +388,7 @@ struct Engine::Impl {
       // loads it), and here — never lazily from a slot thread.
       if (overlay_) preload_jpeg_rgb();
       if (measure_) preload_measure();  // likewise: only an engine that will launch K7 loads it
+      if (diameters_) preload_measure_diameters();  // and K9
       d_lut_ = dmalloc<float>(kLutArenaFloats, "hipMalloc norm tables");
     }
     const double t1 = now_s();
@@ -736,6 +743,12 @@ struct Engine::Impl {
         check_hip(hipHostMalloc((void**)&s.h_measure, sizeof(SliceMeasure) * n, hipHostMallocMapped), "hipHostMalloc measure");
         check_hip(hipHostGetDevicePointer((void**)&s.d_measure, s.h_measure, 0), "hipHostGetDevicePointer measure");
         mark("measure");
+      }
+      if (diameters_) {
+        const int n = s.cap_slices;
+        check_hip(hipHostMalloc((void**)&s.h_diam, sizeof(SliceDiameters) * n, hipHostMallocMapped), "hipHostMalloc diameters");
+        check_hip(hipHostGetDevicePointer((void**)&s.d_diam, s.h_diam, 0), "hipHostGetDevicePointer diameters");
+        mark("diameters");
       }
     } catch (...) {
       hip_free_all(s);
@@ -1188,6 +1201,8 @@ struct Engine::Impl {
     if (measure_)
       launch_measure(plane(kPDilated), plane(kPRegion), d_raw, d_desc, nl, cfg.pipe.measure_connectivity, s.d_measure,
                      s.d_ms_scratch, s.max_w, s.max_h, s.stream);
+    if (diameters_)
+      launch_measure_diameters(plane(kPDilated), d_desc, nl, s.d_diam, s.d_ms_scratch, s.max_w, s.max_h, s.stream);
     if (s.any_canvas) launch_render(d_raw, s.d_f32, s.d_bits, d_stats, d_rd, ncanv, cw, ch, s.d_canvas, s.stream);
     JpegRenderSrc rsrc;
     rsrc.raw = d_raw;
@@ -1264,6 +1279,12 @@ struct Engine::Impl {
     const LoadedSlice& L = s.loaded[(size_t)s.live[(size_t)c]];
     const SliceMeasure& m = s.h_measure[c];
     if (m.components == 0xFFFFFFFFu) throw DeviceError("measure: slice exceeds the measurement scratch");
+    if (diameters_) {
+      const SliceDiameters& dm = s.h_diam[c];
+      if (dm.lesion_px == kDiametersNotMeasured) throw DeviceError("measure: slice exceeds the measurement scratch");
+      return measure::to_json(m, dm, L.w, L.h, L.sx, L.sy, L.slope, L.intercept, cfg.pipe.apply_rescale,
+                              cfg.pipe.measure_connectivity);
+    }
     return measure::to_json(m, L.w, L.h, L.sx, L.sy, L.slope, L.intercept, cfg.pipe.apply_rescale,
                             cfg.pipe.measure_connectivity);
   }
@@ -1797,6 +1818,7 @@ struct Engine::Impl {
     }
     if (measure_) {
       r.measure = s.h_measure[0];
+      if (diameters_) r.diameters = s.h_diam[0];
       r.measure_json = measure_text(s, 0);
     }
     return r;
@@ -1812,6 +1834,8 @@ struct Engine::Impl {
   uint32_t ov_color_ = 0;
   // Measurements (PipelineParams::measure): K7 after K2 on every batch, a sidecar per slice.
   bool measure_ = false;
+  // Diameters (PipelineParams::measure_diameters): K9 after K7, further keys in the sidecar.
+  bool diameters_ = false;
 };
 
 Engine::Engine(const EngineConfig& cfg) : impl_(std::make_unique<Impl>(cfg)) {}
