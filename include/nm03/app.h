@@ -92,6 +92,9 @@ struct AppConfig {
   // (nm03/measure.h VolumeMeasure); components at measure_volume_connectivity (6 | 26).
   bool measure_volume = false;
   int measure_volume_connectivity = 26;
+  // --measure-volume-lesions N (implies --measure-volume): the sidecar also lists the N largest
+  // lesions (nm03/measure.h VolumeLesion) and rank 0 writes <out>/lesions.csv; 0 = off, else 1 … 64.
+  int measure_volume_lesions = 0;
   // CLOCK_REALTIME when parse_args began (the --json record's "main_unix_s"): with the launcher's
   // own clock it splits a cold run's wall into process start-up (exec → main) and the rest.
   double main_unix_s = 0;
@@ -168,8 +171,14 @@ struct VolumeTotals {
   int64_t volumes = 0;  // patients with a sidecar
   uint64_t volume_vox = 0;
   double volume_mm3 = 0;
+  int64_t lesions = -1;  // --measure-volume-lesions: rows of lesions.csv over the job's measured patients (−1: not asked for)
 };
 VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows);
+// --measure-volume-lesions: <out_root>/lesions.csv from the same sidecar texts, in plan order: a header,
+// then one row per reported lesion (patient, lesion = its 0-based rank, then the lesion object's fields
+// with first and bbox flattened); a failed patient has one row with its status name in `lesion` and
+// empty fields. Returns the number of lesion rows.
+int64_t write_lesions_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows);
 std::string volume_totals_json(const VolumeTotals& t);  // the --json record's "measure_volume" object
 
 // Number of GPUs visible to this process, counted WITHOUT initialising HIP (KFD topology +

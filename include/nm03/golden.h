@@ -121,6 +121,15 @@ VolumeMeasure measure_volume(const std::vector<uint8_t>& dilated, const std::vec
                              int connectivity);
 // The sidecar text of a record for volume `v` (measure::volume_to_json with the volume's fields).
 std::string measure_volume_json(const VolumeMeasure& m, const VolumeInput& v, bool apply_rescale, int connectivity);
+// The `max_lesions` (1 … kMaxVolumeLesions) largest components of `dilated` at `connectivity`
+// (VolumeParams::measure_lesions, nm03/measure.h VolumeLesion), largest first; a tie goes to the
+// component whose first voxel in raster order comes first. Independent of the K10 kernels: a flood
+// fill per component with per-voxel statistics and face loops, then a sort.
+std::vector<VolumeLesion> measure_volume_lesions(const std::vector<uint8_t>& dilated, const VolumeInput& v,
+                                                 int connectivity, int max_lesions);
+// The sidecar text with the lesion keys (the matching measure::volume_to_json overload).
+std::string measure_volume_json(const VolumeMeasure& m, const std::vector<VolumeLesion>& lesions, int max_lesions,
+                                const VolumeInput& v, bool apply_rescale, int connectivity);
 
 struct SliceResult {
   std::vector<float> clipped, median, sharpened;

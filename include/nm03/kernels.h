@@ -210,13 +210,36 @@ void preload_measure_diameters();
 // do not fit 32 bits, and for a connectivity other than 6 / 26.
 using nm03::volume_measure_scratch_words;
 constexpr int kVolumeMeasureAccWords = 32;
+// `lesions` (optional, --measure-volume-lesions): the K10 launches below are enqueued between the two
+// passes; null leaves the twelve launches as they are.
+struct VolumeLesionWork {
+  int max_lesions = 0;            // N, 1..kMaxVolumeLesions
+  void* work = nullptr;           // volume_lesions_work_bytes(w, h, d, N) of device memory, no initialisation needed
+  VolumeLesion* out = nullptr;    // N records (device, pinned or host-mapped memory); those past the count are zero
+  uint32_t* out_count = nullptr;  // the reported count, min(N, components)
+};
 void launch_volume_measure(const uint64_t* dilated, const uint64_t* region, const uint16_t* raw, size_t raw_plane_stride,
                            int w, int h, int d, uint8_t type, uint8_t stored_bits, int connectivity, uint32_t* scratch,
-                           uint64_t* acc, VolumeMeasure* out, hipStream_t stream);
+                           uint64_t* acc, VolumeMeasure* out, hipStream_t stream,
+                           const VolumeLesionWork* lesions = nullptr);
 // Loads K8's code object on the current device. Not part of preload_kernels: only a VolumeRunner's
 // first measuring run (before that run's first launch, while its stream is idle) and the Python op
 // (before its first launch) load it, so a run without --measure-volume never pays for it.
 void preload_volume_measure();
+
+// K10 (k10_volume_lesions.hip): the VolumeLesion records (nm03/measure.h) of the N largest components
+// of the `dilated` bit volume, from K8's labelling of the mask as vm_roots_kernel leaves it in
+// `scratch` (launch_volume_measure enqueues this between its two passes). Five launches on `stream`:
+// init, candidates (every workgroup's N best roots), select (one workgroup), accumulate (a thread per
+// word), final. No host round trip, no allocation; records and count are written with plain vector
+// stores. The candidate list holds N keys per workgroup of the word grid, so it cannot overflow.
+size_t volume_lesions_work_bytes(int w, int h, int d, int max_lesions);
+void launch_volume_lesions(const uint64_t* dilated, const uint16_t* raw, size_t raw_plane_stride, int w, int h, int d,
+                           uint8_t type, uint8_t stored_bits, const uint32_t* scratch, const VolumeLesionWork& lesions,
+                           hipStream_t stream);
+// Loads K10's code object on the current device: only a VolumeRunner's first run that asks for lesions
+// and the Python op load it.
+void preload_volume_lesions();
 
 // K6: binary threshold lo ≤ x ≤ hi → u8 0/1 (in 16-byte aligned, out 4-byte aligned).
 void launch_threshold(const float* in, uint8_t* out, size_t n, float lo, float hi, hipStream_t stream);

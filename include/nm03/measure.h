@@ -121,6 +121,23 @@ struct alignas(64) VolumeMeasure {
 };
 static_assert(sizeof(VolumeMeasure) == 128, "VolumeMeasure layout");
 
+// One lesion of the dilated volume (--measure-volume-lesions N): the record the K10 kernels write for
+// each of the N largest connected components at the measurement connectivity. Order: voxels
+// descending; a tie goes to the lesion whose first voxel in raster (z, y, x) order comes first. Exact
+// integers with the definitions of the global record, so over ALL components they add up to it: a face
+// between a mask voxel and a non-mask voxel (or the frame) belongs to the mask voxel's lesion.
+struct alignas(64) VolumeLesion {
+  uint64_t voxels;                     // voxel count
+  int32_t first[3];                    // x, y, z of the first voxel in raster order
+  int32_t bbox[6];                     // x0, y0, z0, x1, y1, z1 inclusive
+  uint64_t sum_x, sum_y, sum_z;        // coordinate sums
+  uint64_t faces_x, faces_y, faces_z;  // voxel faces normal to each axis against non-mask / the frame
+  int64_t raw_sum;                     // over the stored sample values under the lesion
+  int32_t raw_min, raw_max;
+};
+static_assert(sizeof(VolumeLesion) == 128, "VolumeLesion layout");
+constexpr int kMaxVolumeLesions = 64;
+
 // Euler number of a bit volume from window counts over the zero-padded volume: n3 = set voxels,
 // n2 = pairs of face-adjacent positions, n1 = 2×2 windows (three orientations), n0 = 2×2×2 windows.
 // At 26-connectivity a pair or window counts when ANY of its voxels is set and
@@ -199,6 +216,23 @@ std::string volume_to_json(const VolumeMeasure& m, int w, int h, int d, double s
 // after the other: what the kernels compute, without a GPU.
 VolumeMeasure volume_words(const uint64_t* dilated, const uint64_t* region, const uint16_t* raw, size_t raw_plane_stride,
                            int w, int h, int d, int wpr, uint8_t type, uint8_t stored_bits, int connectivity);
+
+// The sidecar text with --measure-volume-lesions: the text above with two keys after `mean` —
+// lesions_max (the N asked for) and lesions, an array of `count` objects in the records' order, each
+// with keys in fixed order: voxels, first [x, y, z], bbox [x0, y0, z0, x1, y1, z1], sum_x / _y / _z,
+// faces_x / _y / _z, raw_sum, raw_min, raw_max, then the derived doubles (%.9g): volume_mm3,
+// volume_ml, surface_mm2 (the formulas above on the lesion's integers), equivalent_diameter_mm =
+// cbrt(6 · volume_mm3 / π), centroid_x / _y / _z, centroid_*_mm and mean.
+std::string volume_to_json(const VolumeMeasure& m, const VolumeLesion* lesions, int count, int lesions_max, int w, int h,
+                           int d, double spacing_x, double spacing_y, double spacing_z,
+                           const std::string& spacing_z_source, float slope, float intercept, bool apply_rescale,
+                           int connectivity);
+
+// The `max_lesions` largest components of a bit volume computed on the host with the per-word lesion
+// logic of the K10 kernels (nm03/volume_measure_core.h: root keys, stretch figures) on K8's run
+// union-find, one word after the other. Returns the reported count, min(max_lesions, components).
+int volume_lesions_words(const uint64_t* dilated, const uint16_t* raw, size_t raw_plane_stride, int w, int h, int d,
+                         int wpr, uint8_t type, uint8_t stored_bits, int connectivity, int max_lesions, VolumeLesion* out);
 
 inline const char* volume_sidecar_name() { return "volume_measure.json"; }
 

@@ -58,7 +58,10 @@ struct VolumeResult {
   std::vector<uint8_t> band, region, dilated;  // 0/1 per voxel (when requested)
   double kernels_s = 0;
   VolumeMeasure measure = {};  // VolumeParams::measure: the K8 record of the dilated volume
-  double measure_s = 0;        // GPU time of the K8 launches (outside kernels_s)
+  double measure_s = 0;        // GPU time of the K8 launches (outside kernels_s; the K10 launches included)
+  // VolumeParams::measure_lesions: the K10 records of the largest components, largest first
+  // (min(measure_lesions, measure.components) of them).
+  std::vector<VolumeLesion> lesions;
 };
 
 struct VolumeExportStats {
@@ -74,6 +77,9 @@ struct VolumeParams {
   std::vector<Seed> seeds;    // empty → reference seed pattern on the middle slice
   bool measure = false;           // also measure the dilated volume (K8, nm03/measure.h VolumeMeasure)
   int measure_connectivity = 26;  // 6 | 26: components; cavities use the dual
+  // With measure: also one record per lesion for the N largest components (K10, nm03/measure.h
+  // VolumeLesion); 0 = off, else 1 … kMaxVolumeLesions.
+  int measure_lesions = 0;
 };
 
 // Runs the 3D pipeline on `device`; copies masks back when `want_masks`. A VolumeRunner keeps
@@ -86,7 +92,8 @@ class VolumeRunner {
   VolumeRunner(const VolumeRunner&) = delete;
   VolumeRunner& operator=(const VolumeRunner&) = delete;
   // With p.measure the K8 kernels run after the segmentation (first use loads their code object and
-  // allocates their scratch, kept like the other buffers); without it nothing of K8 is touched.
+  // allocates their scratch, kept like the other buffers); without it nothing of K8 is touched. The
+  // same holds for p.measure_lesions and K10.
   VolumeResult run(const VolumeInput& v, const VolumeParams& p, bool want_masks);
   // After run() on the same volume: the 2·d exported JPEG files of the 3D cohort mode, in plane
   // order (original, processed), rendered and encoded on the GPU (K3/K4) from the volume still on
@@ -98,7 +105,8 @@ class VolumeRunner {
   // coordinates. Preprocesses the slab's planes, runs the global region-growing fixpoint and the
   // halo cube dilation with the other ranks of `comm` (collective), leaving the slab on the device:
   // export_jpegs(slab, ...) then exports its planes. Masks (when requested) are the slab's.
-  // p.measure throws std::invalid_argument: components that cross slabs would need a collective.
+  // p.measure or p.measure_lesions throws std::invalid_argument: components that cross slabs would
+  // need a collective.
   VolumeResult run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p, bool want_masks,
                         struct SlabStats* stats = nullptr);
 

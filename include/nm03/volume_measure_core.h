@@ -268,4 +268,116 @@ NM03_HD void count_roots(const BitVolume& V, P& par, int z, int y, int k, uint32
   }
 }
 
+// ---- per-lesion phase (K10): on the MASK pass's final labelling ----------------------------------
+// After phases C and D of the mask pass every run's slot holds its root and the slot after a root the
+// component's voxel count. A root is the smallest slot of its component (unions link the larger root
+// under the smaller), so it names the component's first voxel in raster (z, y, x) order.
+
+// The order of the lesions as one u64, larger = earlier: more voxels, then the smaller root slot.
+// Slots are unique, so the keys are a total order; 0 is no key (an area is at least 1).
+NM03_HD uint64_t lesion_key(uint32_t area, uint32_t slot) { return ((uint64_t)area << 32) | (uint64_t)(uint32_t)~slot; }
+NM03_HD uint32_t lesion_key_slot(uint64_t key) { return ~(uint32_t)key; }
+NM03_HD uint32_t lesion_key_area(uint64_t key) { return (uint32_t)(key >> 32); }
+
+// The voxel a slot names.
+NM03_HD void slot_voxel(const BitVolume& V, uint32_t slot, int32_t xyz[3]) {
+  const uint32_t row = slot / ((uint32_t)V.w + 1u);
+  xyz[0] = (int32_t)(slot - row * ((uint32_t)V.w + 1u));
+  xyz[2] = (int32_t)(row / (uint32_t)V.h);
+  xyz[1] = (int32_t)(row - (uint32_t)xyz[2] * (uint32_t)V.h);
+}
+
+// The bits of word (z, y, k) at which a run starts that is a root.
+template <class P>
+NM03_HD uint64_t root_bits(const BitVolume& V, P& par, int z, int y, int k) {
+  const uint64_t m = V.at(z, y, k);
+  if (m == 0ull) return 0ull;
+  const uint64_t ml = V.at(z, y, k - 1);
+  uint64_t roots = 0ull;
+  for (uint64_t t = m & ~((m << 1) | (ml >> 63)); t; t &= t - 1) {
+    const uint32_t s = V.slot(z, y, (k << 6) + ctz64(t));
+    if (par.ld(s) == s) roots |= t & (~t + 1ull);
+  }
+  return roots;
+}
+
+// The largest key among the roots at `bits` of word (z, y, k) and, in `bit`, where it starts; 0 for none.
+template <class P>
+NM03_HD uint64_t best_root_key(const BitVolume& V, P& par, int z, int y, int k, uint64_t bits, int& bit) {
+  uint64_t best = 0ull;
+  for (uint64_t t = bits; t; t &= t - 1) {
+    const int b = ctz64(t);
+    const uint32_t s = V.slot(z, y, (k << 6) + b);
+    const uint64_t key = lesion_key(par.ld(s + 1u), s);
+    if (key > best) best = key, bit = b;
+  }
+  return best;
+}
+
+// Index of `slot` in the ascending array s[0 .. n), −1 when it is not there: at most 7 probes.
+NM03_HD int find_slot(const uint32_t* s, int n, uint32_t slot) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (s[mid] < slot) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n && s[lo] == slot ? lo : -1;
+}
+
+// The voxels of word (z, y, k) with an open face — the neighbour on that side is not mask, or the
+// frame — on each of the six sides: the global record's faces, kept as bits so that they can be
+// masked to the voxels of one lesion.
+struct WordFaces {
+  uint64_t xl, xh, yl, yh, zl, zh;
+};
+NM03_HD WordFaces word_faces(const BitVolume& V, int z, int y, int k, uint64_t m) {
+  const uint64_t ml = V.at(z, y, k - 1), mr = V.at(z, y, k + 1);
+  WordFaces f;
+  f.xl = m & ~((m << 1) | (ml >> 63));
+  f.xh = m & ~((m >> 1) | (mr << 63));
+  f.yl = m & ~V.at(z, y - 1, k);
+  f.yh = m & ~V.at(z, y + 1, k);
+  f.zl = m & ~V.at(z - 1, y, k);
+  f.zh = m & ~V.at(z + 1, y, k);
+  return f;
+}
+
+// The figures of a set of voxels of one lesion (the intensities aside).
+struct LesionFigures {
+  uint64_t vox = 0, sum_x = 0, sum_y = 0, sum_z = 0, faces_x = 0, faces_y = 0, faces_z = 0;
+  int32_t x0 = 0x7FFFFFFF, y0 = 0x7FFFFFFF, z0 = 0x7FFFFFFF, x1 = -1, y1 = -1, z1 = -1;
+};
+
+// Adds the share of the voxels `s` ≠ 0 of word (z, y, k) — stretches of one lesion — to f.
+NM03_HD void lesion_bits_figures(int z, int y, int k, const WordFaces& wf, uint64_t s, LesionFigures& f) {
+  const uint32_t c = (uint32_t)pop64(s);
+  f.vox += c;
+  f.sum_x += (uint64_t)c * (uint32_t)(k << 6) + bit_position_sum(s);
+  f.sum_y += (uint64_t)c * (uint32_t)y;
+  f.sum_z += (uint64_t)c * (uint32_t)z;
+  const int lo = (k << 6) + ctz64(s), hi = (k << 6) + 63 - clz64(s);
+  f.x0 = lo < f.x0 ? lo : f.x0;
+  f.x1 = hi > f.x1 ? hi : f.x1;
+  f.y0 = y < f.y0 ? y : f.y0;
+  f.y1 = y > f.y1 ? y : f.y1;
+  f.z0 = z < f.z0 ? z : f.z0;
+  f.z1 = z > f.z1 ? z : f.z1;
+  f.faces_x += (uint64_t)(pop64(s & wf.xl) + pop64(s & wf.xh));
+  f.faces_y += (uint64_t)(pop64(s & wf.yl) + pop64(s & wf.yh));
+  f.faces_z += (uint64_t)(pop64(s & wf.zl) + pop64(s & wf.zh));
+}
+
+// Every in-word stretch of word (z, y, k) = m: emit(root of its run, the stretch's bits).
+template <class P, class Emit>
+NM03_HD void lesion_stretches(const BitVolume& V, P& par, int z, int y, int k, uint64_t m, Emit&& emit) {
+  for (uint64_t t = m & ~(m << 1); t; t &= t - 1) {
+    const int b = ctz64(t);
+    const uint64_t rest = ~(m >> b);  // bit j clear while voxel b + j is set
+    const uint32_t len = rest == 0ull ? 64u - (uint32_t)b : (uint32_t)ctz64(rest);
+    const uint64_t bits = (len == 64u ? ~0ull : ((1ull << len) - 1ull)) << b;
+    emit(compressed_root(par, V.run_slot(z, y, (k << 6) + b)), bits);
+  }
+}
+
 }  // namespace nm03::vmcore

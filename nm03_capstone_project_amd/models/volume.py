@@ -5,7 +5,10 @@
 
 With `measure=True` every run also measures the dilated volume on the GPU (K8, nm03/measure.h
 VolumeMeasure): the result gains `measure` (the record's integers) and `measure_json` (the text of the
-CLI's volume_measure.json, from the one native volume_to_json)."""
+CLI's volume_measure.json, from the one native volume_to_json). With `measure_lesions=N` (1 … 64; needs
+`measure`) the K10 kernels also report the N largest connected components: the result gains `lesions`
+(a list of dicts of each record's integers, largest first) and `measure_json` is the longer text with
+the `lesions_max` / `lesions` keys."""
 import numpy as np
 
 from .._native import native
@@ -20,7 +23,7 @@ def _meta_args(meta):
 
 class VolumePipeline:
     def __init__(self, config: PipelineConfig = None, connectivity: int = 6, dilation: int = 7, measure: bool = False,
-                 measure_connectivity: int = 26):
+                 measure_connectivity: int = 26, measure_lesions: int = 0):
         self.config = config or PipelineConfig()
         self.connectivity = connectivity
         self.dilation = dilation
@@ -28,6 +31,11 @@ class VolumePipeline:
         self.measure_connectivity = int(measure_connectivity)
         if self.measure_connectivity not in (6, 26):
             raise ValueError(f"3D measurement connectivity must be 6 or 26 (got {measure_connectivity})")
+        self.measure_lesions = int(measure_lesions)
+        if self.measure_lesions and not self.measure:
+            raise ValueError("measure_lesions needs measure=True")
+        if not 0 <= self.measure_lesions <= 64:
+            raise ValueError(f"measure_lesions must be 0 (off) or 1..64 (got {measure_lesions})")
         self._runners = {}  # device -> native VolumeRunner (buffers/stream reused across volumes)
 
     def default_seeds(self, volume):
@@ -48,7 +56,8 @@ class VolumePipeline:
             return runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s)
         return runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s, measure=self.measure,
                           measure_connectivity=self.measure_connectivity, spacing=[float(v) for v in spacing],
-                          spacing_z_source=str(spacing_z_source), **_meta_args(meta))
+                          spacing_z_source=str(spacing_z_source), measure_lesions=self.measure_lesions,
+                          **_meta_args(meta))
 
     def run_series(self, series_dir, seeds=None, device=None):
         """A DICOM series directory as one volume (utils.read_series: the reference's file-number
@@ -85,7 +94,8 @@ class VolumePipeline:
     def golden_measure(self, dilated, region, raw, spacing=(1.0, 1.0, 1.0), spacing_z_source="default", meta=None):
         """The golden model's record of `dilated` (+ popcount of `region`) over the samples `raw`
         ([D, H, W] each) at this pipeline's measure_connectivity → (measure dict, measure_json text):
-        what `run` returns under those keys when measuring."""
+        what `run` returns under those keys when measuring. With measure_lesions the text is the longer
+        one and the tuple has a third member, the list of lesion dicts (`run`'s `lesions`)."""
         n = native()
         a = _meta_args(meta)
         d, h, w = np.asarray(dilated).shape
@@ -93,7 +103,13 @@ class VolumePipeline:
                                       np.ascontiguousarray(region, dtype=np.uint8),
                                       np.ascontiguousarray(raw, dtype=np.uint16), a["type"], a["stored_bits"],
                                       self.measure_connectivity)
+        lesions = None
+        if self.measure_lesions:
+            lesions = n.golden_measure_volume_lesions(np.ascontiguousarray(dilated, dtype=np.uint8),
+                                                      np.ascontiguousarray(raw, dtype=np.uint16), self.measure_lesions,
+                                                      a["type"], a["stored_bits"], self.measure_connectivity)
         text = n.volume_measure_to_json(rec, w, h, d, float(spacing[0]), float(spacing[1]), float(spacing[2]),
                                         str(spacing_z_source), a["slope"], a["intercept"],
-                                        bool(self.config.pipeline_params().apply_rescale), self.measure_connectivity)
-        return rec, text
+                                        bool(self.config.pipeline_params().apply_rescale), self.measure_connectivity,
+                                        lesions, self.measure_lesions)
+        return (rec, text) if lesions is None else (rec, text, lesions)

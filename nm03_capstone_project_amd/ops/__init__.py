@@ -1,6 +1,6 @@
 """torch-tensor entry points of the gfx950 kernels (K1a median, K1b sharpen+band, K2 SRG+morph,
 K3 overlay render, K4 JPEG (gray and colour), K5 3D SRG + cube / ball dilation + per-plane border, K6 threshold, K7 mask measurements,
-K8 volume measurements,
+K8 volume measurements, K10 per-lesion volume measurements,
 K9 lesion diameters) and
 plain-PyTorch fp32 references of the same ops (ops.reference).
 
@@ -9,6 +9,6 @@ the native launcher and returns torch tensors — there is no CPU/Python fallbac
 native extension the call raises.
 """
 from .kernels import (border3d, dilate3d, jpeg_encode, jpeg_encode_rgb, measure_diameters, measure_mask, measure_volume,  # noqa: F401
-                      median2d, pack_bits,
+                      measure_volume_lesions, median2d, pack_bits,
                       region_grow, region_grow3d, render_overlay, sharpen_band, threshold, unpack_bits)
 from . import reference  # noqa: F401

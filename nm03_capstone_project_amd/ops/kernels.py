@@ -335,3 +335,32 @@ def measure_volume(dilated, region, raw, connectivity=26, pixel_type="u16", stor
     rw = pack_bits(region.bool()).contiguous()
     return native().k_measure_volume(dw.data_ptr(), rw.data_ptr(), x.data_ptr(), w, h, d, pixel_type, int(stored_bits),
                                      int(connectivity), _stream())
+
+
+def measure_volume_lesions(dilated, region, raw, max_lesions, connectivity=26, pixel_type="u16", stored_bits=16):
+    """measure_volume plus one record per LESION (K10, nm03/measure.h VolumeLesion) → (record, lesions):
+    `record` is measure_volume's dict; `lesions` lists the `max_lesions` (1 … 64) largest connected
+    components of `dilated` at `connectivity`, largest first (a tie goes to the one whose first voxel in
+    raster (z, y, x) order comes first; fewer components give a shorter list, an empty mask an empty
+    one), each a dict of exact integers: voxels, first [x, y, z], bbox [x0, y0, z0, x1, y1, z1],
+    sum_x / _y / _z, faces_x / _y / _z (the lesion's open voxel faces, as in the record) and
+    raw_sum / raw_min / raw_max. Over all components the lesions' integers add up to the record's.
+
+    The lesion launches run between K8's two passes, on the labelling the mask pass leaves behind."""
+    _check_conn3d(connectivity)
+    if not 1 <= int(max_lesions) <= 64:
+        raise ValueError("max_lesions must be 1..64")
+    if dilated.dim() != 3 or region.shape != dilated.shape or raw.shape != dilated.shape:
+        raise ValueError("dilated, region and raw must be [D, H, W] of one shape")
+    if not (dilated.is_cuda and region.is_cuda):
+        raise ValueError("masks must be CUDA (HIP) tensors")
+    x = raw.contiguous()
+    _check(x, _U16, "raw")
+    d, h, w = (int(v) for v in dilated.shape)
+    if d < 1 or h < 1 or w < 1:
+        raise ValueError("empty volume")
+    dw = pack_bits(dilated.bool()).contiguous()
+    rw = pack_bits(region.bool()).contiguous()
+    rec, lesions = native().k_measure_volume_lesions(dw.data_ptr(), rw.data_ptr(), x.data_ptr(), w, h, d, int(max_lesions),
+                                                     pixel_type, int(stored_bits), int(connectivity), _stream())
+    return rec, lesions

@@ -387,6 +387,56 @@ def measure_volume(dilated, region, raw, connectivity=26, pixel_type="u16", stor
     }
 
 
+def measure_volume_lesions(dilated, region, raw, max_lesions, connectivity=26, pixel_type="u16", stored_bits=16):
+    """(record, lesions) as ops.measure_volume_lesions gives them, in NumPy + scipy.ndimage.label: the
+    record is measure_volume's; the lesions are the labels' statistics — ndimage.label numbers the
+    components in the raster order of their first voxels, so a stable sort by size gives the order
+    rule — with the open faces by shifted comparisons against the zero-padded mask."""
+    import numpy as np
+    from scipy import ndimage
+
+    def to_np(t):
+        return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+    if not 1 <= int(max_lesions) <= 64:
+        raise ValueError("max_lesions must be 1..64")
+    rec = measure_volume(dilated, region, raw, connectivity, pixel_type, stored_bits)
+    m = to_np(dilated).astype(bool)
+    lab, ncomp = ndimage.label(m, structure=ndimage.generate_binary_structure(3, 3 if connectivity == 26 else 1))
+    sizes = np.bincount(lab.ravel(), minlength=ncomp + 1)[1:]
+    order = np.argsort(-sizes, kind="stable")[:int(max_lesions)]
+    raw_v = to_np(raw).view(np.uint16).astype(np.int64)
+    sh = 16 - int(stored_bits)
+    if pixel_type == "i16":
+        raw_v = ((raw_v << sh) & 0xFFFF).astype(np.uint16).view(np.int16).astype(np.int64) >> sh
+    else:
+        raw_v = raw_v & (0xFFFF >> sh)
+    p = np.pad(m, 1)
+    core = (slice(1, -1),) * 3
+    # open[axis][side]: mask voxels whose neighbour on that side is not mask (or is the frame)
+    opened = []
+    for axis in (2, 1, 0):  # x, y, z
+        lo = [slice(1, -1)] * 3
+        hi = [slice(1, -1)] * 3
+        lo[axis], hi[axis] = slice(None, -2), slice(2, None)
+        opened.append((p[core] & ~p[tuple(lo)], p[core] & ~p[tuple(hi)]))
+    lesions = []
+    for i in order:
+        sel = lab == i + 1
+        zs, ys, xs = np.nonzero(sel)  # raster order
+        under = raw_v[sel]
+        faces = [int((a & sel).sum()) + int((b & sel).sum()) for a, b in opened]
+        lesions.append({
+            "voxels": int(sizes[i]),
+            "first": [int(xs[0]), int(ys[0]), int(zs[0])],
+            "bbox": [int(xs.min()), int(ys.min()), int(zs.min()), int(xs.max()), int(ys.max()), int(zs.max())],
+            "sum_x": int(xs.sum()), "sum_y": int(ys.sum()), "sum_z": int(zs.sum()),
+            "faces_x": faces[0], "faces_y": faces[1], "faces_z": faces[2],
+            "raw_sum": int(under.sum()), "raw_min": int(under.min()), "raw_max": int(under.max()),
+        })
+    return rec, lesions
+
+
 def psnr(a, b):
     mse = ((a.double() - b.double()) ** 2).mean().item()
     return math.inf if mse == 0 else 10 * math.log10(255.0 ** 2 / mse)

@@ -132,3 +132,27 @@ def read_volume_measurements(out_dir):
             rows.append({k: v if k in text else None if v == "" else float(v) if k in floats else int(v)
                          for k, v in r.items()})
     return rows
+
+
+def read_volume_lesions(out_dir):
+    """Rows of <out_dir>/lesions.csv (written by the 3D CLI with --measure-volume-lesions) as dicts keyed
+    by the header: one per reported lesion, patients in plan order, `lesion` the 0-based rank (largest
+    first). A failed patient has one row with its status name in `lesion` and None in every field.
+    Integer columns come back as int, the derived ones as float."""
+    import csv
+    import os
+    floats = {"volume_mm3", "volume_ml", "surface_mm2", "equivalent_diameter_mm", "centroid_x", "centroid_y", "centroid_z",
+              "centroid_x_mm", "centroid_y_mm", "centroid_z_mm", "mean"}
+    rows = []
+    with open(os.path.join(out_dir, "lesions.csv"), newline="") as f:
+        for r in csv.DictReader(f):
+            row = {}
+            for k, v in r.items():
+                if k == "patient":
+                    row[k] = v
+                elif k == "lesion":
+                    row[k] = int(v) if v.isdigit() else v
+                else:
+                    row[k] = None if v == "" else float(v) if k in floats else int(v)
+            rows.append(row)
+    return rows

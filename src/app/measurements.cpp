@@ -82,6 +82,22 @@ const char* const kVolumeColumns[] = {
 constexpr size_t kNumVolumeColumns = sizeof(kVolumeColumns) / sizeof(kVolumeColumns[0]);
 constexpr size_t kVolColVox = 4, kVolColMm3 = 30;
 
+// --measure-volume-lesions: the columns after patient, lesion — a lesion object's keys in its order, first and
+// bbox flattened.
+const char* const kLesionColumns[] = {
+    "voxels",     "first_x",    "first_y",   "first_z",       "bbox_x0",       "bbox_y0",       "bbox_z0", "bbox_x1",
+    "bbox_y1",    "bbox_z1",    "sum_x",     "sum_y",         "sum_z",         "faces_x",       "faces_y", "faces_z",
+    "raw_sum",    "raw_min",    "raw_max",   "volume_mm3",    "volume_ml",     "surface_mm2",   "equivalent_diameter_mm",
+    "centroid_x", "centroid_y", "centroid_z", "centroid_x_mm", "centroid_y_mm", "centroid_z_mm", "mean"};
+constexpr size_t kNumLesionColumns = sizeof(kLesionColumns) / sizeof(kLesionColumns[0]);
+const char* const kLesionsKey = ",\"lesions_max\":";
+
+// The volume sidecar's text without the lesion keys: what --measure-volume alone writes.
+std::string without_lesions(const std::string& text) {
+  const size_t at = text.find(kLesionsKey);
+  return at == std::string::npos ? text : text.substr(0, at) + "}\n";
+}
+
 }  // namespace
 
 VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows) {
@@ -92,7 +108,7 @@ VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<Vo
   o << "\n";
   for (const auto& r : rows) {
     std::vector<std::string> v;
-    const bool have = r.ok && parse_sidecar(r.sidecar, v, kNumVolumeColumns);
+    const bool have = r.ok && parse_sidecar(without_lesions(r.sidecar), v, kNumVolumeColumns);
     o << r.id << "," << (r.ok ? (have ? "ok" : "no_sidecar") : "failed");
     for (size_t c = 0; c < kNumVolumeColumns; ++c) {
       std::string x = have ? v[c] : std::string();
@@ -113,10 +129,58 @@ VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<Vo
 }
 
 std::string volume_totals_json(const VolumeTotals& t) {
-  char buf[200];
-  std::snprintf(buf, sizeof buf, "{\"volumes\": %lld, \"volume_vox_total\": %llu, \"volume_mm3_total\": %.9g}",
-                (long long)t.volumes, (unsigned long long)t.volume_vox, t.volume_mm3);
+  char buf[240];
+  if (t.lesions >= 0)
+    std::snprintf(buf, sizeof buf,
+                  "{\"volumes\": %lld, \"volume_vox_total\": %llu, \"volume_mm3_total\": %.9g, \"lesions\": %lld}",
+                  (long long)t.volumes, (unsigned long long)t.volume_vox, t.volume_mm3, (long long)t.lesions);
+  else
+    std::snprintf(buf, sizeof buf, "{\"volumes\": %lld, \"volume_vox_total\": %llu, \"volume_mm3_total\": %.9g}",
+                  (long long)t.volumes, (unsigned long long)t.volume_vox, t.volume_mm3);
   return buf;
+}
+
+int64_t write_lesions_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows) {
+  int64_t total = 0;
+  std::ostringstream o;
+  o << "patient,lesion";
+  for (const char* c : kLesionColumns) o << "," << c;
+  o << "\n";
+  auto empty_row = [&](const std::string& id, const char* status) {
+    o << id << "," << status;
+    for (size_t c = 0; c < kNumLesionColumns; ++c) o << ",";
+    o << "\n";
+  };
+  for (const auto& r : rows) {
+    if (!r.ok) {
+      empty_row(r.id, "failed");
+      continue;
+    }
+    // The array of flat objects after "lesions":[ — each one parses like a sidecar of its own.
+    const size_t key = r.sidecar.find(kLesionsKey);
+    const size_t open = key == std::string::npos ? key : r.sidecar.find('[', key);
+    if (open == std::string::npos) {
+      empty_row(r.id, "no_sidecar");
+      continue;
+    }
+    int rank = 0;
+    for (size_t i = r.sidecar.find('{', open); i != std::string::npos; i = r.sidecar.find('{', i)) {
+      const size_t end = r.sidecar.find('}', i);
+      if (end == std::string::npos) break;
+      std::vector<std::string> v;
+      if (!parse_sidecar(r.sidecar.substr(i, end - i + 1), v, kNumLesionColumns)) break;
+      o << r.id << "," << rank++;
+      for (const auto& x : v) o << "," << x;
+      o << "\n";
+      ++total;
+      i = end;
+    }
+  }
+  const std::string text = o.str();
+  std::ofstream f(cohort::with_slash(out_root) + "lesions.csv", std::ios::binary | std::ios::trunc);
+  f.write(text.data(), (std::streamsize)text.size());
+  if (!f) throw std::runtime_error("Cannot write " + cohort::with_slash(out_root) + "lesions.csv");
+  return total;
 }
 
 MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients,

@@ -27,6 +27,7 @@
 #include "nm03/jpeg.h"
 #include "nm03/kernels.h"
 #include "nm03/log.h"
+#include "nm03/measure.h"
 #include "nm03/metaimage.h"
 #include "nm03/numa.h"
 #include "nm03/volume.h"
@@ -68,6 +69,9 @@ void usage(const std::string& which) {
             << "                         surface, components, cavities, tunnels): <patient>/volume_measure.json and\n"
             << "                         <out>/volumes.csv (needs --mode 3d; not with --split-volume)\n"
             << "  --measure-volume-connectivity 6|26  connectivity of the 3D component count (default 26; cavities use the dual)\n"
+            << "  --measure-volume-lesions N  3d: --measure-volume plus one record per lesion for the N largest connected\n"
+            << "                         components (1..64; voxels, first voxel, bbox, sums, surface, intensities), largest\n"
+            << "                         first: keys lesions_max / lesions in the sidecar, and <out>/lesions.csv\n"
             << "  --mode 2d|3d           3d: whole series as a volume (SRG 6-conn + cube dilation)\n"
             << "  --split-volume         3d: each volume split into z-slabs over all ranks (halo exchange)\n"
             << "  --input FILE           test_pipeline: slice to process\n"
@@ -262,6 +266,17 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
       }
       c.measure_volume_connectivity = v == "6" ? 6 : 26;
     }
+    else if (a == "--measure-volume-lesions") {
+      const std::string v = val();
+      char* end = nullptr;
+      const long n = std::strtol(v.c_str(), &end, 10);
+      if (end == v.c_str() || *end || n < 1 || n > kMaxVolumeLesions) {
+        std::cerr << "--measure-volume-lesions must be 1.." << kMaxVolumeLesions << std::endl;
+        std::exit(2);
+      }
+      c.measure_volume_lesions = (int)n;
+      c.measure_volume = true;
+    }
     else if (a == "--measure-connectivity") {
       const std::string v = val();
       if (v != "4" && v != "8") {
@@ -309,6 +324,14 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
   }
   if (c.engine.pipe.measure && c.mode == "3d") {
     std::cerr << "--measure is not available with --mode 3d (use --measure-volume)" << std::endl;
+    std::exit(2);
+  }
+  if (c.measure_volume_lesions && c.mode != "3d") {
+    std::cerr << "--measure-volume-lesions needs --mode 3d" << std::endl;
+    std::exit(2);
+  }
+  if (c.measure_volume_lesions && c.split_volume) {
+    std::cerr << "--measure-volume-lesions is not available with --split-volume" << std::endl;
     std::exit(2);
   }
   if (c.measure_volume && c.mode != "3d") {

@@ -40,6 +40,7 @@ int main(int argc, char** argv) {
   int dil3d = 7;
   bool measure_volume = false;  // volume: also K8 (the volumetry of the dilated volume) per run
   int measure_volume_conn = 26;
+  int measure_volume_lesions = 0;  // volume: also K10 (one record per lesion, the N largest) per run
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto v = [&] { return std::string(argv[++i]); };
@@ -67,6 +68,14 @@ int main(int argc, char** argv) {
     else if (a == "--measure-connectivity") ec.pipe.measure_connectivity = std::atoi(v().c_str()) == 4 ? 4 : 8;
     else if (a == "--measure-volume") measure_volume = true;
     else if (a == "--measure-volume-connectivity") measure_volume_conn = std::atoi(v().c_str()) == 6 ? 6 : 26;
+    else if (a == "--measure-volume-lesions") {
+      measure_volume_lesions = std::atoi(v().c_str());
+      if (measure_volume_lesions < 1 || measure_volume_lesions > nm03::kMaxVolumeLesions) {
+        std::cerr << "--measure-volume-lesions must be 1.." << nm03::kMaxVolumeLesions << std::endl;
+        return 2;
+      }
+      measure_volume = true;
+    }
     else if (a == "--se-shape") ec.pipe.se_shape = v() == "disc" ? nm03::kSeDisc : nm03::kSeSquare;
     else if (a == "--render-filter") ec.render.filter = v() == "nearest" ? nm03::kFilterNearest : nm03::kFilterBilinear;
     else {
@@ -162,11 +171,14 @@ int main(int argc, char** argv) {
       vp.dilation_size = dil3d;
       vp.measure = measure_volume;
       vp.measure_connectivity = measure_volume_conn;
+      vp.measure_lesions = measure_volume_lesions;
       nm03::VolumeRunner runner(ec.device);
       for (int w = 0; w < warmup; ++w) runner.run(v, vp, false);
       double ks = 0, ms = 0;
       int sweeps = 0;
       nm03::VolumeMeasure vm = {};
+      size_t lesions = 0;
+      uint64_t lesion0_vox = 0;
       const double t0 = now_s();
       for (int k = 0; k < steps; ++k) {
         auto r = runner.run(v, vp, false);
@@ -174,6 +186,8 @@ int main(int argc, char** argv) {
         ms += r.measure_s;
         sweeps = r.sweeps;
         vm = r.measure;
+        lesions = r.lesions.size();
+        lesion0_vox = lesions ? r.lesions[0].voxels : 0;
       }
       const double dt = now_s() - t0;
       // + the GPU export of every plane (render + JPEG, both images), as the 3D CLI does
@@ -192,6 +206,9 @@ int main(int argc, char** argv) {
       if (measure_volume)
         std::cout << ", \"measure_ms_per_volume\": " << ms * 1e3 / steps << ", \"volume_vox\": " << vm.volume_vox
                   << ", \"components\": " << vm.components << ", \"cavities\": " << vm.cavities;
+      if (measure_volume_lesions)
+        std::cout << ", \"lesions_max\": " << measure_volume_lesions << ", \"lesions\": " << lesions
+                  << ", \"largest_lesion_vox\": " << lesion0_vox;
       std::cout << "}" << std::endl;
     } else if (config == "volume-cpu") {
       if (pids.empty()) throw std::runtime_error("no patients");

@@ -1,11 +1,13 @@
-// Golden model of the volume measurements (nm03/measure.h VolumeMeasure), the sidecar text, and the
-// host run of the K8 kernels' word arithmetic.
+// Golden model of the volume measurements (nm03/measure.h VolumeMeasure, VolumeLesion), the sidecar
+// text, and the host run of the K8 and K10 kernels' word arithmetic.
 //
 // golden::measure_volume is plain per-voxel code that shares nothing with the kernels' algorithm:
 // components by stack flood fill, cavities by labelling the COMPLEMENT of the 1-voxel-padded mask at
 // the dual connectivity, the Euler number by per-voxel loops over the padded array. It is the oracle
 // of every GPU comparison. measure::volume_words is the opposite: the kernels' own per-word functions
 // (nm03/volume_measure_core.h) over a plain host array, one word after the other.
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <stdexcept>
 #include <vector>
@@ -140,6 +142,78 @@ std::string measure_volume_json(const VolumeMeasure& m, const VolumeInput& v, bo
                                  v.spacing_z_source, v.slope, v.intercept, apply_rescale, connectivity);
 }
 
+std::vector<VolumeLesion> measure_volume_lesions(const std::vector<uint8_t>& dilated, const VolumeInput& v,
+                                                 int connectivity, int max_lesions) {
+  if (connectivity != 6 && connectivity != 26)
+    throw std::invalid_argument("measure_volume_lesions: connectivity must be 6 or 26");
+  if (max_lesions < 1 || max_lesions > kMaxVolumeLesions)
+    throw std::invalid_argument("measure_volume_lesions: lesions must be 1.." + std::to_string(kMaxVolumeLesions));
+  const int w = v.w, h = v.h, d = v.d;
+  const size_t n = (size_t)w * h * d;
+  if (w <= 0 || h <= 0 || d <= 0 || dilated.size() != n || v.raw.size() != n)
+    throw std::invalid_argument("measure_volume_lesions: volume and samples must be d × h × w");
+  auto set = [&](int x, int y, int z) {
+    return x >= 0 && y >= 0 && z >= 0 && x < w && y < h && z < d && dilated[((size_t)z * h + y) * w + x] != 0;
+  };
+  std::vector<uint8_t> seen(n, 0);
+  std::vector<size_t> stack;
+  std::vector<VolumeLesion> all;
+  // Raster order of the start voxels = order of the components' first voxels.
+  for (size_t start = 0; start < n; ++start) {
+    if (!dilated[start] || seen[start]) continue;
+    VolumeLesion l{};
+    bool first = true;
+    seen[start] = 1;
+    stack.push_back(start);
+    while (!stack.empty()) {
+      const size_t p = stack.back();
+      stack.pop_back();
+      const int x = (int)(p % (size_t)w), y = (int)(p / (size_t)w % (size_t)h), z = (int)(p / ((size_t)w * h));
+      if (first) l.first[0] = x, l.first[1] = y, l.first[2] = z;  // the start voxel
+      ++l.voxels;
+      l.sum_x += (uint64_t)x;
+      l.sum_y += (uint64_t)y;
+      l.sum_z += (uint64_t)z;
+      const int c[3] = {x, y, z};
+      for (int k = 0; k < 3; ++k) {
+        if (first || c[k] < l.bbox[k]) l.bbox[k] = c[k];
+        if (first || c[k] > l.bbox[3 + k]) l.bbox[3 + k] = c[k];
+      }
+      l.faces_x += (uint64_t)(!set(x - 1, y, z)) + (uint64_t)(!set(x + 1, y, z));
+      l.faces_y += (uint64_t)(!set(x, y - 1, z)) + (uint64_t)(!set(x, y + 1, z));
+      l.faces_z += (uint64_t)(!set(x, y, z - 1)) + (uint64_t)(!set(x, y, z + 1));
+      const int32_t s = stored_sample(v.raw[p], (uint8_t)v.type, (uint8_t)v.stored_bits);
+      l.raw_sum += s;
+      if (first || s < l.raw_min) l.raw_min = s;
+      if (first || s > l.raw_max) l.raw_max = s;
+      first = false;
+      for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy)
+          for (int dx = -1; dx <= 1; ++dx) {
+            const int dist = (dx != 0) + (dy != 0) + (dz != 0);
+            if (dist == 0 || (connectivity == 6 && dist != 1)) continue;
+            if (!set(x + dx, y + dy, z + dz)) continue;
+            const size_t q = ((size_t)(z + dz) * h + (y + dy)) * w + (x + dx);
+            if (seen[q]) continue;
+            seen[q] = 1;
+            stack.push_back(q);
+          }
+    }
+    all.push_back(l);
+  }
+  // `all` is in first-voxel order: a stable sort by size keeps that order among equals.
+  std::stable_sort(all.begin(), all.end(), [](const VolumeLesion& a, const VolumeLesion& b) { return a.voxels > b.voxels; });
+  if (all.size() > (size_t)max_lesions) all.resize((size_t)max_lesions);
+  return all;
+}
+
+std::string measure_volume_json(const VolumeMeasure& m, const std::vector<VolumeLesion>& lesions, int max_lesions,
+                                const VolumeInput& v, bool apply_rescale, int connectivity) {
+  return measure::volume_to_json(m, lesions.data(), (int)lesions.size(), max_lesions, v.w, v.h, v.d, (double)v.spacing_x,
+                                 (double)v.spacing_y, v.spacing_z, v.spacing_z_source, v.slope, v.intercept, apply_rescale,
+                                 connectivity);
+}
+
 }  // namespace golden
 
 namespace measure {
@@ -214,6 +288,65 @@ std::string volume_to_json(const VolumeMeasure& m, int w, int h, int d, double s
   put_d("centroid_z_mm", any, cz * sz);
   put_d("mean", any, mean);
   s += "}\n";
+  return s;
+}
+
+std::string volume_to_json(const VolumeMeasure& m, const VolumeLesion* lesions, int count, int lesions_max, int w, int h,
+                           int d, double sx, double sy, double sz, const std::string& spacing_z_source, float slope,
+                           float intercept, bool apply_rescale, int connectivity) {
+  std::string s = volume_to_json(m, w, h, d, sx, sy, sz, spacing_z_source, slope, intercept, apply_rescale, connectivity);
+  s.resize(s.size() - 2);  // the closing brace and the newline: the lesion keys follow `mean`
+  char buf[256];
+  auto put_u = [&](const char* key, unsigned long long v, bool comma = true) {
+    std::snprintf(buf, sizeof buf, "%s\"%s\":%llu", comma ? "," : "", key, v);
+    s += buf;
+  };
+  auto put_i = [&](const char* key, long long v) {
+    std::snprintf(buf, sizeof buf, ",\"%s\":%lld", key, v);
+    s += buf;
+  };
+  auto put_d = [&](const char* key, double v) {
+    std::snprintf(buf, sizeof buf, ",\"%s\":%.9g", key, v);
+    s += buf;
+  };
+  std::snprintf(buf, sizeof buf, ",\"lesions_max\":%d,\"lesions\":[", lesions_max);
+  s += buf;
+  for (int i = 0; i < count; ++i) {
+    const VolumeLesion& l = lesions[i];
+    s += i ? ",{" : "{";
+    put_u("voxels", l.voxels, false);
+    std::snprintf(buf, sizeof buf, ",\"first\":[%d,%d,%d],\"bbox\":[%d,%d,%d,%d,%d,%d]", l.first[0], l.first[1], l.first[2],
+                  l.bbox[0], l.bbox[1], l.bbox[2], l.bbox[3], l.bbox[4], l.bbox[5]);
+    s += buf;
+    put_u("sum_x", l.sum_x);
+    put_u("sum_y", l.sum_y);
+    put_u("sum_z", l.sum_z);
+    put_u("faces_x", l.faces_x);
+    put_u("faces_y", l.faces_y);
+    put_u("faces_z", l.faces_z);
+    put_i("raw_sum", l.raw_sum);
+    put_i("raw_min", l.raw_min);
+    put_i("raw_max", l.raw_max);
+    // A reported lesion has at least one voxel: no null here.
+    const double n = (double)l.voxels;
+    const double mm3 = n * sx * sy * sz;
+    const double cx = (double)l.sum_x / n, cy = (double)l.sum_y / n, cz = (double)l.sum_z / n;
+    double mean = (double)l.raw_sum / n;
+    if (apply_rescale) mean = mean * (double)slope + (double)intercept;
+    put_d("volume_mm3", mm3);
+    put_d("volume_ml", mm3 / 1000.0);
+    put_d("surface_mm2", (double)l.faces_x * sy * sz + (double)l.faces_y * sx * sz + (double)l.faces_z * sx * sy);
+    put_d("equivalent_diameter_mm", std::cbrt(6.0 * mm3 / 3.14159265358979323846));
+    put_d("centroid_x", cx);
+    put_d("centroid_y", cy);
+    put_d("centroid_z", cz);
+    put_d("centroid_x_mm", cx * sx);
+    put_d("centroid_y_mm", cy * sy);
+    put_d("centroid_z_mm", cz * sz);
+    put_d("mean", mean);
+    s += "}";
+  }
+  s += "]}\n";
   return s;
 }
 
@@ -296,6 +429,88 @@ VolumeMeasure volume_words(const uint64_t* dilated, const uint64_t* region, cons
   r.raw_min = any ? r0 : 0;
   r.raw_max = any ? r1 : 0;
   return r;
+}
+
+int volume_lesions_words(const uint64_t* dilated, const uint16_t* raw, size_t raw_plane_stride, int w, int h, int d, int wpr,
+                         uint8_t type, uint8_t stored_bits, int connectivity, int max_lesions, VolumeLesion* out) {
+  if (connectivity != 6 && connectivity != 26)
+    throw std::invalid_argument("volume_lesions_words: connectivity must be 6 or 26");
+  if (max_lesions < 1 || max_lesions > kMaxVolumeLesions)
+    throw std::invalid_argument("volume_lesions_words: lesions must be 1.." + std::to_string(kMaxVolumeLesions));
+  const size_t slots = volume_measure_scratch_words(w, h, d);
+  if (slots == 0 || wpr != (w + 63) / 64)
+    throw std::invalid_argument("volume_lesions_words: (w + 1) * h * d + 1 must stay below 2^32, wpr = ceil(w / 64)");
+  using namespace vmcore;
+  std::vector<uint32_t> scratch(slots, 0xDEADBEEFu);
+  HostParents par{scratch.data()};
+  const BitVolume M{dilated, w, h, d, wpr, false};
+  auto each_word = [&](auto&& fn) {
+    for (int z = 0; z < d; ++z)
+      for (int y = 0; y < h; ++y)
+        for (int k = 0; k < wpr; ++k) fn(z, y, k);
+  };
+  // K8's mask pass, up to the state K10 reads.
+  each_word([&](int z, int y, int k) { init_runs(M, z, y, k, par); });
+  each_word([&](int z, int y, int k) { unite_word(M, par, z, y, k, connectivity == 26); });
+  each_word([&](int z, int y, int k) { compress_runs(M, par, z, y, k); });
+  each_word([&](int z, int y, int k) {
+    stretch_areas(M, par, z, y, k, [&](uint32_t root, uint32_t len) { par.add(root + 1u, len); });
+  });
+  // candidates + select: every root's key, the max_lesions largest.
+  std::vector<uint64_t> keys;
+  each_word([&](int z, int y, int k) {
+    uint64_t roots = root_bits(M, par, z, y, k);
+    while (roots) {
+      int bit = 0;
+      keys.push_back(best_root_key(M, par, z, y, k, roots, bit));
+      roots &= ~(1ull << bit);
+    }
+  });
+  std::sort(keys.begin(), keys.end(), [](uint64_t a, uint64_t b) { return a > b; });
+  const int count = (int)std::min<size_t>(keys.size(), (size_t)max_lesions);
+  std::vector<uint32_t> srt_slot((size_t)count);
+  for (int i = 0; i < count; ++i) srt_slot[(size_t)i] = lesion_key_slot(keys[(size_t)i]);
+  std::sort(srt_slot.begin(), srt_slot.end());
+  std::vector<int> srt_rank((size_t)count);
+  for (int i = 0; i < count; ++i)
+    srt_rank[(size_t)find_slot(srt_slot.data(), count, lesion_key_slot(keys[(size_t)i]))] = i;
+  // accumulate
+  std::vector<LesionFigures> fig((size_t)count);
+  std::vector<int64_t> rsum((size_t)count, 0);
+  std::vector<int32_t> rmin((size_t)count, 0x7FFFFFFF), rmax((size_t)count, (int32_t)0x80000000);
+  each_word([&](int z, int y, int k) {
+    const uint64_t m = M.at(z, y, k);
+    if (m == 0ull) return;
+    const WordFaces wf = word_faces(M, z, y, k, m);
+    lesion_stretches(M, par, z, y, k, m, [&](uint32_t root, uint64_t bits) {
+      const int idx = find_slot(srt_slot.data(), count, root);
+      if (idx < 0) return;
+      const size_t r = (size_t)srt_rank[(size_t)idx];
+      lesion_bits_figures(z, y, k, wf, bits, fig[r]);
+      for (uint64_t t = bits; t; t &= t - 1) {
+        const int x = (k << 6) + ctz64(t);
+        const int32_t v = stored_sample(raw[(size_t)z * raw_plane_stride + (size_t)y * w + x], type, stored_bits);
+        rsum[r] += v;
+        rmin[r] = v < rmin[r] ? v : rmin[r];
+        rmax[r] = v > rmax[r] ? v : rmax[r];
+      }
+    });
+  });
+  // final
+  for (int i = 0; i < count; ++i) {
+    const LesionFigures& f = fig[(size_t)i];
+    VolumeLesion r{};
+    r.voxels = f.vox;
+    slot_voxel(M, lesion_key_slot(keys[(size_t)i]), r.first);
+    r.bbox[0] = f.x0, r.bbox[1] = f.y0, r.bbox[2] = f.z0, r.bbox[3] = f.x1, r.bbox[4] = f.y1, r.bbox[5] = f.z1;
+    r.sum_x = f.sum_x, r.sum_y = f.sum_y, r.sum_z = f.sum_z;
+    r.faces_x = f.faces_x, r.faces_y = f.faces_y, r.faces_z = f.faces_z;
+    r.raw_sum = rsum[(size_t)i];
+    r.raw_min = rmin[(size_t)i];
+    r.raw_max = rmax[(size_t)i];
+    out[i] = r;
+  }
+  return count;
 }
 
 }  // namespace measure

@@ -23,6 +23,8 @@
 //            lengths that share a root are summed in the wave first, so one large body costs one
 //            atomic per wave, not one per stretch
 //   D        roots are counted and their areas maximised
+//   (lesions  optional, --measure-volume-lesions: K10's launches (k10_volume_lesions.hip) go here, between the
+//            mask pass's root count and the complement pass, which overwrites the labelling they read)
 //   cavities the scratch is reused for the COMPLEMENT inside the frame (~word & row_word_mask) at the
 //            dual connectivity: init runs, B, runs pointed at their roots, then every stretch on a
 //            frame face marks its root (second slot = 1; one store per root and wave) and the
@@ -52,15 +54,11 @@
 #include "nm03/kernels.h"
 #include "nm03/measure.h"
 #include "nm03/volume_measure_core.h"
+#include "volume_measure_util.h"
 
 namespace nm03::gpu {
 
-constexpr int kVmThreads = 256;
-constexpr int kVmWaves = kVmThreads / 64;
-
 namespace {
-
-using vmcore::BitVolume;
 
 // Accumulator record (kVolumeMeasureAccWords u64): sums in u64 words, then the extrema as i32.
 enum : int {
@@ -70,62 +68,8 @@ enum : int {
 };
 static_assert(kAccNumSums <= kAccExtrema && kAccExtrema + 4 <= kVolumeMeasureAccWords, "accumulator layout");
 
-// Parents, areas and marks: relaxed agent-scope atomics (see the header comment).
-struct DeviceParents {
-  uint32_t* p;
-  __device__ __forceinline__ uint32_t ld(uint32_t i) const {
-    return __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __device__ __forceinline__ void st(uint32_t i, uint32_t v) const {
-    __hip_atomic_store(p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __device__ __forceinline__ uint32_t fetch_min(uint32_t i, uint32_t v) const {
-    return __hip_atomic_fetch_min(p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __device__ __forceinline__ void add(uint32_t i, uint32_t v) const {
-    (void)__hip_atomic_fetch_add(p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-};
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
-    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
-    v += ((uint64_t)hi << 32) | lo;
-  }
-  return v;
-}
-__device__ __forceinline__ int32_t wave_min_i32(int32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int32_t wave_max_i32(int32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 __device__ __forceinline__ void acc_add(uint64_t* acc, int i, uint64_t v) {
   if (v) (void)__hip_atomic_fetch_add(acc + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The thread's word: (z, y, k) of word i < total.
-struct WordIndex {
-  int z, y, k;
-  bool valid;
-};
-__device__ __forceinline__ WordIndex my_word(const BitVolume& V) {
-  const uint32_t total = (uint32_t)V.d * (uint32_t)V.h * (uint32_t)V.n;  // < 2^32 (launch_volume_measure)
-  const uint32_t i = blockIdx.x * (uint32_t)kVmThreads + threadIdx.x;
-  WordIndex w;
-  w.valid = i < total;
-  const uint32_t row = i / (uint32_t)V.n;
-  w.k = (int)(i - row * (uint32_t)V.n);
-  w.z = (int)(row / (uint32_t)V.h);
-  w.y = (int)(row - (uint32_t)w.z * (uint32_t)V.h);
-  return w;
 }
 
 }  // namespace
@@ -348,7 +292,7 @@ __global__ void vm_final_kernel(const uint64_t* __restrict__ acc, int connectivi
 
 void launch_volume_measure(const uint64_t* dilated, const uint64_t* region, const uint16_t* raw, size_t raw_plane_stride,
                            int w, int h, int d, uint8_t type, uint8_t stored_bits, int connectivity, uint32_t* scratch,
-                           uint64_t* acc, VolumeMeasure* out, hipStream_t stream) {
+                           uint64_t* acc, VolumeMeasure* out, hipStream_t stream, const VolumeLesionWork* lesions) {
   if (connectivity != 6 && connectivity != 26) throw DeviceError("launch_volume_measure: connectivity must be 6 or 26");
   if (w <= 0 || h <= 0 || d <= 0) throw DeviceError("launch_volume_measure: empty volume");
   if (stored_bits < 1 || stored_bits > 16) throw DeviceError("launch_volume_measure: stored bits must be 1..16");
@@ -377,6 +321,10 @@ void launch_volume_measure(const uint64_t* dilated, const uint64_t* region, cons
   check_launch("vm_areas_kernel");
   vm_roots_kernel<<<grid, kVmThreads, 0, stream>>>(M, scratch, acc);
   check_launch("vm_roots_kernel");
+  // The per-lesion phase (K10) reads the mask pass's labelling — every run at its root, the area in the
+  // slot after a root — before the complement pass overwrites the scratch.
+  if (lesions)
+    launch_volume_lesions(dilated, raw, raw_plane_stride, w, h, d, type, stored_bits, scratch, *lesions, stream);
   // Cavities: the complement at the dual connectivity, on the same scratch.
   vm_init_runs_kernel<<<grid, kVmThreads, 0, stream>>>(C, scratch);
   check_launch("vm_init_runs_kernel");

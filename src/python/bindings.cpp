@@ -322,6 +322,57 @@ VolumeMeasure volume_measure_from(const py::dict& d) {
   return m;
 }
 
+// The integers of a lesion record (nm03/measure.h VolumeLesion) as a dict.
+py::dict volume_lesion_dict(const VolumeLesion& l) {
+  py::dict d;
+  d["voxels"] = l.voxels;
+  py::list fi, bb;
+  for (int k = 0; k < 3; ++k) fi.append(l.first[k]);
+  for (int k = 0; k < 6; ++k) bb.append(l.bbox[k]);
+  d["first"] = fi;
+  d["bbox"] = bb;
+  d["sum_x"] = l.sum_x;
+  d["sum_y"] = l.sum_y;
+  d["sum_z"] = l.sum_z;
+  d["faces_x"] = l.faces_x;
+  d["faces_y"] = l.faces_y;
+  d["faces_z"] = l.faces_z;
+  d["raw_sum"] = l.raw_sum;
+  d["raw_min"] = l.raw_min;
+  d["raw_max"] = l.raw_max;
+  return d;
+}
+
+py::list volume_lesion_list(const VolumeLesion* l, size_t n) {
+  py::list out;
+  for (size_t i = 0; i < n; ++i) out.append(volume_lesion_dict(l[i]));
+  return out;
+}
+
+VolumeLesion volume_lesion_from(const py::dict& d) {
+  VolumeLesion l{};
+  l.voxels = d["voxels"].cast<uint64_t>();
+  const std::vector<int> fi = d["first"].cast<std::vector<int>>(), bb = d["bbox"].cast<std::vector<int>>();
+  if (fi.size() != 3 || bb.size() != 6) throw std::invalid_argument("first must have three values, bbox six");
+  for (int k = 0; k < 3; ++k) l.first[k] = fi[(size_t)k];
+  for (int k = 0; k < 6; ++k) l.bbox[k] = bb[(size_t)k];
+  l.sum_x = d["sum_x"].cast<uint64_t>();
+  l.sum_y = d["sum_y"].cast<uint64_t>();
+  l.sum_z = d["sum_z"].cast<uint64_t>();
+  l.faces_x = d["faces_x"].cast<uint64_t>();
+  l.faces_y = d["faces_y"].cast<uint64_t>();
+  l.faces_z = d["faces_z"].cast<uint64_t>();
+  l.raw_sum = d["raw_sum"].cast<int64_t>();
+  l.raw_min = d["raw_min"].cast<int32_t>();
+  l.raw_max = d["raw_max"].cast<int32_t>();
+  return l;
+}
+
+void check_max_lesions(int n) {
+  if (n < 1 || n > kMaxVolumeLesions)
+    throw std::invalid_argument("max_lesions must be 1.." + std::to_string(kMaxVolumeLesions));
+}
+
 // [D, H, W] 0/1 bytes → bit volume (d planes of h rows of ceil(w / 64) words, LSB = left-most voxel).
 std::vector<uint64_t> pack_volume(const py::array_t<uint8_t, py::array::c_style | py::array::forcecast>& a) {
   const int d = (int)a.shape(0), h = (int)a.shape(1), w = (int)a.shape(2), wpr = (w + 63) / 64;
@@ -343,6 +394,7 @@ struct VolumeMeta {
   std::string spacing_z_source = "default";
   bool measure = false;
   int measure_connectivity = 26;
+  int measure_lesions = 0;
 };
 
 void apply_meta(const VolumeMeta& mt, VolumeInput& v) {
@@ -380,6 +432,7 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
     apply_meta(*meta, v);
     vp.measure = meta->measure;
     vp.measure_connectivity = meta->measure_connectivity;
+    vp.measure_lesions = meta->measure_lesions;
   }
   VolumeResult r;
   {
@@ -395,6 +448,11 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
   if (vp.measure) {
     d["measure"] = volume_measure_dict(r.measure);
     d["measure_json"] = golden::measure_volume_json(r.measure, v, vp.pipe.apply_rescale, vp.measure_connectivity);
+    if (vp.measure_lesions) {
+      d["lesions"] = volume_lesion_list(r.lesions.data(), r.lesions.size());
+      d["measure_json"] = golden::measure_volume_json(r.measure, r.lesions, vp.measure_lesions, v, vp.pipe.apply_rescale,
+                                                      vp.measure_connectivity);
+    }
     d["measure_s"] = r.measure_s;
   }
   return d;
@@ -1008,14 +1066,61 @@ PYBIND11_MODULE(_nm03, m) {
   m.def(
       "volume_measure_to_json",
       [](const py::dict& rec, int w, int h, int d, double sx, double sy, double sz, const std::string& source, float slope,
-         float intercept, bool apply_rescale, int connectivity) {
+         float intercept, bool apply_rescale, int connectivity, const py::object& lesions, int lesions_max) {
         // Pixel spacings pass through float, as VolumeInput holds them.
-        return measure::volume_to_json(volume_measure_from(rec), w, h, d, (double)(float)sx, (double)(float)sy, sz, source,
-                                       slope, intercept, apply_rescale, connectivity);
+        if (lesions.is_none())
+          return measure::volume_to_json(volume_measure_from(rec), w, h, d, (double)(float)sx, (double)(float)sy, sz, source,
+                                         slope, intercept, apply_rescale, connectivity);
+        // With `lesions` (a list of lesion dicts, as many as are reported): the text with the lesion keys.
+        std::vector<VolumeLesion> ls;
+        for (const py::handle& l : lesions.cast<py::list>()) ls.push_back(volume_lesion_from(l.cast<py::dict>()));
+        check_max_lesions(lesions_max);
+        if (ls.size() > (size_t)lesions_max) throw std::invalid_argument("more lesions than lesions_max");
+        return measure::volume_to_json(volume_measure_from(rec), ls.data(), (int)ls.size(), lesions_max, w, h, d,
+                                       (double)(float)sx, (double)(float)sy, sz, source, slope, intercept, apply_rescale,
+                                       connectivity);
       },
       py::arg("record"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_x") = 1.0, py::arg("spacing_y") = 1.0,
       py::arg("spacing_z") = 1.0, py::arg("spacing_z_source") = "default", py::arg("slope") = 1.f,
-      py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 26);
+      py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 26,
+      py::arg("lesions") = py::none(), py::arg("lesions_max") = 0);
+  // The N largest components of a volume mask (nm03/measure.h VolumeLesion) by the golden model (flood
+  // fill per component) → list of dicts of the records' integers, largest first.
+  m.def(
+      "golden_measure_volume_lesions",
+      [volume_arrays](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+                      py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, int max_lesions,
+                      const std::string& type, int stored_bits, int connectivity) {
+        check_max_lesions(max_lesions);
+        const VolumeInput v = volume_arrays(dil, dil, raw, type, stored_bits);
+        const std::vector<uint8_t> dv = from_np<uint8_t>(dil);
+        std::vector<VolumeLesion> r;
+        {
+          py::gil_scoped_release nogil;
+          r = golden::measure_volume_lesions(dv, v, connectivity, max_lesions);
+        }
+        return volume_lesion_list(r.data(), r.size());
+      },
+      py::arg("dilated"), py::arg("raw"), py::arg("max_lesions"), py::arg("type") = "u16", py::arg("stored_bits") = 16,
+      py::arg("connectivity") = 26);
+  // The same records from the K10 kernels' per-word lesion logic on K8's run union-find, run on the host
+  // one word after the other (measure::volume_lesions_words).
+  m.def(
+      "volume_lesions_words",
+      [volume_arrays](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+                      py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, int max_lesions,
+                      const std::string& type, int stored_bits, int connectivity) {
+        check_max_lesions(max_lesions);
+        const VolumeInput v = volume_arrays(dil, dil, raw, type, stored_bits);
+        const std::vector<uint64_t> dw = pack_volume(dil);
+        std::vector<VolumeLesion> r((size_t)max_lesions);
+        const int n = measure::volume_lesions_words(dw.data(), v.raw.data(), (size_t)v.w * v.h, v.w, v.h, v.d, (v.w + 63) / 64,
+                                                    (uint8_t)v.type, (uint8_t)v.stored_bits, connectivity, max_lesions, r.data());
+        return volume_lesion_list(r.data(), (size_t)n);
+      },
+      py::arg("dilated"), py::arg("raw"), py::arg("max_lesions"), py::arg("type") = "u16", py::arg("stored_bits") = 16,
+      py::arg("connectivity") = 26);
+  m.attr("MAX_VOLUME_LESIONS") = kMaxVolumeLesions;
 
   // ---- JPEG --------------------------------------------------------------------------------------
   m.def("jpeg_encode_gray420", [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> g, int quality) {
@@ -1240,8 +1345,9 @@ PYBIND11_MODULE(_nm03, m) {
              const PipelineParams& p, int connectivity, int dilation,
              const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_connectivity,
              const std::vector<double>& spacing, const std::string& spacing_z_source, const std::string& type,
-             int stored_bits, float slope, float intercept) {
+             int stored_bits, float slope, float intercept, int measure_lesions) {
             VolumeMeta mt;
+            mt.measure_lesions = measure_lesions;
             mt.type = type;
             mt.stored_bits = stored_bits;
             mt.slope = slope;
@@ -1257,7 +1363,8 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("dilation") = 7, py::arg("seeds") = std::vector<std::tuple<int, int, int>>{},
           py::arg("measure") = false, py::arg("measure_connectivity") = 26,
           py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0}, py::arg("spacing_z_source") = "default",
-          py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f, py::arg("intercept") = 0.f)
+          py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f, py::arg("intercept") = 0.f,
+          py::arg("measure_lesions") = 0)
       .def(
           "run_slab",
           // One rank's z-slab (planes [z0, z0 + slab depth) of a `depth`-deep volume) through the
@@ -1265,10 +1372,11 @@ PYBIND11_MODULE(_nm03, m) {
           // coordinates. Returns the slab's masks plus rounds / exchanged bytes.
           [](VolumeRunner& self, Comm& comm, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> slab,
              int z0, int depth, const PipelineParams& p, int connectivity, int dilation,
-             const std::vector<std::tuple<int, int, int>>& seeds, bool measure) {
+             const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_lesions) {
             SlabStats st;
             VolumeMeta mt;
             mt.measure = measure;  // refused by run_slab (std::invalid_argument) before anything is launched
+            mt.measure_lesions = measure_lesions;  // alike
             py::dict d = volume_call(slab, p, connectivity, dilation, seeds,
                                      [&](const VolumeInput& v, const VolumeParams& vp) {
                                        return self.run_slab(comm, v, z0, depth, vp, true, &st);
@@ -1279,7 +1387,8 @@ PYBIND11_MODULE(_nm03, m) {
           },
           py::arg("comm"), py::arg("slab"), py::arg("z0"), py::arg("depth"), py::arg("params") = PipelineParams(),
           py::arg("connectivity") = 6, py::arg("dilation") = 7,
-          py::arg("seeds") = std::vector<std::tuple<int, int, int>>{}, py::arg("measure") = false);
+          py::arg("seeds") = std::vector<std::tuple<int, int, int>>{}, py::arg("measure") = false,
+          py::arg("measure_lesions") = 0);
 
   // One-process rehearsal of the z-slab decomposition: `nranks` threads, each with its own
   // VolumeRunner (stream) on `device`, talking over loopback comms — the device-resident exchange
@@ -1896,6 +2005,56 @@ PYBIND11_MODULE(_nm03, m) {
     gpu::check_hip(hipStreamSynchronize(st), "k_measure_volume");
     return volume_measure_dict(res);
   }, py::arg("dilated"), py::arg("region"), py::arg("raw"), py::arg("w"), py::arg("h"), py::arg("d"),
+     py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("connectivity") = 26, py::arg("stream") = 0);
+
+  // K8 with the K10 launches between its two passes: the record dict and the list of the lesion dicts
+  // (the `max_lesions` largest components, largest first). Same arguments as k_measure_volume.
+  m.def("k_measure_volume_lesions", [](uintptr_t dilated, uintptr_t region, uintptr_t raw, int w, int h, int d,
+                                       int max_lesions, const std::string& type, int stored_bits, int connectivity,
+                                       uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    if (connectivity != 6 && connectivity != 26) throw std::invalid_argument("connectivity must be 6 or 26");
+    if (stored_bits < 1 || stored_bits > 16) throw std::invalid_argument("stored_bits must be 1..16");
+    if (w <= 0 || h <= 0 || d <= 0) throw std::invalid_argument("empty volume");
+    check_max_lesions(max_lesions);
+    const size_t slots = gpu::volume_measure_scratch_words(w, h, d);
+    if (slots == 0) throw std::invalid_argument("volume too large to measure: (w + 1) * h * d + 1 must stay below 2^32");
+    const PixelType pt = parse_type(type);
+    {
+      // K8's and K10's code objects, loaded on the current device before this op's first launch there.
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_volume_measure();
+        gpu::preload_volume_lesions();
+        preloaded.push_back(dev);
+      }
+    }
+    const size_t n_out = sizeof(VolumeLesion) * (size_t)(kMaxVolumeLesions + 1);  // records, then the count
+    const size_t work = (gpu::volume_lesions_work_bytes(w, h, d, max_lesions) + 255) / 256 * 256;
+    const size_t o_acc = 0, o_out = 256, o_les = 512, o_work = o_les + n_out, o_par = o_work + work,
+                 total = o_par + slots * sizeof(uint32_t);
+    uint8_t* dev = (uint8_t*)scratch().get(total);
+    gpu::VolumeLesionWork lw;
+    lw.max_lesions = max_lesions;
+    lw.work = dev + o_work;
+    lw.out = (VolumeLesion*)(dev + o_les);
+    lw.out_count = (uint32_t*)(dev + o_les + sizeof(VolumeLesion) * kMaxVolumeLesions);
+    gpu::launch_volume_measure((const uint64_t*)dilated, (const uint64_t*)region, (const uint16_t*)raw, (size_t)w * h, w, h,
+                               d, (uint8_t)(pt == kU8 ? kU16 : pt), (uint8_t)stored_bits, connectivity,
+                               (uint32_t*)(dev + o_par), (uint64_t*)(dev + o_acc), (VolumeMeasure*)(dev + o_out), st, &lw);
+    VolumeMeasure res;
+    std::vector<VolumeLesion> les((size_t)kMaxVolumeLesions + 1);
+    gpu::check_hip(hipMemcpyAsync(&res, dev + o_out, sizeof(VolumeMeasure), hipMemcpyDeviceToHost, st), "D2H record");
+    gpu::check_hip(hipMemcpyAsync(les.data(), dev + o_les, n_out, hipMemcpyDeviceToHost, st), "D2H lesions");
+    gpu::check_hip(hipStreamSynchronize(st), "k_measure_volume_lesions");
+    const uint32_t count = *reinterpret_cast<const uint32_t*>(&les[(size_t)kMaxVolumeLesions]);
+    if (count > (uint32_t)max_lesions) throw std::runtime_error("k_measure_volume_lesions: count out of range");
+    return py::make_tuple(volume_measure_dict(res), volume_lesion_list(les.data(), count));
+  }, py::arg("dilated"), py::arg("region"), py::arg("raw"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("max_lesions"),
      py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("connectivity") = 26, py::arg("stream") = 0);
 
   // ---- comm self-tests (CPU) ------------------------------------------------------------------------

@@ -160,6 +160,10 @@ struct VolumeDevice {
   // allocated by the first measuring run and kept.
   std::unique_ptr<DevBuf> vm_scratch, vm_acc;
   VolumeMeasure* h_measure = nullptr;
+  // K10 (VolumeParams::measure_lesions): candidate list, accumulators and the pinned records and count,
+  // allocated by the first run that asks for lesions (for kMaxVolumeLesions, so any N fits) and kept.
+  std::unique_ptr<DevBuf> vl_work;
+  VolumeLesion* h_lesions = nullptr;  // kMaxVolumeLesions records, then the count
   VolumeDevice(const VolumeInput& v)
       : w(v.w), h(v.h), d(v.d), wpr((v.w + 63) / 64), words((size_t)v.h * ((v.w + 63) / 64)),
         ps(((size_t)v.w * v.h + 7) / 8 * 8),
@@ -180,6 +184,7 @@ struct VolumeDevice {
     return sizeof(SliceDesc) * d + sizeof(TileDesc) * (n_medt + n_shpt) + sizeof(SliceStats) * d;
   }
   ~VolumeDevice() {
+    if (h_lesions) (void)hipHostFree(h_lesions);
     if (h_measure) (void)hipHostFree(h_measure);
     if (h_tables) (void)hipHostFree(h_tables);
     if (h_flag) (void)hipHostFree(h_flag);
@@ -333,6 +338,7 @@ struct VolumeRunner::Impl {
   std::unique_ptr<ExportBufs> X;
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   bool measure_loaded = false;  // K8's code object (first measuring run)
+  bool lesions_loaded = false;  // K10's code object (first run that asks for lesions)
   explicit Impl(int dev) : device(dev) {
     check_hip(hipSetDevice(device), "hipSetDevice");
     preload_kernels();  // every code object, before the first launch (kernels.h)
@@ -364,6 +370,11 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
     I.V = std::make_unique<VolumeDevice>(v);
   }
   VolumeDevice& V = *I.V;
+  if (p.measure_lesions != 0 && !p.measure)
+    throw std::invalid_argument("3D lesion measurements need measure");
+  if (p.measure_lesions < 0 || p.measure_lesions > kMaxVolumeLesions)
+    throw std::invalid_argument("3D lesion count must be in [1, " + std::to_string(kMaxVolumeLesions) + "] (got " +
+                                std::to_string(p.measure_lesions) + ")");
   if (p.measure) {
     if (p.measure_connectivity != 6 && p.measure_connectivity != 26)
       throw std::invalid_argument("3D measurement connectivity must be 6 or 26 (got " +
@@ -383,6 +394,17 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
       V.vm_acc = std::make_unique<DevBuf>(kVolumeMeasureAccWords * sizeof(uint64_t));
       check_hip(hipHostMalloc((void**)&V.h_measure, sizeof(VolumeMeasure), hipHostMallocDefault), "hipHostMalloc measure");
     }
+    if (p.measure_lesions) {  // K10 alike
+      if (!I.lesions_loaded) {
+        preload_volume_lesions();
+        I.lesions_loaded = true;
+      }
+      if (!V.vl_work) {
+        V.vl_work = std::make_unique<DevBuf>(volume_lesions_work_bytes(v.w, v.h, v.d, kMaxVolumeLesions));
+        check_hip(hipHostMalloc((void**)&V.h_lesions, sizeof(VolumeLesion) * (kMaxVolumeLesions + 1), hipHostMallocDefault),
+                  "hipHostMalloc lesions");
+      }
+    }
   }
   const PipeConsts pc = make_consts(p.pipe, 2);
   check_hip(hipEventRecord(I.e0, V.stream), "event");
@@ -394,12 +416,24 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
   volume_segment(V, v, p);
   check_hip(hipEventRecord(I.e1, V.stream), "event");
   if (p.measure) {  // timed outside the e0–e1 pair: kernels_s stays what it is
+    VolumeLesionWork lw;
+    if (p.measure_lesions) {
+      lw.max_lesions = p.measure_lesions;
+      lw.work = V.vl_work->p;
+      lw.out = V.h_lesions;
+      lw.out_count = reinterpret_cast<uint32_t*>(V.h_lesions + kMaxVolumeLesions);
+    }
     launch_volume_measure(V.dil.as<uint64_t>(), V.region.as<uint64_t>(), V.raw.as<uint16_t>(), V.ps, v.w, v.h, v.d,
                           (uint8_t)v.type, (uint8_t)v.stored_bits, p.measure_connectivity, V.vm_scratch->as<uint32_t>(),
-                          V.vm_acc->as<uint64_t>(), V.h_measure, V.stream);
+                          V.vm_acc->as<uint64_t>(), V.h_measure, V.stream, p.measure_lesions ? &lw : nullptr);
     check_hip(hipEventRecord(I.e2, V.stream), "event");
     check_hip(hipEventSynchronize(I.e2), "sync");
     r.measure = *V.h_measure;
+    if (p.measure_lesions) {
+      const uint32_t count = *lw.out_count;
+      if (count > (uint32_t)p.measure_lesions) throw DeviceError("volume lesions: count out of range");
+      r.lesions.assign(V.h_lesions, V.h_lesions + count);
+    }
     float mms = 0;
     (void)hipEventElapsedTime(&mms, I.e1, I.e2);
     r.measure_s = mms * 1e-3;
@@ -548,7 +582,7 @@ static SlabStats slab_grow_dilate_gpu(Comm& comm, VolumeDevice& V, int nseeds, i
 VolumeResult VolumeRunner::run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p,
                                     bool want_masks, SlabStats* stats) {
   if (slab.d < 1 || slab.w < 1 || slab.h < 1) throw SliceError("empty slab");
-  if (p.measure)
+  if (p.measure || p.measure_lesions)
     throw std::invalid_argument("run_slab: measuring a volume split into slabs is not supported "
                                 "(components that cross slabs need a collective)");
   check_volume_params(p.connectivity, p.dilation_size);
@@ -835,9 +869,11 @@ std::vector<std::vector<uint8_t>> golden_export(const VolumeInput& v, const std:
   return files;
 }
 
-// `measured` (optional): the record of the dilated volume by the golden model (--measure-volume).
+// `measured` (optional): the record of the dilated volume by the golden model (--measure-volume), and
+// with vp.measure_lesions the lesion records in `lesions`.
 std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, const VolumeParams& vp,
-                                                      const RenderParams& rp, VolumeMeasure* measured = nullptr) {
+                                                      const RenderParams& rp, VolumeMeasure* measured = nullptr,
+                                                      std::vector<VolumeLesion>* lesions = nullptr) {
   const GoldenPlanes gp = golden_preprocess(v, vp);
   std::vector<Seed> seeds = vp.seeds;
   if (seeds.empty()) {
@@ -847,6 +883,8 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
   const auto region = golden::region_grow3d(gp.band, v.w, v.h, v.d, seeds, vp.connectivity);
   const auto dil = golden::dilate3d(region, v.w, v.h, v.d, vp.dilation_size, vp.pipe.se_shape == kSeDisc);
   if (measured) *measured = golden::measure_volume(dil, region, v, vp.measure_connectivity);
+  if (measured && lesions && vp.measure_lesions)
+    *lesions = golden::measure_volume_lesions(dil, v, vp.measure_connectivity, vp.measure_lesions);
   return golden_export(v, gp.vals, dil, rp);
 }
 
@@ -873,6 +911,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
   vp.dilation_size = cfg.dilation_set ? cfg.engine.pipe.dilation_size : 7;
   vp.measure = cfg.measure_volume;
   vp.measure_connectivity = cfg.measure_volume_connectivity;
+  vp.measure_lesions = cfg.measure_volume_lesions;
   const RenderParams& rp = cfg.engine.render;
   const double t_start = wall_now();
   // ---- plan on rank 0 -----------------------------------------------------------------------
@@ -1005,14 +1044,16 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       o.slices = v.d;
       std::vector<std::vector<uint8_t>> files;
       VolumeMeasure measured = {};
+      std::vector<VolumeLesion> lesions;
       if (cfg.cpu) {
-        files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr);
+        files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions);
       } else {
         VolumeResult r = runner->run(v, vp, false);
         o.sweeps = r.sweeps;
         o.gpu_s = r.kernels_s;
         o.measure_s = r.measure_s;
         measured = r.measure;
+        lesions = std::move(r.lesions);
         VolumeExportStats xs;
         files = runner->export_jpegs(v, vp, rp, &xs);
         o.export_s = xs.export_s;
@@ -1020,7 +1061,10 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       }
       write_planes(pp, 0, v.d, files);
       if (vp.measure) {  // the sidecar next to the planes; its text travels to rank 0 for the table
-        o.measure_json = golden::measure_volume_json(measured, v, vp.pipe.apply_rescale, vp.measure_connectivity);
+        o.measure_json = vp.measure_lesions
+                             ? golden::measure_volume_json(measured, lesions, vp.measure_lesions, v, vp.pipe.apply_rescale,
+                                                           vp.measure_connectivity)
+                             : golden::measure_volume_json(measured, v, vp.pipe.apply_rescale, vp.measure_connectivity);
         const std::string path = pp.out_dir + "/" + measure::volume_sidecar_name();
         std::ofstream f(path, std::ios::binary | std::ios::trunc);
         f.write(o.measure_json.data(), (std::streamsize)o.measure_json.size());
@@ -1147,6 +1191,13 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       volume_totals = write_volumes_csv(cfg.out_dir, rows);
     } catch (const std::exception& e) {
       std::cerr << "Error writing volumes.csv: " << e.what() << std::endl;
+    }
+    if (cfg.measure_volume_lesions) {
+      try {
+        volume_totals.lesions = write_lesions_csv(cfg.out_dir, rows);
+      } catch (const std::exception& e) {
+        std::cerr << "Error writing lesions.csv: " << e.what() << std::endl;
+      }
     }
   }
   if (!cfg.json.empty()) {
