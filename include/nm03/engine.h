@@ -63,7 +63,10 @@ struct EngineConfig {
   // CPUs the pool, slot threads and pinned allocations are bound to (a rank's partition of its
   // GPU's NUMA node, numa::rank_partition). Empty: the whole node of the GPU (multi-node hosts).
   std::vector<int> cpus;
-  int max_dim = 512;    // buffers sized for slices up to max_dim × max_dim
+  // Buffers sized for slices up to max_dim × max_dim (≤ 4096). The descriptors address them with 32-bit
+  // offsets: batch_size × max_dim² samples and 2 · batch_size canvases (bytes) must stay below 2³², or
+  // the constructor throws.
+  int max_dim = 512;
   PipelineParams pipe;
   RenderParams render;
   bool export_jpeg = true;

@@ -375,6 +375,7 @@ struct Engine::Impl {
                                     (jpeg::Sampling)cfg.render.jpeg_sampling);
     if (cfg.render.out_width % 16 || cfg.render.out_height % 16)
       throw DeviceError("canvas size must be a multiple of 16");
+    check_offsets_fit();  // before any allocation
     if (host_only_) make_templates();
     const double t0 = now_s();
     if (!host_only_) {
@@ -581,6 +582,27 @@ struct Engine::Impl {
     check_hip(hipHostMalloc((void**)&pin_arena_, pin_stride_ * n, hipHostMallocDefault), "hipHostMalloc blob arena");
     check_hip(hipHostMalloc((void**)&map_arena_, map_stride_ * n, hipHostMallocMapped), "hipHostMalloc out arena");
     check_hip(hipHostGetDevicePointer((void**)&map_arena_dev_, map_arena_, 0), "hipHostGetDevicePointer out arena");
+  }
+
+  // The descriptors address a slot's buffers with 32-bit offsets: SliceDesc::raw_off / f32_off and
+  // RenderDesc::src_off count samples of the batch_size × max_dim² sample buffers, RenderDesc /
+  // JpegDesc::canvas_off bytes of the canvases (two per slice, five for a test run; the overlay's are
+  // three bytes per pixel, one per slice). A configuration whose buffers reach 2³² is refused here.
+  void check_offsets_fit() const {
+    constexpr uint64_t kLimit = uint64_t(1) << 32;
+    const uint64_t B = (uint64_t)cfg.batch_size, md = (uint64_t)cfg.max_dim;
+    const uint64_t samples = B * align_up((size_t)(md * md), 8);
+    if (samples >= kLimit)
+      throw DeviceError("batch_size " + std::to_string(B) + " x max_dim " + std::to_string(md) + ": " + std::to_string(samples) +
+                        " samples per batch exceed the engine's 32-bit offsets (fewer than 4294967296); lower one of them");
+    const uint64_t cw = (uint64_t)std::max(cfg.render.out_width, 0), ch = (uint64_t)std::max(cfg.render.out_height, 0);
+    const uint64_t canvases = std::max<uint64_t>(2 * B, 5);
+    if (cw * ch >= kLimit || canvases * (cw * ch) >= kLimit)
+      throw DeviceError(std::to_string(canvases) + " canvases of " + std::to_string(cw) + " x " + std::to_string(ch) +
+                        " bytes (batch_size " + std::to_string(B) + ") exceed the engine's 32-bit offsets; lower the batch size");
+    if (overlay_ && 3 * B * (cw * ch) >= kLimit)
+      throw DeviceError(std::to_string(B) + " overlay canvases of " + std::to_string(cw) + " x " + std::to_string(ch) +
+                        " x 3 bytes exceed the engine's 32-bit offsets; lower the batch size");
   }
 
   // Capacities and blob layout of a slot (no allocation).
