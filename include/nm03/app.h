@@ -95,6 +95,10 @@ struct AppConfig {
   // --measure-volume-lesions N (implies --measure-volume): the sidecar also lists the N largest
   // lesions (nm03/measure.h VolumeLesion) and rank 0 writes <out>/lesions.csv; 0 = off, else 1 … 64.
   int measure_volume_lesions = 0;
+  // --measure-intensity with --mode 3d (implies --measure-volume): the volume sidecar and volumes.csv
+  // also carry the intensity keys (nm03/measure.h IntensityStats). In 2D the flag is
+  // engine.pipe.measure_intensity.
+  bool measure_volume_intensity = false;
   // CLOCK_REALTIME when parse_args began (the --json record's "main_unix_s"): with the launcher's
   // own clock it splits a cold run's wall into process start-up (exec → main) and the rest.
   double main_unix_s = 0;
@@ -149,13 +153,16 @@ struct MeasureTotals {
   // --measure-diameters: the job's largest bidimensional_mm2 (0 when no slice has a lesion).
   bool diameters = false;
   double bidimensional_mm2_max = 0;
+  bool intensity = false;  // --measure-intensity: the table has the intensity columns
 };
 // `diameters` (--measure-diameters): the table also has the diameter keys' columns after `mean`
 // (lesion_first, major and perp flattened), and a patient's TOTAL row carries the patient's largest
 // bidimensional_mm2 with the major_mm and perp_mm of that slice (the first such slice; empty when no
 // slice has a lesion). A sidecar written earlier without the flag (--resume) leaves those columns empty.
+// `intensity` (--measure-intensity): the 13 intensity keys' columns after all the others; TOTAL rows leave
+// them empty, and so does a sidecar written earlier without the flag.
 MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients,
-                                     bool diameters = false);
+                                     bool diameters = false, bool intensity = false);
 std::string measure_totals_json(const MeasureTotals& t);  // the --json record's "measure" object
 const char* slice_status_name(int code);
 
@@ -172,8 +179,12 @@ struct VolumeTotals {
   uint64_t volume_vox = 0;
   double volume_mm3 = 0;
   int64_t lesions = -1;  // --measure-volume-lesions: rows of lesions.csv over the job's measured patients (−1: not asked for)
+  bool intensity = false;  // --measure-intensity: the table has the intensity columns
 };
-VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows);
+// `intensity` (--measure-intensity): the 13 intensity keys' columns after `mean`; a sidecar without them
+// (written earlier without the flag) leaves them empty.
+VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows,
+                               bool intensity = false);
 // --measure-volume-lesions: <out_root>/lesions.csv from the same sidecar texts, in plan order: a header,
 // then one row per reported lesion (patient, lesion = its 0-based rank, then the lesion object's fields
 // with first and bbox flattened); a failed patient has one row with its status name in `lesion` and

@@ -130,6 +130,8 @@ struct SingleResult {
   std::string measure_json;
   // PipelineParams::measure_diameters only: the K9 record of the lesion (measure_json then carries its keys too).
   SliceDiameters diameters{};
+  // PipelineParams::measure_intensity only: the K11 record (measure_json then carries its keys too).
+  IntensityStats intensity{};
 };
 
 struct RunHandle;  // a submitted run (Engine::submit)

@@ -108,9 +108,21 @@ SliceDiameters measure_diameters(const std::vector<uint8_t>& dilated, int connec
 // The sidecar text of a record pair (measure::to_json with the diameter keys).
 std::string measure_json(const SliceMeasure& m, const SliceDiameters& d, const SliceInput& s, const PipelineParams& p);
 // The sidecar text the --cpu paths write for slice `s`: measure() and, with p.measure_diameters,
-// measure_diameters() at p.measure_connectivity, through the matching measure_json.
+// measure_diameters() at p.measure_connectivity, through the matching measure_json; with
+// p.measure_intensity also measure_intensity(), its keys after all the others.
 std::string measure_sidecar(const std::vector<uint8_t>& dilated, const std::vector<uint8_t>& region, const SliceInput& s,
                             const PipelineParams& p);
+
+// First-order intensity statistics (nm03/measure.h IntensityStats) of the stored samples under
+// `dilated` (0/1 per pixel, h × w; the overload below: per voxel, d planes of h × w). The oracle of the
+// K11 kernels: it collects the samples, sorts them and indexes at rank − 1, and sums the squares — no
+// histogram; it shares only stored_sample and the rank formula with the kernels.
+IntensityStats measure_intensity(const std::vector<uint8_t>& dilated, const SliceInput& s);
+IntensityStats measure_intensity(const std::vector<uint8_t>& dilated, const VolumeInput& v);
+// The volume sidecar text with the intensity keys (the matching measure::volume_to_json overloads);
+// `lesions`: null without --measure-volume-lesions.
+std::string measure_volume_json(const VolumeMeasure& m, const IntensityStats& st, const std::vector<VolumeLesion>* lesions,
+                                int max_lesions, const VolumeInput& v, bool apply_rescale, int connectivity);
 
 // Measurements of a volume (VolumeParams::measure, nm03/measure.h VolumeMeasure): the record on the
 // `dilated` volume plus popcount(`region`) (0/1 per voxel, d planes of h × w), intensities from v.raw.

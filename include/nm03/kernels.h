@@ -241,6 +241,27 @@ void launch_volume_lesions(const uint64_t* dilated, const uint16_t* raw, size_t 
 // and the Python op load it.
 void preload_volume_lesions();
 
+// K11 (k11_intensity.hip), 2D: the IntensityStats record (nm03/measure.h) of the samples under every
+// slice's `dilated` plane, one workgroup per slice, slices of different sizes in one launch
+// (SliceDesc::w, h, wpr, mask_off, raw_off, type, stored_bits), a two-pass radix select in LDS. It reads
+// what K7 reads and writes nothing but `out` (nslices records, plain vector stores; device or
+// host-mapped memory). No global scratch, so every slice is measured; no host round trip, no allocation.
+void launch_measure_intensity(const uint64_t* dilated, const uint16_t* raw, const SliceDesc* descs, int nslices,
+                              IntensityStats* out, hipStream_t stream);
+// K11, 3D: the record of the samples under the `dilated` bit volume (d planes of h rows of ceil(w / 64)
+// words; plane z of the samples at raw + z · raw_plane_stride). Five small launches on `stream`
+// (init, high-byte histogram, select, low-byte histogram, final) separated by kernel boundaries; no host
+// round trip, no allocation. `acc`: kVolumeIntensityAccBytes of device memory, no initialisation needed;
+// `out`: one record, written with plain vector stores (device, pinned or host-mapped memory). Throws
+// DeviceError before any launch for a volume that launch_volume_measure refuses.
+constexpr size_t kVolumeIntensityAccBytes = 8192;
+void launch_volume_intensity(const uint64_t* dilated, const uint16_t* raw, size_t raw_plane_stride, int w, int h, int d,
+                             uint8_t type, uint8_t stored_bits, void* acc, IntensityStats* out, hipStream_t stream);
+// Load K11's code object on the current device. Not part of preload_kernels: only an engine or a
+// VolumeRunner built with the feature on and the Python ops (before their first launch) load it.
+void preload_measure_intensity();
+void preload_volume_intensity();
+
 // K6: binary threshold lo ≤ x ≤ hi → u8 0/1 (in 16-byte aligned, out 4-byte aligned).
 void launch_threshold(const float* in, uint8_t* out, size_t n, float lo, float hi, hipStream_t stream);
 

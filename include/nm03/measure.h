@@ -52,6 +52,20 @@ struct alignas(64) SliceDiameters {
 static_assert(sizeof(SliceDiameters) == 64, "SliceDiameters layout");
 constexpr uint32_t kDiametersNotMeasured = 0xFFFFFFFFu;
 
+// First-order intensity statistics (--measure-intensity): the record the K11 kernels write for one
+// slice or one volume. The samples are the stored sample values (stored_sample below) under the DILATED
+// mask, the set over which raw_sum / raw_min / raw_max are taken, so count = area_px (2D) or volume_vox
+// (3D). pct[j] for p = 10, 25, 50, 75, 90 is the k-th smallest sample with k = (p · count + 99) / 100 in
+// 64-bit integers (nearest rank, 1-based; p50 is the lower median of an even count). Every integer is 0
+// for an empty mask. The derived doubles exist only in measure::to_json / volume_to_json.
+struct alignas(64) IntensityStats {
+  uint64_t count;   // samples under the mask
+  uint64_t sum_sq;  // Σ v² (v² < 2^32 and count < 2^32: no overflow)
+  int32_t pct[5];   // raw_p10, raw_p25, raw_p50, raw_p75, raw_p90
+  uint32_t pad[7];
+};
+static_assert(sizeof(IntensityStats) == 64, "IntensityStats layout");
+
 // ---------------------------------------------------------------------------------------------
 // Bit quads (Gray 1971). Over every 2×2 window of the zero-padded mask, Q1 / Q3 count the windows
 // with exactly one / three set pixels and QD the two diagonal patterns. The Euler number
@@ -259,6 +273,40 @@ std::string to_json(const SliceMeasure& m, int w, int h, float spacing_x, float 
 // maximum when the spacing is isotropic.
 std::string to_json(const SliceMeasure& m, const SliceDiameters& d, int w, int h, float spacing_x, float spacing_y,
                     float slope, float intercept, bool apply_rescale, int connectivity);
+
+// The sidecar texts with --measure-intensity: the texts above with the intensity keys appended — after
+// `mean` (after the diameter keys when there are any; in 3D before lesions_max / lesions), so the text
+// before the new keys is byte for byte the text without them. First the integers: raw_sum_sq, raw_p10,
+// raw_p25, raw_p50, raw_p75, raw_p90; then the derived doubles (%.9g):
+//   std = √((n · sum_sq − raw_sum²) / n²), the population standard deviation, the numerator formed
+//         exactly in 128-bit integers; times |slope| when apply_rescale
+//   p10, p25, median, p75, p90 = slope · raw_pP + intercept when apply_rescale, else raw_pP
+//   iqr = |p75 − p25|
+// With a negative slope these are the MAPPED raw order statistics (p10 > p90), as `mean` is the mapped
+// raw mean. All seven are null for an empty mask.
+std::string to_json(const SliceMeasure& m, const IntensityStats& st, int w, int h, float spacing_x, float spacing_y,
+                    float slope, float intercept, bool apply_rescale, int connectivity);
+std::string to_json(const SliceMeasure& m, const SliceDiameters& d, const IntensityStats& st, int w, int h, float spacing_x,
+                    float spacing_y, float slope, float intercept, bool apply_rescale, int connectivity);
+std::string volume_to_json(const VolumeMeasure& m, const IntensityStats& st, int w, int h, int d, double spacing_x,
+                           double spacing_y, double spacing_z, const std::string& spacing_z_source, float slope,
+                           float intercept, bool apply_rescale, int connectivity);
+std::string volume_to_json(const VolumeMeasure& m, const IntensityStats& st, const VolumeLesion* lesions, int count,
+                           int lesions_max, int w, int h, int d, double spacing_x, double spacing_y, double spacing_z,
+                           const std::string& spacing_z_source, float slope, float intercept, bool apply_rescale,
+                           int connectivity);
+// The population standard deviation of the raw samples, √(n · sum_sq − raw_sum²) / n with the radicand
+// exact in 128-bit integers; 0 for an empty mask.
+double intensity_std(const IntensityStats& st, int64_t raw_sum);
+// The appended keys alone (",\"raw_sum_sq\":…" up to iqr), for the overloads above.
+std::string intensity_keys(const IntensityStats& st, int64_t raw_sum, float slope, float intercept, bool apply_rescale);
+
+// The record of the samples under a bit plane (h rows of wpr words) or, with d > 1 planes of h · wpr
+// words and the samples of plane z at raw + z · raw_plane_stride, a bit volume, computed on the host
+// with the two-pass radix select of nm03/intensity_core.h, one word after the other: what the K11
+// kernels compute, without a GPU.
+IntensityStats intensity_words(const uint64_t* dilated, const uint16_t* raw, size_t raw_plane_stride, int w, int h, int d,
+                               int wpr, uint8_t type, uint8_t stored_bits);
 
 // File name of a slice's sidecar next to its JPEGs.
 inline std::string sidecar_name(const std::string& stem) { return stem + "_measure.json"; }

@@ -54,6 +54,10 @@ struct PipelineParams {
   bool measure_diameters = false;
   // Multi-frame files (dicom::select_frame): -1 rejects them (default), k ≥ 0 imports frame k.
   int frame = -1;
+  // First-order intensity statistics of the samples under the dilated mask (--measure-intensity,
+  // nm03/measure.h IntensityStats): exact percentiles and Σ v², further keys in the sidecar. Opt-in;
+  // implies `measure`.
+  bool measure_intensity = false;
 };
 
 enum SeShape : int { kSeSquare = 0, kSeDisc = 1 };

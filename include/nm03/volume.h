@@ -62,6 +62,8 @@ struct VolumeResult {
   // VolumeParams::measure_lesions: the K10 records of the largest components, largest first
   // (min(measure_lesions, measure.components) of them).
   std::vector<VolumeLesion> lesions;
+  // VolumeParams::measure_intensity: the K11 record of the samples under the dilated volume.
+  IntensityStats intensity = {};
 };
 
 struct VolumeExportStats {
@@ -80,6 +82,8 @@ struct VolumeParams {
   // With measure: also one record per lesion for the N largest components (K10, nm03/measure.h
   // VolumeLesion); 0 = off, else 1 … kMaxVolumeLesions.
   int measure_lesions = 0;
+  // With measure: also the first-order intensity statistics (K11, nm03/measure.h IntensityStats).
+  bool measure_intensity = false;
 };
 
 // Runs the 3D pipeline on `device`; copies masks back when `want_masks`. A VolumeRunner keeps
@@ -93,7 +97,7 @@ class VolumeRunner {
   VolumeRunner& operator=(const VolumeRunner&) = delete;
   // With p.measure the K8 kernels run after the segmentation (first use loads their code object and
   // allocates their scratch, kept like the other buffers); without it nothing of K8 is touched. The
-  // same holds for p.measure_lesions and K10.
+  // same holds for p.measure_lesions and K10, and for p.measure_intensity and K11 (after K8's last launch).
   VolumeResult run(const VolumeInput& v, const VolumeParams& p, bool want_masks);
   // After run() on the same volume: the 2·d exported JPEG files of the 3D cohort mode, in plane
   // order (original, processed), rendered and encoded on the GPU (K3/K4) from the volume still on
@@ -105,7 +109,7 @@ class VolumeRunner {
   // coordinates. Preprocesses the slab's planes, runs the global region-growing fixpoint and the
   // halo cube dilation with the other ranks of `comm` (collective), leaving the slab on the device:
   // export_jpegs(slab, ...) then exports its planes. Masks (when requested) are the slab's.
-  // p.measure or p.measure_lesions throws std::invalid_argument: components that cross slabs would
+  // p.measure, p.measure_lesions or p.measure_intensity throws std::invalid_argument: components that cross slabs would
   // need a collective.
   VolumeResult run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p, bool want_masks,
                         struct SlabStats* stats = nullptr);

@@ -41,6 +41,9 @@ class PipelineConfig:
     # bidimensional diameters of the lesion (the largest component) in the sidecar; implies `measure`;
     # run_array / golden gain "diameters"
     measure_diameters: bool = False
+    # exact percentiles (10/25/50/75/90), sum of squares, std and iqr of the samples under the dilated mask
+    # in the sidecar (K11); implies `measure`; run_array / golden gain "intensity"
+    measure_intensity: bool = False
     # render / export
     out_width: int = 512
     out_height: int = 512
@@ -65,7 +68,7 @@ class PipelineConfig:
     _PIPE = ("norm_low", "norm_high", "norm_min", "norm_max", "clip_min", "clip_max", "median_window",
              "sharpen_gain", "sharpen_sigma", "sharpen_mask", "srg_min", "srg_max", "srg_connectivity",
              "dilation_size", "erosion_size", "min_dim", "apply_rescale", "frame", "se_shape", "measure",
-             "measure_connectivity", "measure_diameters")
+             "measure_connectivity", "measure_diameters", "measure_intensity")
     _RENDER = ("out_width", "out_height", "label_opacity", "border_opacity", "border_radius", "jpeg_quality",
                "jpeg_sampling")
 
@@ -73,7 +76,7 @@ class PipelineConfig:
         p = native().PipelineParams()
         for k in self._PIPE:
             setattr(p, k, getattr(self, k))
-        p.measure = bool(self.measure or self.measure_diameters)
+        p.measure = bool(self.measure or self.measure_diameters or self.measure_intensity)
         return p
 
     def render_params(self):

@@ -8,7 +8,10 @@ VolumeMeasure): the result gains `measure` (the record's integers) and `measure_
 CLI's volume_measure.json, from the one native volume_to_json). With `measure_lesions=N` (1 … 64; needs
 `measure`) the K10 kernels also report the N largest connected components: the result gains `lesions`
 (a list of dicts of each record's integers, largest first) and `measure_json` is the longer text with
-the `lesions_max` / `lesions` keys."""
+the `lesions_max` / `lesions` keys. With `measure_intensity=True` (needs `measure`) the K11 kernels also
+report the exact 10/25/50/75/90th percentile and the sum of squares of the samples under the dilated
+volume: the result gains `intensity` (the record's integers) and `measure_json` carries the intensity
+keys after `mean` (before the lesion keys)."""
 import numpy as np
 
 from .._native import native
@@ -23,7 +26,7 @@ def _meta_args(meta):
 
 class VolumePipeline:
     def __init__(self, config: PipelineConfig = None, connectivity: int = 6, dilation: int = 7, measure: bool = False,
-                 measure_connectivity: int = 26, measure_lesions: int = 0):
+                 measure_connectivity: int = 26, measure_lesions: int = 0, measure_intensity: bool = False):
         self.config = config or PipelineConfig()
         self.connectivity = connectivity
         self.dilation = dilation
@@ -36,6 +39,9 @@ class VolumePipeline:
             raise ValueError("measure_lesions needs measure=True")
         if not 0 <= self.measure_lesions <= 64:
             raise ValueError(f"measure_lesions must be 0 (off) or 1..64 (got {measure_lesions})")
+        self.measure_intensity = bool(measure_intensity)
+        if self.measure_intensity and not self.measure:
+            raise ValueError("measure_intensity needs measure=True")
         self._runners = {}  # device -> native VolumeRunner (buffers/stream reused across volumes)
 
     def default_seeds(self, volume):
@@ -57,7 +63,7 @@ class VolumePipeline:
         return runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s, measure=self.measure,
                           measure_connectivity=self.measure_connectivity, spacing=[float(v) for v in spacing],
                           spacing_z_source=str(spacing_z_source), measure_lesions=self.measure_lesions,
-                          **_meta_args(meta))
+                          measure_intensity=self.measure_intensity, **_meta_args(meta))
 
     def run_series(self, series_dir, seeds=None, device=None):
         """A DICOM series directory as one volume (utils.read_series: the reference's file-number
@@ -95,7 +101,9 @@ class VolumePipeline:
         """The golden model's record of `dilated` (+ popcount of `region`) over the samples `raw`
         ([D, H, W] each) at this pipeline's measure_connectivity → (measure dict, measure_json text):
         what `run` returns under those keys when measuring. With measure_lesions the text is the longer
-        one and the tuple has a third member, the list of lesion dicts (`run`'s `lesions`)."""
+        one and the tuple has a third member, the list of lesion dicts (`run`'s `lesions`). With
+        measure_intensity the text carries the intensity keys and the tuple's last member is the intensity
+        dict (`run`'s `intensity`)."""
         n = native()
         a = _meta_args(meta)
         d, h, w = np.asarray(dilated).shape
@@ -112,4 +120,12 @@ class VolumePipeline:
                                         str(spacing_z_source), a["slope"], a["intercept"],
                                         bool(self.config.pipeline_params().apply_rescale), self.measure_connectivity,
                                         lesions, self.measure_lesions)
-        return (rec, text) if lesions is None else (rec, text, lesions)
+        if not self.measure_intensity:
+            return (rec, text) if lesions is None else (rec, text, lesions)
+        intensity = n.golden_measure_volume_intensity(np.ascontiguousarray(dilated, dtype=np.uint8),
+                                                      np.ascontiguousarray(raw, dtype=np.uint16), a["type"], a["stored_bits"])
+        text = n.volume_measure_to_json(rec, w, h, d, float(spacing[0]), float(spacing[1]), float(spacing[2]),
+                                        str(spacing_z_source), a["slope"], a["intercept"],
+                                        bool(self.config.pipeline_params().apply_rescale), self.measure_connectivity,
+                                        lesions, self.measure_lesions, intensity)
+        return (rec, text, intensity) if lesions is None else (rec, text, lesions, intensity)

@@ -364,3 +364,66 @@ def measure_volume_lesions(dilated, region, raw, max_lesions, connectivity=26, p
     rec, lesions = native().k_measure_volume_lesions(dw.data_ptr(), rw.data_ptr(), x.data_ptr(), w, h, d, int(max_lesions),
                                                      pixel_type, int(stored_bits), int(connectivity), _stream())
     return rec, lesions
+
+
+def measure_intensity(dilated, raw, pixel_type="u16", stored_bits=16):
+    """First-order intensity statistics of the stored samples of `raw` under masks (K11, nm03/measure.h
+    IntensityStats) → list of dicts of the record's exact integers: count (= area_px), raw_sum_sq (Σ v²)
+    and raw_p10 / raw_p25 / raw_p50 / raw_p75 / raw_p90, the k-th smallest sample with
+    k = (p · count + 99) // 100 (nearest rank; raw_p50 is the lower median). An empty mask gives zeros.
+
+    `dilated` (bool) and `raw` (16-bit storage) are CUDA tensors [N, H, W] or [H, W], or lists of [H, W]
+    tensors of ANY sizes: the whole batch is one launch, one workgroup per mask (a two-pass radix select
+    in LDS). `pixel_type` and `stored_bits` hold for every slice, or are lists with one entry per slice."""
+    def as_list(t):
+        if isinstance(t, (list, tuple)):
+            return list(t)
+        return list(_as3d(t))
+    dl, xl = as_list(dilated), as_list(raw)
+    if not dl or len(xl) != len(dl):
+        raise ValueError("dilated and raw must hold the same number of slices")
+    types = list(pixel_type) if isinstance(pixel_type, (list, tuple)) else [pixel_type] * len(dl)
+    bits = [int(b) for b in stored_bits] if isinstance(stored_bits, (list, tuple)) else [int(stored_bits)] * len(dl)
+    if len(types) != len(dl) or len(bits) != len(dl):
+        raise ValueError("pixel_type and stored_bits lists need one entry per slice")
+    if any(t not in ("u16", "i16", "u8") for t in types):
+        raise ValueError("pixel_type must be u16, i16 or u8")
+    if any(not 1 <= b <= 16 for b in bits):
+        raise ValueError("stored_bits must be 1..16")
+    hs, ws, dw, xs = [], [], [], []
+    for d, x in zip(dl, xl):
+        if d.dim() != 2 or x.shape != d.shape:
+            raise ValueError("every slice needs dilated and raw of one [H, W] shape")
+        if not d.is_cuda:
+            raise ValueError("masks must be CUDA (HIP) tensors")
+        x = x.contiguous()
+        _check(x, _U16, "raw")
+        hs.append(int(d.shape[0]))
+        ws.append(int(d.shape[1]))
+        dw.append(pack_bits(d.bool().unsqueeze(0)).reshape(-1))
+        xs.append(x.reshape(-1).view(torch.int16))
+    planes = torch.cat(dw).contiguous()
+    samples = torch.cat(xs).contiguous()
+    return native().k_measure_intensity(planes.data_ptr(), samples.data_ptr(), hs, ws, types, bits, _stream())
+
+
+def measure_volume_intensity(dilated, raw, pixel_type="u16", stored_bits=16):
+    """measure_intensity's record for a volume mask (K11's five 3D launches) → one dict: count
+    (= volume_vox), raw_sum_sq and the five raw percentiles of the stored samples of `raw` under `dilated`.
+
+    `dilated` (bool) and `raw` (16-bit storage) are CUDA tensors [D, H, W] of one shape; a volume with
+    (W + 1)·H·D + 1 ≥ 2³² raises, as for measure_volume."""
+    if dilated.dim() != 3 or raw.shape != dilated.shape:
+        raise ValueError("dilated and raw must be [D, H, W] of one shape")
+    if not dilated.is_cuda:
+        raise ValueError("masks must be CUDA (HIP) tensors")
+    if not 1 <= int(stored_bits) <= 16:
+        raise ValueError("stored_bits must be 1..16")
+    x = raw.contiguous()
+    _check(x, _U16, "raw")
+    d, h, w = (int(v) for v in dilated.shape)
+    if d < 1 or h < 1 or w < 1:
+        raise ValueError("empty volume")
+    dw = pack_bits(dilated.bool()).contiguous()
+    return native().k_measure_volume_intensity(dw.data_ptr(), x.data_ptr(), w, h, d, pixel_type, int(stored_bits),
+                                               _stream())

@@ -437,6 +437,36 @@ def measure_volume_lesions(dilated, region, raw, max_lesions, connectivity=26, p
     return rec, lesions
 
 
+def measure_intensity(dilated, raw, pixel_type="u16", stored_bits=16):
+    """The intensity record (nm03/measure.h IntensityStats) of one mask of any rank (torch or NumPy) in
+    NumPy: the stored samples under the mask sorted, raw_pP = sorted[k − 1] with the integer nearest rank
+    k = (p · n + 99) // 100 (not np.percentile: its float rank disagrees at exact multiples), and the sum
+    of squares in Python integers. Returns the dict of integers ops.measure_intensity gives."""
+    import numpy as np
+
+    def to_np(t):
+        return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+    m = to_np(dilated).astype(bool)
+    v = to_np(raw).view(np.uint16).astype(np.int64)
+    sh = 16 - int(stored_bits)
+    if pixel_type == "i16":
+        v = ((v << sh) & 0xFFFF).astype(np.uint16).view(np.int16).astype(np.int64) >> sh
+    else:
+        v = v & (0xFFFF >> sh)
+    s = np.sort(v[m])
+    n = int(s.size)
+    out = {"count": n, "raw_sum_sq": sum(int(x) * int(x) for x in s)}
+    for p in (10, 25, 50, 75, 90):
+        out[f"raw_p{p}"] = int(s[(p * n + 99) // 100 - 1]) if n else 0
+    return out
+
+
+def measure_volume_intensity(dilated, raw, pixel_type="u16", stored_bits=16):
+    """measure_intensity of a volume mask [D, H, W]: the same definition over the voxels."""
+    return measure_intensity(dilated, raw, pixel_type, stored_bits)
+
+
 def psnr(a, b):
     mse = ((a.double() - b.double()) ** 2).mean().item()
     return math.inf if mse == 0 else 10 * math.log10(255.0 ** 2 / mse)

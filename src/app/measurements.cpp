@@ -40,6 +40,12 @@ const char* const kDiameterColumns[] = {"lesion_px", "lesion_first_x", "lesion_f
 constexpr size_t kNumDiameterColumns = sizeof(kDiameterColumns) / sizeof(kDiameterColumns[0]);
 constexpr size_t kColMajorMm = kNumColumns + 13, kColPerpMm = kNumColumns + 14, kColBidimensional = kNumColumns + 15;
 
+// --measure-intensity: the columns after all of those — the intensity keys in their order.
+const char* const kIntensityColumns[] = {"raw_sum_sq", "raw_p10", "raw_p25", "raw_p50", "raw_p75", "raw_p90", "std",
+                                         "p10",        "p25",     "median",  "p75",     "p90",     "iqr"};
+constexpr size_t kNumIntensityColumns = sizeof(kIntensityColumns) / sizeof(kIntensityColumns[0]);
+const char* const kIntensityKey = ",\"raw_sum_sq\":";
+
 // The values of one sidecar line in column order ("" for null). The text is this program's own
 // (one flat object, one array of four integers): values are what stands between ':' or ',' and the
 // next ',' / ']' / '}'.
@@ -98,23 +104,38 @@ std::string without_lesions(const std::string& text) {
   return at == std::string::npos ? text : text.substr(0, at) + "}\n";
 }
 
+// A sidecar's text without the intensity keys (they are the last keys of a flat object, or stand before
+// the lesion keys, which the caller has cut), and those keys' 13 values in `intensity` when there are any.
+std::string without_intensity(const std::string& text, std::vector<std::string>* intensity) {
+  const size_t at = text.find(kIntensityKey);
+  if (at == std::string::npos) return text;
+  std::vector<std::string> v;
+  if (intensity && parse_sidecar("{" + text.substr(at + 1), v, kNumIntensityColumns)) *intensity = v;
+  return text.substr(0, at) + "}\n";
+}
+
 }  // namespace
 
-VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows) {
+VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows, bool intensity) {
   VolumeTotals tot;
+  tot.intensity = intensity;
   std::ostringstream o;
   o << "patient,status";
   for (const char* c : kVolumeColumns) o << "," << c;
+  if (intensity)
+    for (const char* c : kIntensityColumns) o << "," << c;
   o << "\n";
   for (const auto& r : rows) {
-    std::vector<std::string> v;
-    const bool have = r.ok && parse_sidecar(without_lesions(r.sidecar), v, kNumVolumeColumns);
+    std::vector<std::string> v, iv;
+    const bool have = r.ok && parse_sidecar(without_intensity(without_lesions(r.sidecar), &iv), v, kNumVolumeColumns);
     o << r.id << "," << (r.ok ? (have ? "ok" : "no_sidecar") : "failed");
     for (size_t c = 0; c < kNumVolumeColumns; ++c) {
       std::string x = have ? v[c] : std::string();
       if (x.size() >= 2 && x.front() == '"' && x.back() == '"') x = x.substr(1, x.size() - 2);
       o << "," << x;
     }
+    if (intensity)
+      for (size_t c = 0; c < kNumIntensityColumns; ++c) o << "," << (have && iv.size() == kNumIntensityColumns ? iv[c] : std::string());
     o << "\n";
     if (!have) continue;
     ++tot.volumes;
@@ -137,7 +158,9 @@ std::string volume_totals_json(const VolumeTotals& t) {
   else
     std::snprintf(buf, sizeof buf, "{\"volumes\": %lld, \"volume_vox_total\": %llu, \"volume_mm3_total\": %.9g}",
                   (long long)t.volumes, (unsigned long long)t.volume_vox, t.volume_mm3);
-  return buf;
+  std::string s = buf;
+  if (t.intensity) s.insert(s.size() - 1, ", \"intensity\": true");
+  return s;
 }
 
 int64_t write_lesions_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows) {
@@ -184,15 +207,18 @@ int64_t write_lesions_csv(const std::string& out_root, const std::vector<VolumeP
 }
 
 MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients,
-                                     bool diameters) {
+                                     bool diameters, bool intensity) {
   MeasureTotals tot;
   tot.diameters = diameters;
+  tot.intensity = intensity;
   const size_t ncols = kNumColumns + (diameters ? kNumDiameterColumns : 0);
   std::ostringstream o;
   o << "patient,file,status";
   for (const char* c : kColumns) o << "," << c;
   if (diameters)
     for (const char* c : kDiameterColumns) o << "," << c;
+  if (intensity)
+    for (const char* c : kIntensityColumns) o << "," << c;
   o << "\n";
   char buf[64];
   for (const auto& p : patients) {
@@ -204,19 +230,23 @@ MeasureTotals write_measurements_csv(const std::string& out_root, const std::vec
     std::string bidim_text, major_text, perp_text;
     for (size_t i = 0; i < p.files.size(); ++i) {
       const std::string name = cohort::filename(p.files[i]);
-      std::vector<std::string> v;
+      std::vector<std::string> v, iv;
       bool have = false;
       if (p.status[i] == kSliceOk) {
         std::ifstream f(cohort::with_slash(p.out_dir) + measure::sidecar_name(cohort::stem(p.files[i])), std::ios::binary);
         std::stringstream ss;
         if (f) ss << f.rdbuf();
         // With `diameters` a sidecar without the diameter keys (written earlier without the flag) is read too.
-        const std::string text = ss.str();
+        // With `intensity` the intensity keys, the sidecar's last, go to their own columns; without them
+        // (a sidecar written earlier without the flag) those columns stay empty.
+        const std::string text = intensity ? without_intensity(ss.str(), &iv) : ss.str();
         have = f && (parse_sidecar(text, v, ncols) || (diameters && parse_sidecar(text, v, kNumColumns)));
         if (have) v.resize(ncols);
       }
       o << p.id << "," << name << "," << (p.status[i] == kSliceOk && !have ? "no_sidecar" : slice_status_name(p.status[i]));
       for (size_t c = 0; c < ncols; ++c) o << "," << (have ? v[c] : std::string());
+      if (intensity)
+        for (size_t c = 0; c < kNumIntensityColumns; ++c) o << "," << (have && iv.size() == kNumIntensityColumns ? iv[c] : std::string());
       o << "\n";
       if (!have) continue;
       ++tot.slices;
@@ -240,6 +270,8 @@ MeasureTotals write_measurements_csv(const std::string& out_root, const std::vec
       if (diameters && c == kColPerpMm) o << perp_text;
       if (diameters && c == kColBidimensional) o << bidim_text;
     }
+    if (intensity)
+      for (size_t c = 0; c < kNumIntensityColumns; ++c) o << ",";
     o << "\n";
     tot.area_px += area_px;
     tot.area_mm2 += area_mm2;
@@ -261,7 +293,9 @@ std::string measure_totals_json(const MeasureTotals& t) {
   else
     std::snprintf(buf, sizeof buf, "{\"slices\": %lld, \"area_px_total\": %llu, \"area_mm2_total\": %.9g}", (long long)t.slices,
                   (unsigned long long)t.area_px, t.area_mm2);
-  return buf;
+  std::string s = buf;
+  if (t.intensity) s.insert(s.size() - 1, ", \"intensity\": true");
+  return s;
 }
 
 }  // namespace nm03::app

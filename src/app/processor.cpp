@@ -64,6 +64,9 @@ void usage(const std::string& which) {
             << "                         <out>/measurements.csv; test_pipeline: measure.json (2D only)\n"
             << "  --measure-diameters    --measure plus the bidimensional diameters of the lesion (the largest component):\n"
             << "                         major and perpendicular diameter and their product in the sidecar and the table\n"
+            << "  --measure-intensity    --measure (with --mode 3d: --measure-volume) plus exact first-order statistics of the\n"
+            << "                         samples under the dilated mask: 10/25/50/75/90th percentile, sum of squares, std, iqr\n"
+            << "                         in the sidecar and the table (not with --split-volume)\n"
             << "  --measure-connectivity 4|8  connectivity of the component count (default 8; holes use the dual)\n"
             << "  --measure-volume       3d: also write the volumetry of each patient's dilated volume (voxels, mm3,\n"
             << "                         surface, components, cavities, tunnels): <patient>/volume_measure.json and\n"
@@ -152,6 +155,7 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
   arm_fast_exit();
   install_crash_handler();
   AppConfig c;
+  bool measure_intensity = false;  // --measure-intensity
   c.main_unix_s = main_unix;
   c.data_root = cohort::default_data_root();
   c.out_dir = which == "test_pipeline" ? "../out-test" : which == "img_processing_sequential" ? "../out-sequential" : "../out-parallel";
@@ -257,6 +261,7 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
     else if (a == "--overlay") c.engine.render.overlay = true;
     else if (a == "--measure") c.engine.pipe.measure = true;
     else if (a == "--measure-diameters") c.engine.pipe.measure = c.engine.pipe.measure_diameters = true;
+    else if (a == "--measure-intensity") measure_intensity = true;  // resolved after the loop: --mode may follow
     else if (a == "--measure-volume") c.measure_volume = true;
     else if (a == "--measure-volume-connectivity") {
       const std::string v = val();
@@ -318,6 +323,13 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
     std::cerr << "--overlay needs --jpeg-sampling 420 or 444: a one-component gray file cannot carry colour" << std::endl;
     std::exit(2);
   }
+  if (measure_intensity && c.split_volume) {
+    std::cerr << "--measure-intensity is not available with --split-volume" << std::endl;
+    std::exit(2);
+  }
+  // --measure-intensity implies --measure, or --measure-volume with --mode 3d.
+  if (measure_intensity && c.mode == "3d") c.measure_volume = c.measure_volume_intensity = true;
+  if (measure_intensity && c.mode != "3d") c.engine.pipe.measure = c.engine.pipe.measure_intensity = true;
   if (c.engine.pipe.measure_diameters && c.mode == "3d") {
     std::cerr << "--measure-diameters is not available with --mode 3d" << std::endl;
     std::exit(2);
@@ -498,7 +510,8 @@ int run_sequential(const AppConfig& cfg) {
       std::cout << "Successfully processed " << successful << "/" << patients.size() << " patients." << std::endl;  // :341
       if (cfg.engine.pipe.measure) {
         try {
-          measure_totals = write_measurements_csv(cfg.out_dir, measured, cfg.engine.pipe.measure_diameters);
+          measure_totals = write_measurements_csv(cfg.out_dir, measured, cfg.engine.pipe.measure_diameters,
+                                                  cfg.engine.pipe.measure_intensity);
         } catch (const std::exception& e) {
           std::cerr << "Error writing measurements.csv: " << e.what() << std::endl;
         }
@@ -648,7 +661,8 @@ std::vector<MeasurePatient> measure_patients(const std::vector<PatientPlan>& pla
 void write_measure_table(const AppConfig& cfg, const std::vector<PatientPlan>& plan, const std::vector<SliceStatus>& gst,
                          MeasureTotals* totals) {
   try {
-    *totals = write_measurements_csv(cfg.out_dir, measure_patients(plan, gst), cfg.engine.pipe.measure_diameters);
+    *totals = write_measurements_csv(cfg.out_dir, measure_patients(plan, gst), cfg.engine.pipe.measure_diameters,
+                                     cfg.engine.pipe.measure_intensity);
   } catch (const std::exception& e) {
     std::cerr << "Error writing measurements.csv: " << e.what() << std::endl;
   }

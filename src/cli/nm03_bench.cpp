@@ -41,6 +41,7 @@ int main(int argc, char** argv) {
   bool measure_volume = false;  // volume: also K8 (the volumetry of the dilated volume) per run
   int measure_volume_conn = 26;
   int measure_volume_lesions = 0;  // volume: also K10 (one record per lesion, the N largest) per run
+  bool measure_intensity = false;  // cohort with --measure / volume with --measure-volume: also K11 (percentiles, sum of squares)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto v = [&] { return std::string(argv[++i]); };
@@ -65,6 +66,7 @@ int main(int argc, char** argv) {
     else if (a == "--overlay") ec.render.overlay = true;  // cohort: also the colour overlay per slice
     else if (a == "--measure") ec.pipe.measure = true;    // cohort: also K7 and the measurement sidecar per slice
     else if (a == "--measure-diameters") ec.pipe.measure = ec.pipe.measure_diameters = true;  // cohort: K7, K9 and the extended sidecar
+    else if (a == "--measure-intensity") measure_intensity = true;
     else if (a == "--measure-connectivity") ec.pipe.measure_connectivity = std::atoi(v().c_str()) == 4 ? 4 : 8;
     else if (a == "--measure-volume") measure_volume = true;
     else if (a == "--measure-volume-connectivity") measure_volume_conn = std::atoi(v().c_str()) == 6 ? 6 : 26;
@@ -83,6 +85,9 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  // --measure-intensity implies the measurement it extends: --measure (cohort) or --measure-volume (volume).
+  if (measure_intensity && config == "cohort") ec.pipe.measure = ec.pipe.measure_intensity = true;
+  if (measure_intensity && config == "volume") measure_volume = true;
   try {
     const std::string base = nm03::cohort::cohort_dir(root);
     auto pids = nm03::cohort::find_patient_dirs(base);
@@ -172,6 +177,7 @@ int main(int argc, char** argv) {
       vp.measure = measure_volume;
       vp.measure_connectivity = measure_volume_conn;
       vp.measure_lesions = measure_volume_lesions;
+      vp.measure_intensity = measure_intensity;
       nm03::VolumeRunner runner(ec.device);
       for (int w = 0; w < warmup; ++w) runner.run(v, vp, false);
       double ks = 0, ms = 0;
@@ -179,6 +185,7 @@ int main(int argc, char** argv) {
       nm03::VolumeMeasure vm = {};
       size_t lesions = 0;
       uint64_t lesion0_vox = 0;
+      nm03::IntensityStats vi = {};
       const double t0 = now_s();
       for (int k = 0; k < steps; ++k) {
         auto r = runner.run(v, vp, false);
@@ -186,6 +193,7 @@ int main(int argc, char** argv) {
         ms += r.measure_s;
         sweeps = r.sweeps;
         vm = r.measure;
+        vi = r.intensity;
         lesions = r.lesions.size();
         lesion0_vox = lesions ? r.lesions[0].voxels : 0;
       }
@@ -209,6 +217,7 @@ int main(int argc, char** argv) {
       if (measure_volume_lesions)
         std::cout << ", \"lesions_max\": " << measure_volume_lesions << ", \"lesions\": " << lesions
                   << ", \"largest_lesion_vox\": " << lesion0_vox;
+      if (measure_intensity) std::cout << ", \"intensity\": true, \"raw_p50\": " << vi.pct[2];
       std::cout << "}" << std::endl;
     } else if (config == "volume-cpu") {
       if (pids.empty()) throw std::runtime_error("no patients");

@@ -107,6 +107,14 @@ std::string measure_json(const SliceMeasure& m, const SliceDiameters& d, const S
 std::string measure_sidecar(const std::vector<uint8_t>& dilated, const std::vector<uint8_t>& region, const SliceInput& s,
                             const PipelineParams& p) {
   const SliceMeasure m = measure(dilated, region, s, p.measure_connectivity);
+  if (p.measure_intensity) {  // the intensity keys after all the others
+    const IntensityStats st = measure_intensity(dilated, s);
+    if (!p.measure_diameters)
+      return measure::to_json(m, st, s.w, s.h, s.spacing_x, s.spacing_y, s.slope, s.intercept, p.apply_rescale,
+                              p.measure_connectivity);
+    return measure::to_json(m, measure_diameters(dilated, p.measure_connectivity, s.w, s.h), st, s.w, s.h, s.spacing_x,
+                            s.spacing_y, s.slope, s.intercept, p.apply_rescale, p.measure_connectivity);
+  }
   if (!p.measure_diameters) return measure_json(m, s, p);
   return measure_json(m, measure_diameters(dilated, p.measure_connectivity, s.w, s.h), s, p);
 }

@@ -26,6 +26,7 @@
 #include "nm03/metaimage.h"
 #include "nm03/numa.h"
 #include "nm03/golden.h"
+#include "nm03/intensity_core.h"
 #include "nm03/jpeg.h"
 #include "nm03/jpeg_dct.h"
 #include "nm03/jpeg_lossless.h"
@@ -275,6 +276,28 @@ SliceDiameters diameters_from(const py::dict& d) {
   return m;
 }
 
+// The integers of an intensity record (nm03/measure.h IntensityStats) as a dict.
+py::dict intensity_dict(const IntensityStats& s) {
+  py::dict d;
+  d["count"] = s.count;
+  d["raw_sum_sq"] = s.sum_sq;
+  d["raw_p10"] = s.pct[0];
+  d["raw_p25"] = s.pct[1];
+  d["raw_p50"] = s.pct[2];
+  d["raw_p75"] = s.pct[3];
+  d["raw_p90"] = s.pct[4];
+  return d;
+}
+
+IntensityStats intensity_from(const py::dict& d) {
+  IntensityStats s{};
+  s.count = d["count"].cast<uint64_t>();
+  s.sum_sq = d["raw_sum_sq"].cast<uint64_t>();
+  static const char* const keys[5] = {"raw_p10", "raw_p25", "raw_p50", "raw_p75", "raw_p90"};
+  for (int j = 0; j < 5; ++j) s.pct[j] = d[keys[j]].cast<int32_t>();
+  return s;
+}
+
 // The integers of a volume record (nm03/measure.h VolumeMeasure) as a dict.
 py::dict volume_measure_dict(const VolumeMeasure& m) {
   py::dict d;
@@ -395,6 +418,7 @@ struct VolumeMeta {
   bool measure = false;
   int measure_connectivity = 26;
   int measure_lesions = 0;
+  bool measure_intensity = false;
 };
 
 void apply_meta(const VolumeMeta& mt, VolumeInput& v) {
@@ -433,6 +457,7 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
     vp.measure = meta->measure;
     vp.measure_connectivity = meta->measure_connectivity;
     vp.measure_lesions = meta->measure_lesions;
+    vp.measure_intensity = meta->measure_intensity;
   }
   VolumeResult r;
   {
@@ -452,6 +477,11 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
       d["lesions"] = volume_lesion_list(r.lesions.data(), r.lesions.size());
       d["measure_json"] = golden::measure_volume_json(r.measure, r.lesions, vp.measure_lesions, v, vp.pipe.apply_rescale,
                                                       vp.measure_connectivity);
+    }
+    if (vp.measure_intensity) {
+      d["intensity"] = intensity_dict(r.intensity);
+      d["measure_json"] = golden::measure_volume_json(r.measure, r.intensity, vp.measure_lesions ? &r.lesions : nullptr,
+                                                      vp.measure_lesions, v, vp.pipe.apply_rescale, vp.measure_connectivity);
     }
     d["measure_s"] = r.measure_s;
   }
@@ -485,6 +515,7 @@ PYBIND11_MODULE(_nm03, m) {
       .def_readwrite("se_shape", &PipelineParams::se_shape)
       .def_readwrite("measure", &PipelineParams::measure)
       .def_readwrite("measure_diameters", &PipelineParams::measure_diameters)
+      .def_readwrite("measure_intensity", &PipelineParams::measure_intensity)
       .def_property(
           "measure_connectivity", [](const PipelineParams& p) { return (int)p.measure_connectivity; },
           [](PipelineParams& p, int v) {
@@ -840,9 +871,10 @@ PYBIND11_MODULE(_nm03, m) {
           d["overlay"] = to_np<uint8_t>(j.overlay_canvas, {rp.out_height, rp.out_width, 3});
           d["jpeg_overlay"] = py::bytes((const char*)j.overlay.data(), j.overlay.size());
         }
-        if (p.measure || p.measure_diameters) {
+        if (p.measure || p.measure_diameters || p.measure_intensity) {
           const SliceMeasure sm = golden::measure(r.dilated, r.region, s, p.measure_connectivity);
           d["measure"] = measure_dict(sm);
+          if (p.measure_intensity) d["intensity"] = intensity_dict(golden::measure_intensity(r.dilated, s));
           if (p.measure_diameters) {
             const SliceDiameters sd = golden::measure_diameters(r.dilated, p.measure_connectivity, s.w, s.h);
             d["diameters"] = diameters_dict(sd);
@@ -850,6 +882,7 @@ PYBIND11_MODULE(_nm03, m) {
           } else {
             d["measure_json"] = golden::measure_json(sm, s, p);
           }
+          if (p.measure_intensity) d["measure_json"] = golden::measure_sidecar(r.dilated, r.region, s, p);
         }
         return d;
       },
@@ -982,11 +1015,15 @@ PYBIND11_MODULE(_nm03, m) {
   m.def(
       "measure_to_json",
       [](const py::dict& rec, int w, int h, float sx, float sy, float slope, float intercept, bool apply_rescale,
-         int connectivity) {
+         int connectivity, const py::object& intensity) {
+        if (!intensity.is_none())  // the text with the intensity keys (an IntensityStats dict)
+          return measure::to_json(measure_from(rec), intensity_from(intensity.cast<py::dict>()), w, h, sx, sy, slope, intercept,
+                                  apply_rescale, connectivity);
         return measure::to_json(measure_from(rec), w, h, sx, sy, slope, intercept, apply_rescale, connectivity);
       },
       py::arg("record"), py::arg("w"), py::arg("h"), py::arg("spacing_x") = 1.f, py::arg("spacing_y") = 1.f,
-      py::arg("slope") = 1.f, py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 8);
+      py::arg("slope") = 1.f, py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 8,
+      py::arg("intensity") = py::none());
 
   // The diameter record (nm03/measure.h SliceDiameters) of a mask [H, W] from the golden model.
   m.def(
@@ -1000,13 +1037,16 @@ PYBIND11_MODULE(_nm03, m) {
   m.def(
       "measure_diameters_to_json",
       [](const py::dict& rec, const py::dict& diam, int w, int h, float sx, float sy, float slope, float intercept,
-         bool apply_rescale, int connectivity) {
+         bool apply_rescale, int connectivity, const py::object& intensity) {
+        if (!intensity.is_none())
+          return measure::to_json(measure_from(rec), diameters_from(diam), intensity_from(intensity.cast<py::dict>()), w, h, sx,
+                                  sy, slope, intercept, apply_rescale, connectivity);
         return measure::to_json(measure_from(rec), diameters_from(diam), w, h, sx, sy, slope, intercept, apply_rescale,
                                 connectivity);
       },
       py::arg("record"), py::arg("diameters"), py::arg("w"), py::arg("h"), py::arg("spacing_x") = 1.f,
       py::arg("spacing_y") = 1.f, py::arg("slope") = 1.f, py::arg("intercept") = 0.f, py::arg("apply_rescale") = true,
-      py::arg("connectivity") = 8);
+      py::arg("connectivity") = 8, py::arg("intensity") = py::none());
 
   // ---- volume measurements (nm03/measure.h VolumeMeasure) ----------------------------------------------
   auto volume_arrays = [](const py::array_t<uint8_t, py::array::c_style | py::array::forcecast>& dil,
@@ -1066,16 +1106,26 @@ PYBIND11_MODULE(_nm03, m) {
   m.def(
       "volume_measure_to_json",
       [](const py::dict& rec, int w, int h, int d, double sx, double sy, double sz, const std::string& source, float slope,
-         float intercept, bool apply_rescale, int connectivity, const py::object& lesions, int lesions_max) {
+         float intercept, bool apply_rescale, int connectivity, const py::object& lesions, int lesions_max,
+         const py::object& intensity) {
         // Pixel spacings pass through float, as VolumeInput holds them.
-        if (lesions.is_none())
+        if (lesions.is_none()) {
+          if (!intensity.is_none())  // the text with the intensity keys (an IntensityStats dict)
+            return measure::volume_to_json(volume_measure_from(rec), intensity_from(intensity.cast<py::dict>()), w, h, d,
+                                           (double)(float)sx, (double)(float)sy, sz, source, slope, intercept, apply_rescale,
+                                           connectivity);
           return measure::volume_to_json(volume_measure_from(rec), w, h, d, (double)(float)sx, (double)(float)sy, sz, source,
                                          slope, intercept, apply_rescale, connectivity);
+        }
         // With `lesions` (a list of lesion dicts, as many as are reported): the text with the lesion keys.
         std::vector<VolumeLesion> ls;
         for (const py::handle& l : lesions.cast<py::list>()) ls.push_back(volume_lesion_from(l.cast<py::dict>()));
         check_max_lesions(lesions_max);
         if (ls.size() > (size_t)lesions_max) throw std::invalid_argument("more lesions than lesions_max");
+        if (!intensity.is_none())
+          return measure::volume_to_json(volume_measure_from(rec), intensity_from(intensity.cast<py::dict>()), ls.data(),
+                                         (int)ls.size(), lesions_max, w, h, d, (double)(float)sx, (double)(float)sy, sz, source,
+                                         slope, intercept, apply_rescale, connectivity);
         return measure::volume_to_json(volume_measure_from(rec), ls.data(), (int)ls.size(), lesions_max, w, h, d,
                                        (double)(float)sx, (double)(float)sy, sz, source, slope, intercept, apply_rescale,
                                        connectivity);
@@ -1083,7 +1133,7 @@ PYBIND11_MODULE(_nm03, m) {
       py::arg("record"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_x") = 1.0, py::arg("spacing_y") = 1.0,
       py::arg("spacing_z") = 1.0, py::arg("spacing_z_source") = "default", py::arg("slope") = 1.f,
       py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 26,
-      py::arg("lesions") = py::none(), py::arg("lesions_max") = 0);
+      py::arg("lesions") = py::none(), py::arg("lesions_max") = 0, py::arg("intensity") = py::none());
   // The N largest components of a volume mask (nm03/measure.h VolumeLesion) by the golden model (flood
   // fill per component) → list of dicts of the records' integers, largest first.
   m.def(
@@ -1121,6 +1171,66 @@ PYBIND11_MODULE(_nm03, m) {
       py::arg("dilated"), py::arg("raw"), py::arg("max_lesions"), py::arg("type") = "u16", py::arg("stored_bits") = 16,
       py::arg("connectivity") = 26);
   m.attr("MAX_VOLUME_LESIONS") = kMaxVolumeLesions;
+
+  // ---- intensity statistics (nm03/measure.h IntensityStats) ----------------------------------------------
+  // The nearest rank of percentile p among n samples (nm03/intensity_core.h) and the raw standard
+  // deviation of a record (the exact 128-bit radicand), as the sidecar text uses them.
+  m.def("intensity_rank", [](uint32_t p, uint64_t n) { return icore::percentile_rank(p, n); });
+  m.def("intensity_std", [](const py::dict& rec, int64_t raw_sum) { return measure::intensity_std(intensity_from(rec), raw_sum); });
+  // The golden model (collect, sort, index) on a mask [H, W] and its 16-bit samples.
+  m.def(
+      "golden_measure_intensity",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+         py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, const std::string& type, int stored_bits) {
+        if (dil.ndim() != 2 || raw.ndim() != 2 || raw.shape(0) != dil.shape(0) || raw.shape(1) != dil.shape(1))
+          throw std::invalid_argument("dilated and raw must be [H, W] of one shape");
+        const golden::SliceInput s = slice_from(raw, type, stored_bits, 1.f, 0.f, 1.f, 1.f);
+        return intensity_dict(golden::measure_intensity(from_np<uint8_t>(dil), s));
+      },
+      py::arg("dilated"), py::arg("raw"), py::arg("type") = "u16", py::arg("stored_bits") = 16);
+  m.def(
+      "golden_measure_volume_intensity",
+      [volume_arrays](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+                      py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, const std::string& type,
+                      int stored_bits) {
+        const VolumeInput v = volume_arrays(dil, dil, raw, type, stored_bits);
+        return intensity_dict(golden::measure_intensity(from_np<uint8_t>(dil), v));
+      },
+      py::arg("dilated"), py::arg("raw"), py::arg("type") = "u16", py::arg("stored_bits") = 16);
+  // The same records from the K11 kernels' two-pass radix select run on the host over bit planes
+  // (measure::intensity_words). `stray_bits`: also set every storage bit past the width, which must not count.
+  m.def(
+      "intensity_words",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+         py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, const std::string& type, int stored_bits,
+         bool stray_bits) {
+        if (dil.ndim() != 2 || raw.ndim() != 2 || raw.shape(0) != dil.shape(0) || raw.shape(1) != dil.shape(1))
+          throw std::invalid_argument("dilated and raw must be [H, W] of one shape");
+        const golden::SliceInput s = slice_from(raw, type, stored_bits, 1.f, 0.f, 1.f, 1.f);
+        const int wpr = (s.w + 63) / 64;
+        std::vector<uint64_t> plane((size_t)s.h * wpr, 0ull);
+        auto a = dil.unchecked<2>();
+        for (int y = 0; y < s.h; ++y) {
+          for (int x = 0; x < s.w; ++x)
+            if (a(y, x)) plane[(size_t)y * wpr + (x >> 6)] |= 1ull << (x & 63);
+          if (stray_bits) plane[(size_t)y * wpr + wpr - 1] |= ~row_word_mask(wpr - 1, s.w);
+        }
+        return intensity_dict(measure::intensity_words(plane.data(), s.raw.data(), (size_t)s.w * s.h, s.w, s.h, 1, wpr,
+                                                       (uint8_t)s.type, (uint8_t)s.stored_bits));
+      },
+      py::arg("dilated"), py::arg("raw"), py::arg("type") = "u16", py::arg("stored_bits") = 16,
+      py::arg("stray_bits") = false);
+  m.def(
+      "volume_intensity_words",
+      [volume_arrays](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+                      py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, const std::string& type,
+                      int stored_bits) {
+        const VolumeInput v = volume_arrays(dil, dil, raw, type, stored_bits);
+        const std::vector<uint64_t> dw = pack_volume(dil);
+        return intensity_dict(measure::intensity_words(dw.data(), v.raw.data(), (size_t)v.w * v.h, v.w, v.h, v.d,
+                                                       (v.w + 63) / 64, (uint8_t)v.type, (uint8_t)v.stored_bits));
+      },
+      py::arg("dilated"), py::arg("raw"), py::arg("type") = "u16", py::arg("stored_bits") = 16);
 
   // ---- JPEG --------------------------------------------------------------------------------------
   m.def("jpeg_encode_gray420", [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> g, int quality) {
@@ -1313,6 +1423,7 @@ PYBIND11_MODULE(_nm03, m) {
                d["measure"] = measure_dict(r.measure);
                d["measure_json"] = r.measure_json;
                if (e.config().pipe.measure_diameters) d["diameters"] = diameters_dict(r.diameters);
+               if (e.config().pipe.measure_intensity) d["intensity"] = intensity_dict(r.intensity);
              }
              return d;
            },
@@ -1345,9 +1456,10 @@ PYBIND11_MODULE(_nm03, m) {
              const PipelineParams& p, int connectivity, int dilation,
              const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_connectivity,
              const std::vector<double>& spacing, const std::string& spacing_z_source, const std::string& type,
-             int stored_bits, float slope, float intercept, int measure_lesions) {
+             int stored_bits, float slope, float intercept, int measure_lesions, bool measure_intensity) {
             VolumeMeta mt;
             mt.measure_lesions = measure_lesions;
+            mt.measure_intensity = measure_intensity;
             mt.type = type;
             mt.stored_bits = stored_bits;
             mt.slope = slope;
@@ -1364,7 +1476,7 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("measure") = false, py::arg("measure_connectivity") = 26,
           py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0}, py::arg("spacing_z_source") = "default",
           py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f, py::arg("intercept") = 0.f,
-          py::arg("measure_lesions") = 0)
+          py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false)
       .def(
           "run_slab",
           // One rank's z-slab (planes [z0, z0 + slab depth) of a `depth`-deep volume) through the
@@ -1372,11 +1484,12 @@ PYBIND11_MODULE(_nm03, m) {
           // coordinates. Returns the slab's masks plus rounds / exchanged bytes.
           [](VolumeRunner& self, Comm& comm, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> slab,
              int z0, int depth, const PipelineParams& p, int connectivity, int dilation,
-             const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_lesions) {
+             const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_lesions, bool measure_intensity) {
             SlabStats st;
             VolumeMeta mt;
             mt.measure = measure;  // refused by run_slab (std::invalid_argument) before anything is launched
             mt.measure_lesions = measure_lesions;  // alike
+            mt.measure_intensity = measure_intensity;
             py::dict d = volume_call(slab, p, connectivity, dilation, seeds,
                                      [&](const VolumeInput& v, const VolumeParams& vp) {
                                        return self.run_slab(comm, v, z0, depth, vp, true, &st);
@@ -1388,7 +1501,7 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("comm"), py::arg("slab"), py::arg("z0"), py::arg("depth"), py::arg("params") = PipelineParams(),
           py::arg("connectivity") = 6, py::arg("dilation") = 7,
           py::arg("seeds") = std::vector<std::tuple<int, int, int>>{}, py::arg("measure") = false,
-          py::arg("measure_lesions") = 0);
+          py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false);
 
   // One-process rehearsal of the z-slab decomposition: `nranks` threads, each with its own
   // VolumeRunner (stream) on `device`, talking over loopback comms — the device-resident exchange
@@ -2056,6 +2169,98 @@ PYBIND11_MODULE(_nm03, m) {
     return py::make_tuple(volume_measure_dict(res), volume_lesion_list(les.data(), count));
   }, py::arg("dilated"), py::arg("region"), py::arg("raw"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("max_lesions"),
      py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("connectivity") = 26, py::arg("stream") = 0);
+
+  // K11 on a batch of masks of ANY sizes in one launch: planes = the masks' bit planes back to back
+  // (mask i: hs[i] × ceil(ws[i] / 64) words); raw = the slices' u16 samples back to back; one pixel type
+  // and stored_bits per mask (the descriptors carry them). Returns one intensity record dict per mask.
+  m.def("k_measure_intensity", [](uintptr_t planes, uintptr_t raw, const std::vector<int>& hs, const std::vector<int>& ws,
+                                  const std::vector<std::string>& types, const std::vector<int>& stored_bits,
+                                  uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    const int n = (int)hs.size();
+    if (n <= 0 || ws.size() != hs.size()) throw std::invalid_argument("one height and one width per mask");
+    if (types.size() != hs.size() || stored_bits.size() != hs.size())
+      throw std::invalid_argument("one pixel type and one stored_bits per mask");
+    for (int b : stored_bits)
+      if (b < 1 || b > 16) throw std::invalid_argument("stored_bits must be 1..16");
+    {
+      // K11's code object, loaded on the current device before this op's first launch there.
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_measure_intensity();
+        preloaded.push_back(dev);
+      }
+    }
+    std::vector<gpu::SliceDesc> d((size_t)n);
+    size_t raw_off = 0, mask_off = 0;
+    for (int i = 0; i < n; ++i) {
+      const int h = hs[(size_t)i], w = ws[(size_t)i];
+      if (w <= 0 || h <= 0 || w > gpu::kMaxSliceDim || h > gpu::kMaxSliceDim) throw std::invalid_argument("bad mask size");
+      gpu::SliceDesc& s = d[(size_t)i];
+      std::memset(&s, 0, sizeof(s));
+      s.raw_off = (uint32_t)raw_off;
+      s.mask_off = (uint32_t)mask_off;
+      s.w = (uint16_t)w;
+      s.h = (uint16_t)h;
+      s.wpr = (uint16_t)((w + 63) / 64);
+      const PixelType pt = parse_type(types[(size_t)i]);
+      s.type = pt == kU8 ? kU16 : pt;
+      s.stored_bits = (uint8_t)stored_bits[(size_t)i];
+      raw_off += (size_t)h * w;
+      mask_off += (size_t)h * s.wpr;
+    }
+    if (raw_off > 0xFFFFFFFFull) throw std::invalid_argument("batch exceeds 2^32 samples");
+    const size_t o_desc = 0, o_out = (sizeof(gpu::SliceDesc) * n + 255) / 256 * 256, total = o_out + sizeof(IntensityStats) * n;
+    uint8_t* dev = (uint8_t*)scratch().get(total);
+    gpu::check_hip(hipMemcpyAsync(dev + o_desc, d.data(), sizeof(gpu::SliceDesc) * n, hipMemcpyHostToDevice, st), "H2D descriptors");
+    gpu::check_hip(hipStreamSynchronize(st), "sync descriptors");
+    gpu::launch_measure_intensity((const uint64_t*)planes, (const uint16_t*)raw, (const gpu::SliceDesc*)(dev + o_desc), n,
+                                  (IntensityStats*)(dev + o_out), st);
+    std::vector<IntensityStats> res((size_t)n);
+    gpu::check_hip(hipMemcpyAsync(res.data(), dev + o_out, sizeof(IntensityStats) * n, hipMemcpyDeviceToHost, st), "D2H records");
+    gpu::check_hip(hipStreamSynchronize(st), "k_measure_intensity");
+    py::list out;
+    for (auto& r : res) out.append(intensity_dict(r));
+    return out;
+  }, py::arg("planes"), py::arg("raw"), py::arg("hs"), py::arg("ws"), py::arg("types"), py::arg("stored_bits"),
+     py::arg("stream") = 0);
+
+  // K11's five 3D launches on a bit volume [d][h][ceil(w/64)] (int64 words) and the 16-bit samples `raw`
+  // [d][h][w]. Returns the record dict. Synchronous on `stream`.
+  m.def("k_measure_volume_intensity", [](uintptr_t dilated, uintptr_t raw, int w, int h, int d, const std::string& type,
+                                         int stored_bits, uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    if (stored_bits < 1 || stored_bits > 16) throw std::invalid_argument("stored_bits must be 1..16");
+    if (w <= 0 || h <= 0 || d <= 0) throw std::invalid_argument("empty volume");
+    if (gpu::volume_measure_scratch_words(w, h, d) == 0)
+      throw std::invalid_argument("volume too large to measure: (w + 1) * h * d + 1 must stay below 2^32");
+    const PixelType pt = parse_type(type);
+    {
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_volume_intensity();
+        preloaded.push_back(dev);
+      }
+    }
+    const size_t o_out = 0, o_acc = 256, total = o_acc + gpu::kVolumeIntensityAccBytes;
+    uint8_t* dev = (uint8_t*)scratch().get(total);
+    gpu::launch_volume_intensity((const uint64_t*)dilated, (const uint16_t*)raw, (size_t)w * h, w, h, d,
+                                 (uint8_t)(pt == kU8 ? kU16 : pt), (uint8_t)stored_bits, dev + o_acc,
+                                 (IntensityStats*)(dev + o_out), st);
+    IntensityStats res;
+    gpu::check_hip(hipMemcpyAsync(&res, dev + o_out, sizeof(IntensityStats), hipMemcpyDeviceToHost, st), "D2H record");
+    gpu::check_hip(hipStreamSynchronize(st), "k_measure_volume_intensity");
+    return intensity_dict(res);
+  }, py::arg("dilated"), py::arg("raw"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("type") = "u16",
+     py::arg("stored_bits") = 16, py::arg("stream") = 0);
 
   // ---- comm self-tests (CPU) ------------------------------------------------------------------------
   m.def("loopback_selftest", [](int n) {

@@ -171,6 +171,9 @@ struct Slot {
   // Diameters (PipelineParams::measure_diameters; null without it): K9's host-mapped records.
   SliceDiameters* h_diam = nullptr;
   SliceDiameters* d_diam = nullptr;
+  // Intensity statistics (PipelineParams::measure_intensity; null without it): K11's host-mapped records.
+  IntensityStats* h_intensity = nullptr;
+  IntensityStats* d_intensity = nullptr;
 };
 
 // Private fd tables for the host pool's workers. Every open and
@@ -243,6 +246,7 @@ void hip_free_all(Slot& s) {
   if (s.h_ov_sizes) (void)hipHostFree(s.h_ov_sizes);
   if (s.h_measure) (void)hipHostFree(s.h_measure);
   if (s.h_diam) (void)hipHostFree(s.h_diam);
+  if (s.h_intensity) (void)hipHostFree(s.h_intensity);
   if (s.d_ms_scratch) (void)hipFree(s.d_ms_scratch);
   for (void* p : {(void*)s.d_rgb, (void*)s.ov_jw.look, (void*)s.ov_jw.ticket, (void*)s.ov_jw.spill, (void*)s.d_ov_jd})
     if (p) (void)hipFree(p);
@@ -327,6 +331,8 @@ struct Engine::Impl {
                 ((uint32_t)cfg.render.overlay_color[2] << 16);
     diameters_ = cfg.pipe.measure_diameters;
     if (diameters_) cfg.pipe.measure = true;  // the diameters are measured on K7's labelling
+    intensity_ = cfg.pipe.measure_intensity;
+    if (intensity_) cfg.pipe.measure = true;  // the intensity keys extend K7's sidecar (raw_sum enters std)
     measure_ = cfg.pipe.measure;
     if (measure_ && cfg.host_only)
       throw std::invalid_argument("measure runs on the GPU (the K7 kernel): not available with host_only");
@@ -390,6 +396,7 @@ struct Engine::Impl {
       if (overlay_) preload_jpeg_rgb();
       if (measure_) preload_measure();  // likewise: only an engine that will launch K7 loads it
       if (diameters_) preload_measure_diameters();  // and K9
+      if (intensity_) preload_measure_intensity();  // and K11
       d_lut_ = dmalloc<float>(kLutArenaFloats, "hipMalloc norm tables");
     }
     const double t1 = now_s();
@@ -771,6 +778,12 @@ struct Engine::Impl {
         check_hip(hipHostMalloc((void**)&s.h_diam, sizeof(SliceDiameters) * n, hipHostMallocMapped), "hipHostMalloc diameters");
         check_hip(hipHostGetDevicePointer((void**)&s.d_diam, s.h_diam, 0), "hipHostGetDevicePointer diameters");
         mark("diameters");
+      }
+      if (intensity_) {
+        const int n = s.cap_slices;
+        check_hip(hipHostMalloc((void**)&s.h_intensity, sizeof(IntensityStats) * n, hipHostMallocMapped), "hipHostMalloc intensity");
+        check_hip(hipHostGetDevicePointer((void**)&s.d_intensity, s.h_intensity, 0), "hipHostGetDevicePointer intensity");
+        mark("intensity");
       }
     } catch (...) {
       hip_free_all(s);
@@ -1225,6 +1238,7 @@ struct Engine::Impl {
                      s.d_ms_scratch, s.max_w, s.max_h, s.stream);
     if (diameters_)
       launch_measure_diameters(plane(kPDilated), d_desc, nl, s.d_diam, s.d_ms_scratch, s.max_w, s.max_h, s.stream);
+    if (intensity_) launch_measure_intensity(plane(kPDilated), d_raw, d_desc, nl, s.d_intensity, s.stream);
     if (s.any_canvas) launch_render(d_raw, s.d_f32, s.d_bits, d_stats, d_rd, ncanv, cw, ch, s.d_canvas, s.stream);
     JpegRenderSrc rsrc;
     rsrc.raw = d_raw;
@@ -1304,9 +1318,15 @@ struct Engine::Impl {
     if (diameters_) {
       const SliceDiameters& dm = s.h_diam[c];
       if (dm.lesion_px == kDiametersNotMeasured) throw DeviceError("measure: slice exceeds the measurement scratch");
+      if (intensity_)
+        return measure::to_json(m, dm, s.h_intensity[c], L.w, L.h, L.sx, L.sy, L.slope, L.intercept, cfg.pipe.apply_rescale,
+                                cfg.pipe.measure_connectivity);
       return measure::to_json(m, dm, L.w, L.h, L.sx, L.sy, L.slope, L.intercept, cfg.pipe.apply_rescale,
                               cfg.pipe.measure_connectivity);
     }
+    if (intensity_)
+      return measure::to_json(m, s.h_intensity[c], L.w, L.h, L.sx, L.sy, L.slope, L.intercept, cfg.pipe.apply_rescale,
+                              cfg.pipe.measure_connectivity);
     return measure::to_json(m, L.w, L.h, L.sx, L.sy, L.slope, L.intercept, cfg.pipe.apply_rescale,
                             cfg.pipe.measure_connectivity);
   }
@@ -1841,6 +1861,7 @@ struct Engine::Impl {
     if (measure_) {
       r.measure = s.h_measure[0];
       if (diameters_) r.diameters = s.h_diam[0];
+      if (intensity_) r.intensity = s.h_intensity[0];
       r.measure_json = measure_text(s, 0);
     }
     return r;
@@ -1858,6 +1879,7 @@ struct Engine::Impl {
   bool measure_ = false;
   // Diameters (PipelineParams::measure_diameters): K9 after K7, further keys in the sidecar.
   bool diameters_ = false;
+  bool intensity_ = false;
 };
 
 Engine::Engine(const EngineConfig& cfg) : impl_(std::make_unique<Impl>(cfg)) {}

@@ -164,6 +164,10 @@ struct VolumeDevice {
   // allocated by the first run that asks for lesions (for kMaxVolumeLesions, so any N fits) and kept.
   std::unique_ptr<DevBuf> vl_work;
   VolumeLesion* h_lesions = nullptr;  // kMaxVolumeLesions records, then the count
+  // K11 (VolumeParams::measure_intensity): the accumulators and the pinned record, allocated by the
+  // first run that asks for them and kept.
+  std::unique_ptr<DevBuf> vi_acc;
+  IntensityStats* h_intensity = nullptr;
   VolumeDevice(const VolumeInput& v)
       : w(v.w), h(v.h), d(v.d), wpr((v.w + 63) / 64), words((size_t)v.h * ((v.w + 63) / 64)),
         ps(((size_t)v.w * v.h + 7) / 8 * 8),
@@ -185,6 +189,7 @@ struct VolumeDevice {
   }
   ~VolumeDevice() {
     if (h_lesions) (void)hipHostFree(h_lesions);
+    if (h_intensity) (void)hipHostFree(h_intensity);
     if (h_measure) (void)hipHostFree(h_measure);
     if (h_tables) (void)hipHostFree(h_tables);
     if (h_flag) (void)hipHostFree(h_flag);
@@ -339,6 +344,7 @@ struct VolumeRunner::Impl {
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   bool measure_loaded = false;  // K8's code object (first measuring run)
   bool lesions_loaded = false;  // K10's code object (first run that asks for lesions)
+  bool intensity_loaded = false;  // K11's code object (first run that asks for the intensity statistics)
   explicit Impl(int dev) : device(dev) {
     check_hip(hipSetDevice(device), "hipSetDevice");
     preload_kernels();  // every code object, before the first launch (kernels.h)
@@ -375,6 +381,7 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
   if (p.measure_lesions < 0 || p.measure_lesions > kMaxVolumeLesions)
     throw std::invalid_argument("3D lesion count must be in [1, " + std::to_string(kMaxVolumeLesions) + "] (got " +
                                 std::to_string(p.measure_lesions) + ")");
+  if (p.measure_intensity && !p.measure) throw std::invalid_argument("3D intensity statistics need measure");
   if (p.measure) {
     if (p.measure_connectivity != 6 && p.measure_connectivity != 26)
       throw std::invalid_argument("3D measurement connectivity must be 6 or 26 (got " +
@@ -405,6 +412,16 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
                   "hipHostMalloc lesions");
       }
     }
+    if (p.measure_intensity) {  // K11 alike
+      if (!I.intensity_loaded) {
+        preload_volume_intensity();
+        I.intensity_loaded = true;
+      }
+      if (!V.vi_acc) {
+        V.vi_acc = std::make_unique<DevBuf>(kVolumeIntensityAccBytes);
+        check_hip(hipHostMalloc((void**)&V.h_intensity, sizeof(IntensityStats), hipHostMallocDefault), "hipHostMalloc intensity");
+      }
+    }
   }
   const PipeConsts pc = make_consts(p.pipe, 2);
   check_hip(hipEventRecord(I.e0, V.stream), "event");
@@ -426,9 +443,13 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
     launch_volume_measure(V.dil.as<uint64_t>(), V.region.as<uint64_t>(), V.raw.as<uint16_t>(), V.ps, v.w, v.h, v.d,
                           (uint8_t)v.type, (uint8_t)v.stored_bits, p.measure_connectivity, V.vm_scratch->as<uint32_t>(),
                           V.vm_acc->as<uint64_t>(), V.h_measure, V.stream, p.measure_lesions ? &lw : nullptr);
+    if (p.measure_intensity)  // K11's five launches after K8's last one
+      launch_volume_intensity(V.dil.as<uint64_t>(), V.raw.as<uint16_t>(), V.ps, v.w, v.h, v.d, (uint8_t)v.type,
+                              (uint8_t)v.stored_bits, V.vi_acc->p, V.h_intensity, V.stream);
     check_hip(hipEventRecord(I.e2, V.stream), "event");
     check_hip(hipEventSynchronize(I.e2), "sync");
     r.measure = *V.h_measure;
+    if (p.measure_intensity) r.intensity = *V.h_intensity;
     if (p.measure_lesions) {
       const uint32_t count = *lw.out_count;
       if (count > (uint32_t)p.measure_lesions) throw DeviceError("volume lesions: count out of range");
@@ -582,7 +603,7 @@ static SlabStats slab_grow_dilate_gpu(Comm& comm, VolumeDevice& V, int nseeds, i
 VolumeResult VolumeRunner::run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p,
                                     bool want_masks, SlabStats* stats) {
   if (slab.d < 1 || slab.w < 1 || slab.h < 1) throw SliceError("empty slab");
-  if (p.measure || p.measure_lesions)
+  if (p.measure || p.measure_lesions || p.measure_intensity)
     throw std::invalid_argument("run_slab: measuring a volume split into slabs is not supported "
                                 "(components that cross slabs need a collective)");
   check_volume_params(p.connectivity, p.dilation_size);
@@ -873,7 +894,8 @@ std::vector<std::vector<uint8_t>> golden_export(const VolumeInput& v, const std:
 // with vp.measure_lesions the lesion records in `lesions`.
 std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, const VolumeParams& vp,
                                                       const RenderParams& rp, VolumeMeasure* measured = nullptr,
-                                                      std::vector<VolumeLesion>* lesions = nullptr) {
+                                                      std::vector<VolumeLesion>* lesions = nullptr,
+                                                      IntensityStats* intensity = nullptr) {
   const GoldenPlanes gp = golden_preprocess(v, vp);
   std::vector<Seed> seeds = vp.seeds;
   if (seeds.empty()) {
@@ -885,6 +907,7 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
   if (measured) *measured = golden::measure_volume(dil, region, v, vp.measure_connectivity);
   if (measured && lesions && vp.measure_lesions)
     *lesions = golden::measure_volume_lesions(dil, v, vp.measure_connectivity, vp.measure_lesions);
+  if (measured && intensity && vp.measure_intensity) *intensity = golden::measure_intensity(dil, v);
   return golden_export(v, gp.vals, dil, rp);
 }
 
@@ -912,6 +935,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
   vp.measure = cfg.measure_volume;
   vp.measure_connectivity = cfg.measure_volume_connectivity;
   vp.measure_lesions = cfg.measure_volume_lesions;
+  vp.measure_intensity = cfg.measure_volume_intensity;
   const RenderParams& rp = cfg.engine.render;
   const double t_start = wall_now();
   // ---- plan on rank 0 -----------------------------------------------------------------------
@@ -1045,8 +1069,9 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       std::vector<std::vector<uint8_t>> files;
       VolumeMeasure measured = {};
       std::vector<VolumeLesion> lesions;
+      IntensityStats intensity = {};
       if (cfg.cpu) {
-        files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions);
+        files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions, &intensity);
       } else {
         VolumeResult r = runner->run(v, vp, false);
         o.sweeps = r.sweeps;
@@ -1054,6 +1079,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         o.measure_s = r.measure_s;
         measured = r.measure;
         lesions = std::move(r.lesions);
+        intensity = r.intensity;
         VolumeExportStats xs;
         files = runner->export_jpegs(v, vp, rp, &xs);
         o.export_s = xs.export_s;
@@ -1061,7 +1087,10 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       }
       write_planes(pp, 0, v.d, files);
       if (vp.measure) {  // the sidecar next to the planes; its text travels to rank 0 for the table
-        o.measure_json = vp.measure_lesions
+        o.measure_json = vp.measure_intensity
+                             ? golden::measure_volume_json(measured, intensity, vp.measure_lesions ? &lesions : nullptr,
+                                                           vp.measure_lesions, v, vp.pipe.apply_rescale, vp.measure_connectivity)
+                         : vp.measure_lesions
                              ? golden::measure_volume_json(measured, lesions, vp.measure_lesions, v, vp.pipe.apply_rescale,
                                                            vp.measure_connectivity)
                              : golden::measure_volume_json(measured, v, vp.pipe.apply_rescale, vp.measure_connectivity);
@@ -1188,7 +1217,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
     std::vector<VolumePatientRow> rows;
     for (size_t i = 0; i < plan.size(); ++i) rows.push_back({plan[i].id, outs[i].ok != 0, outs[i].measure_json});
     try {
-      volume_totals = write_volumes_csv(cfg.out_dir, rows);
+      volume_totals = write_volumes_csv(cfg.out_dir, rows, cfg.measure_volume_intensity);
     } catch (const std::exception& e) {
       std::cerr << "Error writing volumes.csv: " << e.what() << std::endl;
     }
