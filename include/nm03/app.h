@@ -99,6 +99,10 @@ struct AppConfig {
   // also carry the intensity keys (nm03/measure.h IntensityStats). In 2D the flag is
   // engine.pipe.measure_intensity.
   bool measure_volume_intensity = false;
+  // --measure-texture with --mode 3d (implies --measure-volume): the volume sidecar and volumes.csv also
+  // carry the texture keys (nm03/texture_core.h) at engine.pipe.texture_levels grey levels
+  // (--texture-levels). In 2D the flag is engine.pipe.measure_texture.
+  bool measure_volume_texture = false;
   // CLOCK_REALTIME when parse_args began (the --json record's "main_unix_s"): with the launcher's
   // own clock it splits a cold run's wall into process start-up (exec → main) and the rest.
   double main_unix_s = 0;
@@ -154,6 +158,7 @@ struct MeasureTotals {
   bool diameters = false;
   double bidimensional_mm2_max = 0;
   bool intensity = false;  // --measure-intensity: the table has the intensity columns
+  int texture_levels = 0;  // --measure-texture: the table has the texture columns (0: not asked for)
 };
 // `diameters` (--measure-diameters): the table also has the diameter keys' columns after `mean`
 // (lesion_first, major and perp flattened), and a patient's TOTAL row carries the patient's largest
@@ -161,8 +166,10 @@ struct MeasureTotals {
 // slice has a lesion). A sidecar written earlier without the flag (--resume) leaves those columns empty.
 // `intensity` (--measure-intensity): the 13 intensity keys' columns after all the others; TOTAL rows leave
 // them empty, and so does a sidecar written earlier without the flag.
+// `texture_levels` (--measure-texture; 0 = off): the 23 texture keys' columns after all of those, under
+// the same rules.
 MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients,
-                                     bool diameters = false, bool intensity = false);
+                                     bool diameters = false, bool intensity = false, int texture_levels = 0);
 std::string measure_totals_json(const MeasureTotals& t);  // the --json record's "measure" object
 const char* slice_status_name(int code);
 
@@ -180,11 +187,13 @@ struct VolumeTotals {
   double volume_mm3 = 0;
   int64_t lesions = -1;  // --measure-volume-lesions: rows of lesions.csv over the job's measured patients (−1: not asked for)
   bool intensity = false;  // --measure-intensity: the table has the intensity columns
+  int texture_levels = 0;  // --measure-texture: the table has the texture columns (0: not asked for)
 };
 // `intensity` (--measure-intensity): the 13 intensity keys' columns after `mean`; a sidecar without them
 // (written earlier without the flag) leaves them empty.
+// `texture_levels` (--measure-texture; 0 = off): the 23 texture keys' columns after those, alike.
 VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows,
-                               bool intensity = false);
+                               bool intensity = false, int texture_levels = 0);
 // --measure-volume-lesions: <out_root>/lesions.csv from the same sidecar texts, in plan order: a header,
 // then one row per reported lesion (patient, lesion = its 0-based rank, then the lesion object's fields
 // with first and bbox flattened); a failed patient has one row with its status name in `lesion` and

@@ -132,6 +132,8 @@ struct SingleResult {
   SliceDiameters diameters{};
   // PipelineParams::measure_intensity only: the K11 record (measure_json then carries its keys too).
   IntensityStats intensity{};
+  // PipelineParams::measure_texture only: the K12 record (measure_json then carries its keys too).
+  measure::Glcm texture;
 };
 
 struct RunHandle;  // a submitted run (Engine::submit)

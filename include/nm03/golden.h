@@ -109,7 +109,8 @@ SliceDiameters measure_diameters(const std::vector<uint8_t>& dilated, int connec
 std::string measure_json(const SliceMeasure& m, const SliceDiameters& d, const SliceInput& s, const PipelineParams& p);
 // The sidecar text the --cpu paths write for slice `s`: measure() and, with p.measure_diameters,
 // measure_diameters() at p.measure_connectivity, through the matching measure_json; with
-// p.measure_intensity also measure_intensity(), its keys after all the others.
+// p.measure_intensity also measure_intensity(), its keys after all the others; with p.measure_texture
+// also measure_texture() at p.texture_levels, its keys after those.
 std::string measure_sidecar(const std::vector<uint8_t>& dilated, const std::vector<uint8_t>& region, const SliceInput& s,
                             const PipelineParams& p);
 
@@ -123,6 +124,19 @@ IntensityStats measure_intensity(const std::vector<uint8_t>& dilated, const Volu
 // `lesions`: null without --measure-volume-lesions.
 std::string measure_volume_json(const VolumeMeasure& m, const IntensityStats& st, const std::vector<VolumeLesion>* lesions,
                                 int max_lesions, const VolumeInput& v, bool apply_rescale, int connectivity);
+
+// The grey-level co-occurrence matrix (nm03/texture_core.h, nm03/measure.h TextureGlcm) of the stored
+// samples under `dilated` (0/1 per pixel, h × w; the overload below: per voxel, d planes of h × w) at
+// `levels` grey levels. The oracle of the K12 kernels: a plain loop over the voxels and the list of
+// forward directions that adds to C[a][b] and C[b][a] — no words, no shifted masks, no directed counts.
+// It shares only stored_sample, sample_key and tcore::level with the kernels.
+measure::Glcm measure_texture(const std::vector<uint8_t>& dilated, const SliceInput& s, int levels);
+measure::Glcm measure_texture(const std::vector<uint8_t>& dilated, const VolumeInput& v, int levels);
+// The volume sidecar text with the texture keys (measure::volume_to_json with `tx`); `st`, `lesions`:
+// null without --measure-intensity / --measure-volume-lesions.
+std::string measure_volume_json(const VolumeMeasure& m, const IntensityStats* st, const std::vector<VolumeLesion>* lesions,
+                                int max_lesions, const measure::Glcm& tx, const VolumeInput& v, bool apply_rescale,
+                                int connectivity);
 
 // Measurements of a volume (VolumeParams::measure, nm03/measure.h VolumeMeasure): the record on the
 // `dilated` volume plus popcount(`region`) (0/1 per voxel, d planes of h × w), intensities from v.raw.

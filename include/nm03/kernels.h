@@ -262,6 +262,34 @@ void launch_volume_intensity(const uint64_t* dilated, const uint16_t* raw, size_
 void preload_measure_intensity();
 void preload_volume_intensity();
 
+// K12 (k12_texture.hip), 2D: the TextureGlcm record (nm03/measure.h: a 64-byte header, then the
+// levels × levels co-occurrence matrix as uint32) of the samples under every slice's `dilated` plane, one
+// workgroup per slice, slices of different sizes in one launch (SliceDesc as for K11). `slots` null:
+// every slice at `levels` grey levels (2 … 64), record i at out + i · glcm_record_bytes(levels). `slots`
+// given (nslices of them, device memory): slice i at slots[i].levels, its record at 32-bit word
+// slots[i].word_off of `out`; `levels` is not used. It reads what K11 reads and writes nothing but `out`
+// (plain vector stores of 32-bit words; device or host-mapped memory, 4-byte aligned). No global scratch,
+// no host round trip, no allocation.
+struct TextureSlot {
+  uint32_t levels;
+  uint32_t word_off;
+};
+void launch_measure_texture(const uint64_t* dilated, const uint16_t* raw, const SliceDesc* descs, int nslices,
+                            const TextureSlot* slots, int levels, void* out, hipStream_t stream);
+// K12, 3D: the record of the samples under the `dilated` bit volume (laid out as for
+// launch_volume_intensity), thirteen forward directions. Four small launches on `stream` (init, range,
+// histogram, final) separated by kernel boundaries; no host round trip, no allocation. `acc`:
+// kVolumeTextureAccBytes of device memory, no initialisation needed; `out`: glcm_record_bytes(levels),
+// written with plain vector stores (device, pinned or host-mapped memory). Throws DeviceError before any
+// launch for a volume that launch_volume_measure refuses.
+constexpr size_t kVolumeTextureAccBytes = 16 * 16384 + 64;
+void launch_volume_texture(const uint64_t* dilated, const uint16_t* raw, size_t raw_plane_stride, int w, int h, int d,
+                           uint8_t type, uint8_t stored_bits, int levels, void* acc, void* out, hipStream_t stream);
+// Load K12's code object on the current device. Not part of preload_kernels: only an engine or a
+// VolumeRunner built with the feature on and the Python ops (before their first launch) load it.
+void preload_measure_texture();
+void preload_volume_texture();
+
 // K6: binary threshold lo ≤ x ≤ hi → u8 0/1 (in 16-byte aligned, out 4-byte aligned).
 void launch_threshold(const float* in, uint8_t* out, size_t n, float lo, float hi, hipStream_t stream);
 

@@ -10,6 +10,7 @@
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "nm03/common.h"
 
@@ -65,6 +66,25 @@ struct alignas(64) IntensityStats {
   uint32_t pad[7];
 };
 static_assert(sizeof(IntensityStats) == 64, "IntensityStats layout");
+
+// Second-order texture (--measure-texture): the header of the record the K12 kernels write for one slice
+// or one volume; the grey-level co-occurrence matrix C follows it as uint32[levels · levels], row-major
+// (glcm_record_bytes). The definition is in nm03/texture_core.h: the samples are the stored sample
+// values under the DILATED mask, discretised to `levels` grey levels between the smallest and the largest
+// of them; C is merged over the forward directions (4 in 2D, 13 in 3D) and symmetric, Σ C = 2 · pairs.
+// A record may lie at any 4-byte aligned address (odd `levels`): it is written and read as 32-bit words,
+// the 64-bit fields low word first.
+struct TextureGlcm {
+  uint32_t levels;   // Ng
+  uint32_t key_lo;   // icore::sample_key of the smallest sample (0 for an empty mask)
+  uint32_t key_hi;   // … of the largest
+  uint32_t reserved;
+  uint64_t samples;  // voxels under the mask
+  uint64_t pairs;    // voxel pairs counted
+  uint32_t pad[8];
+};
+static_assert(sizeof(TextureGlcm) == 64, "TextureGlcm layout");
+constexpr size_t glcm_record_bytes(int levels) { return sizeof(TextureGlcm) + 4u * (size_t)levels * (size_t)levels; }
 
 // ---------------------------------------------------------------------------------------------
 // Bit quads (Gray 1971). Over every 2×2 window of the zero-padded mask, Q1 / Q3 count the windows
@@ -307,6 +327,48 @@ std::string intensity_keys(const IntensityStats& st, int64_t raw_sum, float slop
 // kernels compute, without a GPU.
 IntensityStats intensity_words(const uint64_t* dilated, const uint16_t* raw, size_t raw_plane_stride, int w, int h, int d,
                                int wpr, uint8_t type, uint8_t stored_bits);
+
+// ---- texture (--measure-texture, nm03/texture_core.h) ------------------------------------------------
+// A record on the host: the header and the matrix.
+struct Glcm {
+  TextureGlcm head = {};
+  std::vector<uint32_t> c;  // levels · levels, row-major
+};
+// A record as the kernels write it (header, then the matrix) read from 32-bit words at `p`.
+Glcm glcm_from_record(const void* p);
+
+// Everything the sidecar derives from a matrix, by ONE function in a fixed loop order (i, then j,
+// row-major), so equal matrices give equal text whoever computed them. With p = C / Σ C and IBSI's
+// 1-based grey levels i, j. The integers first; `any` is false when pairs = 0 and every double is then
+// null in the text; `correlation_defined` is false when joint_var = 0.
+struct GlcmFeatures {
+  uint64_t levels = 0, pairs = 0, nonzero = 0, max_count = 0, sum_abs_d = 0, sum_d2 = 0, sum_sq = 0;
+  bool any = false, correlation_defined = false;
+  double joint_max = 0, joint_avg = 0, joint_var = 0, joint_entropy = 0, asm_ = 0, contrast = 0, dissimilarity = 0,
+         inv_diff = 0, inv_diff_moment = 0, correlation = 0, autocorrelation = 0, cluster_tendency = 0, cluster_shade = 0,
+         cluster_prominence = 0, sum_entropy = 0, diff_entropy = 0;
+};
+GlcmFeatures glcm_features(const uint32_t* c, int levels);
+// The appended keys alone: ",\"glcm_levels\":…" up to glcm_diff_entropy (7 integers, then 16 doubles as %.9g or null).
+std::string texture_keys(const uint32_t* c, int levels);
+// The sidecar texts with --measure-texture: the text of the matching overload without `tx` (d, st, lesions:
+// null for a run without that flag) with the texture keys after all existing keys — in 3D before
+// lesions_max / lesions — so the text before them is byte for byte the text without the flag.
+std::string to_json(const SliceMeasure& m, const SliceDiameters* d, const IntensityStats* st, const Glcm& tx, int w, int h,
+                    float spacing_x, float spacing_y, float slope, float intercept, bool apply_rescale, int connectivity);
+std::string volume_to_json(const VolumeMeasure& m, const IntensityStats* st, const VolumeLesion* lesions, int count,
+                           int lesions_max, const Glcm& tx, int w, int h, int d, double spacing_x, double spacing_y,
+                           double spacing_z, const std::string& spacing_z_source, float slope, float intercept,
+                           bool apply_rescale, int connectivity);
+// `text` (a slice's or a volume's sidecar) with `keys` put after its global keys: before the lesion keys
+// when it has them, else before the closing brace.
+std::string insert_global_keys(std::string text, const std::string& keys);
+
+// The record of the samples under a bit plane or (d > 1) a bit volume, laid out as for intensity_words,
+// computed on the host with K12's per-word pair logic (tcore::neighbour_word over the five partner
+// rows, directed counts, one symmetrisation): what the K12 kernels compute, without a GPU.
+Glcm texture_words(const uint64_t* dilated, const uint16_t* raw, size_t raw_plane_stride, int w, int h, int d, int wpr,
+                   uint8_t type, uint8_t stored_bits, int levels);
 
 // File name of a slice's sidecar next to its JPEGs.
 inline std::string sidecar_name(const std::string& stem) { return stem + "_measure.json"; }

@@ -58,6 +58,11 @@ struct PipelineParams {
   // nm03/measure.h IntensityStats): exact percentiles and Σ v², further keys in the sidecar. Opt-in;
   // implies `measure`.
   bool measure_intensity = false;
+  // Second-order texture of the samples under the dilated mask (--measure-texture, nm03/texture_core.h):
+  // the grey-level co-occurrence matrix at `texture_levels` grey levels (--texture-levels, 2 … 64) and the
+  // features derived from it, further keys in the sidecar. Opt-in; implies `measure`.
+  bool measure_texture = false;
+  int texture_levels = 32;
 };
 
 enum SeShape : int { kSeSquare = 0, kSeDisc = 1 };

@@ -64,6 +64,8 @@ struct VolumeResult {
   std::vector<VolumeLesion> lesions;
   // VolumeParams::measure_intensity: the K11 record of the samples under the dilated volume.
   IntensityStats intensity = {};
+  // VolumeParams::measure_texture: the K12 record of the samples under the dilated volume.
+  measure::Glcm texture;
 };
 
 struct VolumeExportStats {
@@ -84,6 +86,10 @@ struct VolumeParams {
   int measure_lesions = 0;
   // With measure: also the first-order intensity statistics (K11, nm03/measure.h IntensityStats).
   bool measure_intensity = false;
+  // With measure: also the grey-level co-occurrence matrix at `texture_levels` (2 … 64) grey levels over
+  // the thirteen forward directions (K12, nm03/measure.h TextureGlcm).
+  bool measure_texture = false;
+  int texture_levels = 32;
 };
 
 // Runs the 3D pipeline on `device`; copies masks back when `want_masks`. A VolumeRunner keeps
@@ -97,7 +103,8 @@ class VolumeRunner {
   VolumeRunner& operator=(const VolumeRunner&) = delete;
   // With p.measure the K8 kernels run after the segmentation (first use loads their code object and
   // allocates their scratch, kept like the other buffers); without it nothing of K8 is touched. The
-  // same holds for p.measure_lesions and K10, and for p.measure_intensity and K11 (after K8's last launch).
+  // same holds for p.measure_lesions and K10, for p.measure_intensity and K11 (after K8's last launch)
+  // and for p.measure_texture and K12 (after K11's).
   VolumeResult run(const VolumeInput& v, const VolumeParams& p, bool want_masks);
   // After run() on the same volume: the 2·d exported JPEG files of the 3D cohort mode, in plane
   // order (original, processed), rendered and encoded on the GPU (K3/K4) from the volume still on
@@ -109,7 +116,7 @@ class VolumeRunner {
   // coordinates. Preprocesses the slab's planes, runs the global region-growing fixpoint and the
   // halo cube dilation with the other ranks of `comm` (collective), leaving the slab on the device:
   // export_jpegs(slab, ...) then exports its planes. Masks (when requested) are the slab's.
-  // p.measure, p.measure_lesions or p.measure_intensity throws std::invalid_argument: components that cross slabs would
+  // p.measure, p.measure_lesions, p.measure_intensity or p.measure_texture throws std::invalid_argument: components that cross slabs would
   // need a collective.
   VolumeResult run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p, bool want_masks,
                         struct SlabStats* stats = nullptr);

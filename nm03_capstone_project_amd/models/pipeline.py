@@ -44,6 +44,11 @@ class PipelineConfig:
     # exact percentiles (10/25/50/75/90), sum of squares, std and iqr of the samples under the dilated mask
     # in the sidecar (K11); implies `measure`; run_array / golden gain "intensity"
     measure_intensity: bool = False
+    # second-order texture of the samples under the dilated mask (K12): the grey-level co-occurrence matrix at
+    # `texture_levels` grey levels (2..64) and 23 keys derived from it in the sidecar; implies `measure`;
+    # run_array / golden gain "texture" (the header integers plus "glcm", the [levels, levels] uint32 matrix)
+    measure_texture: bool = False
+    texture_levels: int = 32
     # render / export
     out_width: int = 512
     out_height: int = 512
@@ -68,7 +73,7 @@ class PipelineConfig:
     _PIPE = ("norm_low", "norm_high", "norm_min", "norm_max", "clip_min", "clip_max", "median_window",
              "sharpen_gain", "sharpen_sigma", "sharpen_mask", "srg_min", "srg_max", "srg_connectivity",
              "dilation_size", "erosion_size", "min_dim", "apply_rescale", "frame", "se_shape", "measure",
-             "measure_connectivity", "measure_diameters", "measure_intensity")
+             "measure_connectivity", "measure_diameters", "measure_intensity", "measure_texture", "texture_levels")
     _RENDER = ("out_width", "out_height", "label_opacity", "border_opacity", "border_radius", "jpeg_quality",
                "jpeg_sampling")
 
@@ -76,7 +81,9 @@ class PipelineConfig:
         p = native().PipelineParams()
         for k in self._PIPE:
             setattr(p, k, getattr(self, k))
-        p.measure = bool(self.measure or self.measure_diameters or self.measure_intensity)
+        if self.measure_texture and not 2 <= int(self.texture_levels) <= 64:
+            raise ValueError(f"texture_levels must be 2..64 (got {self.texture_levels})")
+        p.measure = bool(self.measure or self.measure_diameters or self.measure_intensity or self.measure_texture)
         return p
 
     def render_params(self):

@@ -11,7 +11,10 @@ CLI's volume_measure.json, from the one native volume_to_json). With `measure_le
 the `lesions_max` / `lesions` keys. With `measure_intensity=True` (needs `measure`) the K11 kernels also
 report the exact 10/25/50/75/90th percentile and the sum of squares of the samples under the dilated
 volume: the result gains `intensity` (the record's integers) and `measure_json` carries the intensity
-keys after `mean` (before the lesion keys)."""
+keys after `mean` (before the lesion keys). With `measure_texture=True` (needs `measure`) the K12 kernels
+also report the grey-level co-occurrence matrix of those samples at `texture_levels` grey levels over the
+thirteen forward directions: the result gains `texture` (the header integers plus `glcm`) and
+`measure_json` carries the 23 texture keys after the intensity keys (before the lesion keys)."""
 import numpy as np
 
 from .._native import native
@@ -26,7 +29,8 @@ def _meta_args(meta):
 
 class VolumePipeline:
     def __init__(self, config: PipelineConfig = None, connectivity: int = 6, dilation: int = 7, measure: bool = False,
-                 measure_connectivity: int = 26, measure_lesions: int = 0, measure_intensity: bool = False):
+                 measure_connectivity: int = 26, measure_lesions: int = 0, measure_intensity: bool = False, measure_texture: bool = False,
+                 texture_levels: int = 32):
         self.config = config or PipelineConfig()
         self.connectivity = connectivity
         self.dilation = dilation
@@ -42,6 +46,12 @@ class VolumePipeline:
         self.measure_intensity = bool(measure_intensity)
         if self.measure_intensity and not self.measure:
             raise ValueError("measure_intensity needs measure=True")
+        self.measure_texture = bool(measure_texture)
+        self.texture_levels = int(texture_levels)
+        if self.measure_texture and not self.measure:
+            raise ValueError("measure_texture needs measure=True")
+        if self.measure_texture and not 2 <= self.texture_levels <= 64:
+            raise ValueError(f"texture_levels must be 2..64 (got {texture_levels})")
         self._runners = {}  # device -> native VolumeRunner (buffers/stream reused across volumes)
 
     def default_seeds(self, volume):
@@ -63,7 +73,8 @@ class VolumePipeline:
         return runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s, measure=self.measure,
                           measure_connectivity=self.measure_connectivity, spacing=[float(v) for v in spacing],
                           spacing_z_source=str(spacing_z_source), measure_lesions=self.measure_lesions,
-                          measure_intensity=self.measure_intensity, **_meta_args(meta))
+                          measure_intensity=self.measure_intensity, measure_texture=self.measure_texture,
+                          texture_levels=self.texture_levels, **_meta_args(meta))
 
     def run_series(self, series_dir, seeds=None, device=None):
         """A DICOM series directory as one volume (utils.read_series: the reference's file-number
@@ -103,7 +114,8 @@ class VolumePipeline:
         what `run` returns under those keys when measuring. With measure_lesions the text is the longer
         one and the tuple has a third member, the list of lesion dicts (`run`'s `lesions`). With
         measure_intensity the text carries the intensity keys and the tuple's last member is the intensity
-        dict (`run`'s `intensity`)."""
+        dict (`run`'s `intensity`). With measure_texture the text carries the texture keys too and the
+        texture dict (`run`'s `texture`) comes last of all."""
         n = native()
         a = _meta_args(meta)
         d, h, w = np.asarray(dilated).shape
@@ -120,6 +132,17 @@ class VolumePipeline:
                                         str(spacing_z_source), a["slope"], a["intercept"],
                                         bool(self.config.pipeline_params().apply_rescale), self.measure_connectivity,
                                         lesions, self.measure_lesions)
+        if self.measure_texture:
+            dil8 = np.ascontiguousarray(dilated, dtype=np.uint8)
+            raw16 = np.ascontiguousarray(raw, dtype=np.uint16)
+            intensity = (n.golden_measure_volume_intensity(dil8, raw16, a["type"], a["stored_bits"])
+                         if self.measure_intensity else None)
+            texture = n.golden_measure_volume_texture(dil8, raw16, self.texture_levels, a["type"], a["stored_bits"])
+            text = n.volume_measure_to_json(rec, w, h, d, float(spacing[0]), float(spacing[1]), float(spacing[2]),
+                                            str(spacing_z_source), a["slope"], a["intercept"],
+                                            bool(self.config.pipeline_params().apply_rescale), self.measure_connectivity,
+                                            lesions, self.measure_lesions, intensity, texture)
+            return tuple(x for x in (rec, text, lesions, intensity) if x is not None) + (texture,)
         if not self.measure_intensity:
             return (rec, text) if lesions is None else (rec, text, lesions)
         intensity = n.golden_measure_volume_intensity(np.ascontiguousarray(dilated, dtype=np.uint8),

@@ -427,3 +427,74 @@ def measure_volume_intensity(dilated, raw, pixel_type="u16", stored_bits=16):
     dw = pack_bits(dilated.bool()).contiguous()
     return native().k_measure_volume_intensity(dw.data_ptr(), x.data_ptr(), w, h, d, pixel_type, int(stored_bits),
                                                _stream())
+
+
+def measure_texture(dilated, raw, levels=32, pixel_type="u16", stored_bits=16):
+    """Grey-level co-occurrence matrices (GLCM) of the stored samples of `raw` under masks (K12,
+    nm03/texture_core.h) → list of dicts: levels, key_lo, key_hi, samples, pairs and `glcm`, the
+    [levels, levels] uint32 matrix. The samples are discretised to `levels` (2..64) grey levels between the
+    smallest and largest of them; a pair is two mask pixels one index step apart in one of the four
+    forward directions (1,0), (1,1), (0,1), (−1,1); the matrix is merged over them and symmetric, its sum
+    2 · pairs. An empty mask gives zeros.
+
+    `dilated` (bool) and `raw` (16-bit storage) are CUDA tensors [N, H, W] or [H, W], or lists of [H, W]
+    tensors of ANY sizes: the whole batch is one launch, one workgroup per mask. `levels`, `pixel_type`
+    and `stored_bits` hold for every slice, or are lists with one entry per slice."""
+    def as_list(t):
+        if isinstance(t, (list, tuple)):
+            return list(t)
+        return list(_as3d(t))
+    dl, xl = as_list(dilated), as_list(raw)
+    if not dl or len(xl) != len(dl):
+        raise ValueError("dilated and raw must hold the same number of slices")
+    lv = [int(v) for v in levels] if isinstance(levels, (list, tuple)) else [int(levels)] * len(dl)
+    types = list(pixel_type) if isinstance(pixel_type, (list, tuple)) else [pixel_type] * len(dl)
+    bits = [int(b) for b in stored_bits] if isinstance(stored_bits, (list, tuple)) else [int(stored_bits)] * len(dl)
+    if len(types) != len(dl) or len(bits) != len(dl) or len(lv) != len(dl):
+        raise ValueError("levels, pixel_type and stored_bits lists need one entry per slice")
+    if any(t not in ("u16", "i16", "u8") for t in types):
+        raise ValueError("pixel_type must be u16, i16 or u8")
+    if any(not 1 <= b <= 16 for b in bits):
+        raise ValueError("stored_bits must be 1..16")
+    if any(not 2 <= v <= 64 for v in lv):
+        raise ValueError("levels must be 2..64")
+    hs, ws, dw, xs = [], [], [], []
+    for d, x in zip(dl, xl):
+        if d.dim() != 2 or x.shape != d.shape:
+            raise ValueError("every slice needs dilated and raw of one [H, W] shape")
+        if not d.is_cuda:
+            raise ValueError("masks must be CUDA (HIP) tensors")
+        x = x.contiguous()
+        _check(x, _U16, "raw")
+        hs.append(int(d.shape[0]))
+        ws.append(int(d.shape[1]))
+        dw.append(pack_bits(d.bool().unsqueeze(0)).reshape(-1))
+        xs.append(x.reshape(-1).view(torch.int16))
+    planes = torch.cat(dw).contiguous()
+    samples = torch.cat(xs).contiguous()
+    return native().k_measure_texture(planes.data_ptr(), samples.data_ptr(), hs, ws, lv, types, bits, _stream())
+
+
+def measure_volume_texture(dilated, raw, levels=32, pixel_type="u16", stored_bits=16):
+    """measure_texture's record for a volume mask (K12's four 3D launches) → one dict. The pairs are taken
+    over the thirteen forward directions (dx, dy, dz) with components in {−1, 0, 1}: dz = 1, or dz = 0 and
+    dy = 1, or dz = dy = 0 and dx = 1. Index steps: the voxel spacing is not consulted.
+
+    `dilated` (bool) and `raw` (16-bit storage) are CUDA tensors [D, H, W] of one shape; a volume with
+    (W + 1)·H·D + 1 ≥ 2³² raises, as for measure_volume."""
+    if dilated.dim() != 3 or raw.shape != dilated.shape:
+        raise ValueError("dilated and raw must be [D, H, W] of one shape")
+    if not dilated.is_cuda:
+        raise ValueError("masks must be CUDA (HIP) tensors")
+    if not 1 <= int(stored_bits) <= 16:
+        raise ValueError("stored_bits must be 1..16")
+    if not 2 <= int(levels) <= 64:
+        raise ValueError("levels must be 2..64")
+    x = raw.contiguous()
+    _check(x, _U16, "raw")
+    d, h, w = (int(v) for v in dilated.shape)
+    if d < 1 or h < 1 or w < 1:
+        raise ValueError("empty volume")
+    dw = pack_bits(dilated.bool()).contiguous()
+    return native().k_measure_volume_texture(dw.data_ptr(), x.data_ptr(), w, h, d, int(levels), pixel_type,
+                                             int(stored_bits), _stream())

@@ -467,6 +467,97 @@ def measure_volume_intensity(dilated, raw, pixel_type="u16", stored_bits=16):
     return measure_intensity(dilated, raw, pixel_type, stored_bits)
 
 
+GLCM_DIRECTIONS_2D = ((1, 0), (1, 1), (0, 1), (-1, 1))
+GLCM_DIRECTIONS_3D = tuple((dx, dy, dz) for dz in (0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1)
+                           if dz == 1 or (dy == 1) or (dy == 0 and dx == 1))
+
+
+def glcm(mask, raw, levels=32, pixel_type="u16", stored_bits=16, directions=None):
+    """The grey-level co-occurrence record (nm03/texture_core.h) of one mask [H, W] or [D, H, W] (torch or
+    NumPy) in NumPy: the stored samples become keys (signed data with the sign bit flipped), the keys
+    levels by min(levels − 1, (key − lo) · levels // (hi − lo)), and for every direction the mask and the
+    levels are compared with themselves shifted by it and the pairs scattered with np.add.at — into
+    C[a, b] and C[b, a]. `directions`: (dx, dy) or (dx, dy, dz) tuples; None gives the merged forward set
+    (4 in 2D, 13 in 3D). Returns the dict ops.measure_texture gives."""
+    import numpy as np
+
+    def to_np(t):
+        return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+    m = to_np(mask).astype(bool)
+    v = to_np(raw).view(np.uint16).astype(np.int64)
+    sh = 16 - int(stored_bits)
+    if pixel_type == "i16":
+        v = ((v << sh) & 0xFFFF).astype(np.uint16).view(np.int16).astype(np.int64) >> sh
+        key = (v & 0xFFFF) ^ 0x8000
+    else:
+        key = v & (0xFFFF >> sh)
+    two_d = m.ndim == 2
+    if two_d:
+        m, key = m[None], key[None]
+    if directions is None:
+        directions = GLCM_DIRECTIONS_2D if two_d else GLCM_DIRECTIONS_3D
+    ng = int(levels)
+    c = np.zeros((ng, ng), np.int64)
+    out = {"levels": ng, "key_lo": 0, "key_hi": 0, "samples": int(m.sum()), "pairs": 0}
+    if out["samples"]:
+        lo, hi = int(key[m].min()), int(key[m].max())
+        out["key_lo"], out["key_hi"] = lo, hi
+        lev = np.zeros_like(key) if hi == lo else np.minimum(ng - 1, (key - lo) * ng // (hi - lo))
+        D, H, W = m.shape
+
+        def window(n, s):  # the indices i with 0 <= i and i + s in [0, n), and their partners
+            return (slice(max(0, -s), n - max(0, s)), slice(max(0, s), n - max(0, -s)))
+
+        for t in directions:
+            dx, dy, dz = (tuple(t) + (0,))[:3]
+            (z0, z1), (y0, y1), (x0, x1) = window(D, dz), window(H, dy), window(W, dx)
+            both = m[z0, y0, x0] & m[z1, y1, x1]
+            a, b = lev[z0, y0, x0][both], lev[z1, y1, x1][both]
+            np.add.at(c, (a, b), 1)
+            np.add.at(c, (b, a), 1)
+            out["pairs"] += int(both.sum())
+    out["glcm"] = c.astype(np.uint32)
+    return out
+
+
+def glcm_features(c):
+    """The 7 integers and 16 doubles the sidecar derives from a co-occurrence matrix (measure::glcm_features),
+    in vectorised float64, under their sidecar keys; None where the text says null."""
+    import numpy as np
+    c = np.asarray(c).astype(np.int64)
+    ng = c.shape[0]
+    i, j = np.meshgrid(np.arange(1, ng + 1), np.arange(1, ng + 1), indexing="ij")
+    d = np.abs(i - j)
+    total = int(c.sum())
+    out = {"glcm_levels": ng, "glcm_pairs": total // 2, "glcm_nonzero": int((c > 0).sum()), "glcm_max_count": int(c.max()),
+           "glcm_sum_abs_d": int((d * c).sum()), "glcm_sum_d2": int((d * d * c).sum()),
+           "glcm_sum_sq": sum(int(x) * int(x) for x in c.ravel())}
+    names = ("joint_max", "joint_avg", "joint_var", "joint_entropy", "asm", "contrast", "dissimilarity", "inv_diff",
+             "inv_diff_moment", "correlation", "autocorrelation", "cluster_tendency", "cluster_shade", "cluster_prominence",
+             "sum_entropy", "diff_entropy")
+    if total == 0:
+        out.update({"glcm_" + k: None for k in names})
+        return out
+    p = c.astype(np.float64) / float(total)
+
+    def entropy(q):
+        q = q[q > 0]
+        return float(-(q * np.log2(q)).sum())
+
+    mu = float((i * p).sum())
+    var = float(((i - mu) ** 2 * p).sum())
+    s = i + j - 2 * mu
+    psum = np.bincount((i + j).ravel(), weights=p.ravel())
+    pdiff = np.bincount(d.ravel(), weights=p.ravel())
+    vals = (float(p.max()), mu, var, entropy(p.ravel()), float((p * p).sum()), float((d * d * p).sum()), float((d * p).sum()),
+            float((p / (1 + d)).sum()), float((p / (1 + d * d)).sum()),
+            float(((i - mu) * (j - mu) * p).sum()) / var if var > 0 else None, float((i * j * p).sum()),
+            float((s ** 2 * p).sum()), float((s ** 3 * p).sum()), float((s ** 4 * p).sum()), entropy(psum), entropy(pdiff))
+    out.update({"glcm_" + k: v for k, v in zip(names, vals)})
+    return out
+
+
 def psnr(a, b):
     mse = ((a.double() - b.double()) ** 2).mean().item()
     return math.inf if mse == 0 else 10 * math.log10(255.0 ** 2 / mse)

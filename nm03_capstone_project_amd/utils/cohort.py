@@ -97,6 +97,13 @@ class Cohort:
         return items
 
 
+# --measure-texture: the derived (float) columns of measurements.csv and volumes.csv; the seven integer
+# columns (glcm_levels … glcm_sum_sq) come back as int like the other integers.
+_GLCM_FLOATS = {"glcm_" + k for k in (
+    "joint_max", "joint_avg", "joint_var", "joint_entropy", "asm", "contrast", "dissimilarity", "inv_diff", "inv_diff_moment",
+    "correlation", "autocorrelation", "cluster_tendency", "cluster_shade", "cluster_prominence", "sum_entropy", "diff_entropy")}
+
+
 def read_measurements(out_dir):
     """Rows of <out_dir>/measurements.csv (written by the CLIs with --measure) as dicts keyed by the
     header: one per slice (`status` "ok" or the failure's name, then empty fields) and one per patient
@@ -104,12 +111,12 @@ def read_measurements(out_dir):
     have the diameter columns (lesion_px … major_angle_deg, arrays flattened), and a TOTAL row the
     patient's largest bidimensional_mm2 with the major_mm and perp_mm of that slice. With
     --measure-intensity the rows also have the 13 intensity columns (raw_sum_sq, raw_p10 … raw_p90, std,
-    p10 … p90, iqr; empty in TOTAL rows). Integer columns
+    p10 … p90, iqr; empty in TOTAL rows), with --measure-texture the 23 glcm_ columns alike. Integer columns
     come back as int, the derived ones as float, empty fields as None."""
     import csv
     import os
     floats = {"area_mm2", "centroid_x", "centroid_y", "centroid_x_mm", "centroid_y_mm", "mean", "major_mm", "perp_mm",
-              "bidimensional_mm2", "major_angle_deg", "std", "p10", "p25", "median", "p75", "p90", "iqr"}
+              "bidimensional_mm2", "major_angle_deg", "std", "p10", "p25", "median", "p75", "p90", "iqr"} | _GLCM_FLOATS
     text = {"patient", "file", "status"}
     rows = []
     with open(os.path.join(out_dir, "measurements.csv"), newline="") as f:
@@ -122,13 +129,13 @@ def read_measurements(out_dir):
 def read_volume_measurements(out_dir):
     """Rows of <out_dir>/volumes.csv (written by the 3D CLI with --measure-volume) as dicts keyed by
     the header: one per patient in plan order (`status` "ok", or "failed" and then empty fields). With
-    --measure-intensity the rows also have the 13 intensity columns.
+    --measure-intensity the rows also have the 13 intensity columns, with --measure-texture the 23 glcm_ ones.
     Integer columns come back as int, spacings and the derived ones as float, empty fields as None."""
     import csv
     import os
     floats = {"spacing_x", "spacing_y", "spacing_z", "volume_mm3", "volume_ml", "surface_mm2", "centroid_x",
               "centroid_y", "centroid_z", "centroid_x_mm", "centroid_y_mm", "centroid_z_mm", "mean", "std", "p10", "p25",
-              "median", "p75", "p90", "iqr"}
+              "median", "p75", "p90", "iqr"} | _GLCM_FLOATS
     text = {"patient", "status", "spacing_z_source"}
     rows = []
     with open(os.path.join(out_dir, "volumes.csv"), newline="") as f:

@@ -46,6 +46,18 @@ const char* const kIntensityColumns[] = {"raw_sum_sq", "raw_p10", "raw_p25", "ra
 constexpr size_t kNumIntensityColumns = sizeof(kIntensityColumns) / sizeof(kIntensityColumns[0]);
 const char* const kIntensityKey = ",\"raw_sum_sq\":";
 
+// --measure-texture: the columns after all of those — the texture keys in their order.
+const char* const kTextureColumns[] = {"glcm_levels",          "glcm_pairs",           "glcm_nonzero",
+                                       "glcm_max_count",       "glcm_sum_abs_d",       "glcm_sum_d2",
+                                       "glcm_sum_sq",          "glcm_joint_max",       "glcm_joint_avg",
+                                       "glcm_joint_var",       "glcm_joint_entropy",   "glcm_asm",
+                                       "glcm_contrast",        "glcm_dissimilarity",   "glcm_inv_diff",
+                                       "glcm_inv_diff_moment", "glcm_correlation",     "glcm_autocorrelation",
+                                       "glcm_cluster_tendency", "glcm_cluster_shade",  "glcm_cluster_prominence",
+                                       "glcm_sum_entropy",     "glcm_diff_entropy"};
+constexpr size_t kNumTextureColumns = sizeof(kTextureColumns) / sizeof(kTextureColumns[0]);
+const char* const kTextureKey = ",\"glcm_levels\":";
+
 // The values of one sidecar line in column order ("" for null). The text is this program's own
 // (one flat object, one array of four integers): values are what stands between ':' or ',' and the
 // next ',' / ']' / '}'.
@@ -114,20 +126,44 @@ std::string without_intensity(const std::string& text, std::vector<std::string>*
   return text.substr(0, at) + "}\n";
 }
 
+// Likewise the texture keys: the last keys of a sidecar whose lesion keys the caller has cut.
+std::string without_texture(const std::string& text, std::vector<std::string>* texture) {
+  const size_t at = text.find(kTextureKey);
+  if (at == std::string::npos) return text;
+  std::vector<std::string> v;
+  if (texture && parse_sidecar("{" + text.substr(at + 1), v, kNumTextureColumns)) *texture = v;
+  return text.substr(0, at) + "}\n";
+}
+
+// The texture columns of one row: the values, or empty fields.
+void put_texture(std::ostringstream& o, bool have, const std::vector<std::string>& tv) {
+  for (size_t c = 0; c < kNumTextureColumns; ++c) o << "," << (have && tv.size() == kNumTextureColumns ? tv[c] : std::string());
+}
+
+// ", \"texture\": true, \"texture_levels\": N" before the closing brace of a --json totals object.
+void put_texture_totals(std::string& s, int levels) {
+  if (levels) s.insert(s.size() - 1, ", \"texture\": true, \"texture_levels\": " + std::to_string(levels));
+}
+
 }  // namespace
 
-VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows, bool intensity) {
+VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows, bool intensity,
+                               int texture_levels) {
   VolumeTotals tot;
   tot.intensity = intensity;
+  tot.texture_levels = texture_levels;
   std::ostringstream o;
   o << "patient,status";
   for (const char* c : kVolumeColumns) o << "," << c;
   if (intensity)
     for (const char* c : kIntensityColumns) o << "," << c;
+  if (texture_levels)
+    for (const char* c : kTextureColumns) o << "," << c;
   o << "\n";
   for (const auto& r : rows) {
-    std::vector<std::string> v, iv;
-    const bool have = r.ok && parse_sidecar(without_intensity(without_lesions(r.sidecar), &iv), v, kNumVolumeColumns);
+    std::vector<std::string> v, iv, tv;
+    const bool have =
+        r.ok && parse_sidecar(without_intensity(without_texture(without_lesions(r.sidecar), &tv), &iv), v, kNumVolumeColumns);
     o << r.id << "," << (r.ok ? (have ? "ok" : "no_sidecar") : "failed");
     for (size_t c = 0; c < kNumVolumeColumns; ++c) {
       std::string x = have ? v[c] : std::string();
@@ -136,6 +172,7 @@ VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<Vo
     }
     if (intensity)
       for (size_t c = 0; c < kNumIntensityColumns; ++c) o << "," << (have && iv.size() == kNumIntensityColumns ? iv[c] : std::string());
+    if (texture_levels) put_texture(o, have, tv);
     o << "\n";
     if (!have) continue;
     ++tot.volumes;
@@ -160,6 +197,7 @@ std::string volume_totals_json(const VolumeTotals& t) {
                   (long long)t.volumes, (unsigned long long)t.volume_vox, t.volume_mm3);
   std::string s = buf;
   if (t.intensity) s.insert(s.size() - 1, ", \"intensity\": true");
+  put_texture_totals(s, t.texture_levels);
   return s;
 }
 
@@ -207,10 +245,11 @@ int64_t write_lesions_csv(const std::string& out_root, const std::vector<VolumeP
 }
 
 MeasureTotals write_measurements_csv(const std::string& out_root, const std::vector<MeasurePatient>& patients,
-                                     bool diameters, bool intensity) {
+                                     bool diameters, bool intensity, int texture_levels) {
   MeasureTotals tot;
   tot.diameters = diameters;
   tot.intensity = intensity;
+  tot.texture_levels = texture_levels;
   const size_t ncols = kNumColumns + (diameters ? kNumDiameterColumns : 0);
   std::ostringstream o;
   o << "patient,file,status";
@@ -219,6 +258,8 @@ MeasureTotals write_measurements_csv(const std::string& out_root, const std::vec
     for (const char* c : kDiameterColumns) o << "," << c;
   if (intensity)
     for (const char* c : kIntensityColumns) o << "," << c;
+  if (texture_levels)
+    for (const char* c : kTextureColumns) o << "," << c;
   o << "\n";
   char buf[64];
   for (const auto& p : patients) {
@@ -230,7 +271,7 @@ MeasureTotals write_measurements_csv(const std::string& out_root, const std::vec
     std::string bidim_text, major_text, perp_text;
     for (size_t i = 0; i < p.files.size(); ++i) {
       const std::string name = cohort::filename(p.files[i]);
-      std::vector<std::string> v, iv;
+      std::vector<std::string> v, iv, tv;
       bool have = false;
       if (p.status[i] == kSliceOk) {
         std::ifstream f(cohort::with_slash(p.out_dir) + measure::sidecar_name(cohort::stem(p.files[i])), std::ios::binary);
@@ -239,7 +280,9 @@ MeasureTotals write_measurements_csv(const std::string& out_root, const std::vec
         // With `diameters` a sidecar without the diameter keys (written earlier without the flag) is read too.
         // With `intensity` the intensity keys, the sidecar's last, go to their own columns; without them
         // (a sidecar written earlier without the flag) those columns stay empty.
-        const std::string text = intensity ? without_intensity(ss.str(), &iv) : ss.str();
+        // The texture keys come after them and are cut first, whether the table has their columns or not.
+        const std::string cut = without_texture(ss.str(), &tv);
+        const std::string text = intensity ? without_intensity(cut, &iv) : cut;
         have = f && (parse_sidecar(text, v, ncols) || (diameters && parse_sidecar(text, v, kNumColumns)));
         if (have) v.resize(ncols);
       }
@@ -247,6 +290,7 @@ MeasureTotals write_measurements_csv(const std::string& out_root, const std::vec
       for (size_t c = 0; c < ncols; ++c) o << "," << (have ? v[c] : std::string());
       if (intensity)
         for (size_t c = 0; c < kNumIntensityColumns; ++c) o << "," << (have && iv.size() == kNumIntensityColumns ? iv[c] : std::string());
+      if (texture_levels) put_texture(o, have, tv);
       o << "\n";
       if (!have) continue;
       ++tot.slices;
@@ -272,6 +316,7 @@ MeasureTotals write_measurements_csv(const std::string& out_root, const std::vec
     }
     if (intensity)
       for (size_t c = 0; c < kNumIntensityColumns; ++c) o << ",";
+    if (texture_levels) put_texture(o, false, {});
     o << "\n";
     tot.area_px += area_px;
     tot.area_mm2 += area_mm2;
@@ -295,6 +340,7 @@ std::string measure_totals_json(const MeasureTotals& t) {
                   (unsigned long long)t.area_px, t.area_mm2);
   std::string s = buf;
   if (t.intensity) s.insert(s.size() - 1, ", \"intensity\": true");
+  put_texture_totals(s, t.texture_levels);
   return s;
 }
 

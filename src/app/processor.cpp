@@ -67,6 +67,12 @@ void usage(const std::string& which) {
             << "  --measure-intensity    --measure (with --mode 3d: --measure-volume) plus exact first-order statistics of the\n"
             << "                         samples under the dilated mask: 10/25/50/75/90th percentile, sum of squares, std, iqr\n"
             << "                         in the sidecar and the table (not with --split-volume)\n"
+            << "  --measure-texture      --measure (with --mode 3d: --measure-volume) plus second-order texture of the samples\n"
+            << "                         under the dilated mask: the grey-level co-occurrence matrix over the forward\n"
+            << "                         directions (4 in 2D, 13 in 3D; index steps, spacing not consulted) and 23 keys\n"
+            << "                         derived from it (contrast, entropy, correlation, ...) in the sidecar and the table\n"
+            << "                         (not with --split-volume)\n"
+            << "  --texture-levels N     grey levels of --measure-texture, 2..64 (default 32)\n"
             << "  --measure-connectivity 4|8  connectivity of the component count (default 8; holes use the dual)\n"
             << "  --measure-volume       3d: also write the volumetry of each patient's dilated volume (voxels, mm3,\n"
             << "                         surface, components, cavities, tunnels): <patient>/volume_measure.json and\n"
@@ -156,6 +162,8 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
   install_crash_handler();
   AppConfig c;
   bool measure_intensity = false;  // --measure-intensity
+  bool measure_texture = false;    // --measure-texture
+  bool texture_levels_given = false;
   c.main_unix_s = main_unix;
   c.data_root = cohort::default_data_root();
   c.out_dir = which == "test_pipeline" ? "../out-test" : which == "img_processing_sequential" ? "../out-sequential" : "../out-parallel";
@@ -262,6 +270,18 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
     else if (a == "--measure") c.engine.pipe.measure = true;
     else if (a == "--measure-diameters") c.engine.pipe.measure = c.engine.pipe.measure_diameters = true;
     else if (a == "--measure-intensity") measure_intensity = true;  // resolved after the loop: --mode may follow
+    else if (a == "--measure-texture") measure_texture = true;  // alike
+    else if (a == "--texture-levels") {
+      const std::string v = val();
+      char* end = nullptr;
+      const long n = std::strtol(v.c_str(), &end, 10);
+      if (v.empty() || *end != 0 || n < 2 || n > 64) {
+        std::cerr << "--texture-levels must be an integer from 2 to 64 (got " << v << ")" << std::endl;
+        std::exit(2);
+      }
+      c.engine.pipe.texture_levels = (int)n;
+      texture_levels_given = true;
+    }
     else if (a == "--measure-volume") c.measure_volume = true;
     else if (a == "--measure-volume-connectivity") {
       const std::string v = val();
@@ -330,6 +350,17 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
   // --measure-intensity implies --measure, or --measure-volume with --mode 3d.
   if (measure_intensity && c.mode == "3d") c.measure_volume = c.measure_volume_intensity = true;
   if (measure_intensity && c.mode != "3d") c.engine.pipe.measure = c.engine.pipe.measure_intensity = true;
+  if (measure_texture && c.split_volume) {
+    std::cerr << "--measure-texture is not available with --split-volume" << std::endl;
+    std::exit(2);
+  }
+  if (texture_levels_given && !measure_texture) {
+    std::cerr << "--texture-levels needs --measure-texture" << std::endl;
+    std::exit(2);
+  }
+  // --measure-texture implies --measure, or --measure-volume with --mode 3d.
+  if (measure_texture && c.mode == "3d") c.measure_volume = c.measure_volume_texture = true;
+  if (measure_texture && c.mode != "3d") c.engine.pipe.measure = c.engine.pipe.measure_texture = true;
   if (c.engine.pipe.measure_diameters && c.mode == "3d") {
     std::cerr << "--measure-diameters is not available with --mode 3d" << std::endl;
     std::exit(2);
@@ -511,7 +542,8 @@ int run_sequential(const AppConfig& cfg) {
       if (cfg.engine.pipe.measure) {
         try {
           measure_totals = write_measurements_csv(cfg.out_dir, measured, cfg.engine.pipe.measure_diameters,
-                                                  cfg.engine.pipe.measure_intensity);
+                                                  cfg.engine.pipe.measure_intensity,
+                                                  cfg.engine.pipe.measure_texture ? cfg.engine.pipe.texture_levels : 0);
         } catch (const std::exception& e) {
           std::cerr << "Error writing measurements.csv: " << e.what() << std::endl;
         }
@@ -662,7 +694,8 @@ void write_measure_table(const AppConfig& cfg, const std::vector<PatientPlan>& p
                          MeasureTotals* totals) {
   try {
     *totals = write_measurements_csv(cfg.out_dir, measure_patients(plan, gst), cfg.engine.pipe.measure_diameters,
-                                     cfg.engine.pipe.measure_intensity);
+                                     cfg.engine.pipe.measure_intensity,
+                                     cfg.engine.pipe.measure_texture ? cfg.engine.pipe.texture_levels : 0);
   } catch (const std::exception& e) {
     std::cerr << "Error writing measurements.csv: " << e.what() << std::endl;
   }

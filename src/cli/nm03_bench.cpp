@@ -12,6 +12,7 @@
 //   --config single          config 1: test_pipeline's single slice (all stages + 5 renders +
 //                            5 JPEGs, test_pipeline.cpp:29-182) on the GPU, latency per slice
 //   --config single-cpu      config 1 on the golden CPU model
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <iostream>
@@ -41,6 +42,8 @@ int main(int argc, char** argv) {
   bool measure_volume = false;  // volume: also K8 (the volumetry of the dilated volume) per run
   int measure_volume_conn = 26;
   int measure_volume_lesions = 0;  // volume: also K10 (one record per lesion, the N largest) per run
+  bool measure_texture = false;    // cohort with --measure / volume with --measure-volume: also K12 (co-occurrence matrix)
+  int texture_levels = 32;
   bool measure_intensity = false;  // cohort with --measure / volume with --measure-volume: also K11 (percentiles, sum of squares)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -67,6 +70,8 @@ int main(int argc, char** argv) {
     else if (a == "--measure") ec.pipe.measure = true;    // cohort: also K7 and the measurement sidecar per slice
     else if (a == "--measure-diameters") ec.pipe.measure = ec.pipe.measure_diameters = true;  // cohort: K7, K9 and the extended sidecar
     else if (a == "--measure-intensity") measure_intensity = true;
+    else if (a == "--measure-texture") measure_texture = true;
+    else if (a == "--texture-levels") texture_levels = std::min(64, std::max(2, std::atoi(v().c_str())));
     else if (a == "--measure-connectivity") ec.pipe.measure_connectivity = std::atoi(v().c_str()) == 4 ? 4 : 8;
     else if (a == "--measure-volume") measure_volume = true;
     else if (a == "--measure-volume-connectivity") measure_volume_conn = std::atoi(v().c_str()) == 6 ? 6 : 26;
@@ -88,6 +93,9 @@ int main(int argc, char** argv) {
   // --measure-intensity implies the measurement it extends: --measure (cohort) or --measure-volume (volume).
   if (measure_intensity && config == "cohort") ec.pipe.measure = ec.pipe.measure_intensity = true;
   if (measure_intensity && config == "volume") measure_volume = true;
+  // --measure-texture likewise.
+  if (measure_texture && config == "cohort") ec.pipe.measure = ec.pipe.measure_texture = true, ec.pipe.texture_levels = texture_levels;
+  if (measure_texture && config == "volume") measure_volume = true;
   try {
     const std::string base = nm03::cohort::cohort_dir(root);
     auto pids = nm03::cohort::find_patient_dirs(base);
@@ -178,6 +186,8 @@ int main(int argc, char** argv) {
       vp.measure_connectivity = measure_volume_conn;
       vp.measure_lesions = measure_volume_lesions;
       vp.measure_intensity = measure_intensity;
+      vp.measure_texture = measure_texture;
+      vp.texture_levels = texture_levels;
       nm03::VolumeRunner runner(ec.device);
       for (int w = 0; w < warmup; ++w) runner.run(v, vp, false);
       double ks = 0, ms = 0;
@@ -186,6 +196,7 @@ int main(int argc, char** argv) {
       size_t lesions = 0;
       uint64_t lesion0_vox = 0;
       nm03::IntensityStats vi = {};
+      uint64_t glcm_pairs = 0;
       const double t0 = now_s();
       for (int k = 0; k < steps; ++k) {
         auto r = runner.run(v, vp, false);
@@ -194,6 +205,7 @@ int main(int argc, char** argv) {
         sweeps = r.sweeps;
         vm = r.measure;
         vi = r.intensity;
+        glcm_pairs = r.texture.head.pairs;
         lesions = r.lesions.size();
         lesion0_vox = lesions ? r.lesions[0].voxels : 0;
       }
@@ -218,6 +230,8 @@ int main(int argc, char** argv) {
         std::cout << ", \"lesions_max\": " << measure_volume_lesions << ", \"lesions\": " << lesions
                   << ", \"largest_lesion_vox\": " << lesion0_vox;
       if (measure_intensity) std::cout << ", \"intensity\": true, \"raw_p50\": " << vi.pct[2];
+      if (measure_texture)
+        std::cout << ", \"texture\": true, \"texture_levels\": " << texture_levels << ", \"glcm_pairs\": " << glcm_pairs;
       std::cout << "}" << std::endl;
     } else if (config == "volume-cpu") {
       if (pids.empty()) throw std::runtime_error("no patients");

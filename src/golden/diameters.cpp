@@ -106,6 +106,13 @@ std::string measure_json(const SliceMeasure& m, const SliceDiameters& d, const S
 
 std::string measure_sidecar(const std::vector<uint8_t>& dilated, const std::vector<uint8_t>& region, const SliceInput& s,
                             const PipelineParams& p) {
+  if (p.measure_texture) {  // the texture keys after all the others: the text without the flag, then they
+    PipelineParams q = p;
+    q.measure_texture = false;
+    const measure::Glcm tx = measure_texture(dilated, s, p.texture_levels);
+    return measure::insert_global_keys(measure_sidecar(dilated, region, s, q),
+                                       measure::texture_keys(tx.c.data(), (int)tx.head.levels));
+  }
   const SliceMeasure m = measure(dilated, region, s, p.measure_connectivity);
   if (p.measure_intensity) {  // the intensity keys after all the others
     const IntensityStats st = measure_intensity(dilated, s);

@@ -1,6 +1,7 @@
-// Device-side helpers shared by the measurement kernels K7 (k7_measure.hip) and K9 (k9_diameters.hip):
-// the relaxed agent-scope accesses to the labelling scratch, wave64 reductions and the bit plane of
-// one slice.
+// Device-side helpers shared by the measurement kernels K7 (k7_measure.hip), K9 (k9_diameters.hip), K11
+// (k11_intensity.hip) and K12 (k12_texture.hip): the relaxed agent-scope accesses to the labelling
+// scratch, wave64 reductions, the bit plane of one slice, and K11's and K12's sample walk and
+// wave-combining LDS histogram add.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -67,6 +68,55 @@ struct Plane {
     return z == 0ull ? 0 : (k << 6) + 64 - __clzll((long long)z);
   }
 };
+
+constexpr int kPeelRounds = 3;
+
+// hist[key] += 1 for every lane with `on`, equal keys combined in the wave (k11_intensity.hip: "Bin contention").
+// Called by all 64 lanes of a wave together.
+// `give_up`: stop combining after a round that matched fewer than a quarter of the remaining lanes — the
+// keys are spread, further rounds would cost more instructions than the adds they save (K12, whose
+// pair cells of textured content rarely repeat within a word, calls it up to 13 times a word).
+__device__ __forceinline__ void wave_hist_add(uint32_t* hist, uint32_t key, bool on, int lane, bool give_up = false) {
+  uint64_t rest = __ballot(on);
+#pragma unroll
+  for (int r = 0; r < kPeelRounds; ++r) {
+    if (rest == 0ull) return;  // uniform over the wave
+    const int lead = __ffsll((long long)rest) - 1;
+    const uint32_t k = (uint32_t)__shfl((int)key, lead, 64);
+    const uint64_t same = __ballot(on && key == k) & rest;
+    if (lane == lead) atomicAdd(hist + k, (uint32_t)__popcll(same));
+    const bool spread = give_up && 4 * __popcll(same) < __popcll(rest);  // uniform
+    rest &= ~same;
+    if (spread) break;
+  }
+  if ((rest >> lane) & 1ull) atomicAdd(hist + key, 1u);
+}
+
+// The wave's non-empty words in turn, lane = bit: f(on, stored bits) for every lane, four words a round.
+// `m`: the lane's own word (0 for none), `off`: the sample offset of its first pixel.
+template <class F>
+__device__ __forceinline__ void walk_samples(uint64_t m, uint32_t off, const uint16_t* __restrict__ px, int lane, F&& f) {
+  for (uint64_t act = __ballot(m != 0ull); act;) {
+    uint64_t mj[4];
+    uint32_t oj[4];
+    uint16_t rv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      mj[u] = 0ull;
+      oj[u] = 0u;
+      if (act) {
+        const int j = __ffsll((long long)act) - 1;
+        act &= act - 1;
+        mj[u] = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(m >> 32), j, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)m, j, 64);
+        oj[u] = (uint32_t)__shfl((int)off, j, 64);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) rv[u] = ((mj[u] >> lane) & 1ull) ? px[(size_t)oj[u] + (size_t)lane] : (uint16_t)0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) f(((mj[u] >> lane) & 1ull) != 0ull, rv[u]);
+  }
+}
 
 }  // namespace
 }  // namespace nm03::gpu

@@ -32,6 +32,7 @@
 #include "nm03/jpeg_lossless.h"
 #include "nm03/kernels.h"
 #include "nm03/synth.h"
+#include "nm03/texture_core.h"
 #include "nm03/volume.h"
 #include "nm03/volume_slabs.h"
 
@@ -298,6 +299,65 @@ IntensityStats intensity_from(const py::dict& d) {
   return s;
 }
 
+// A texture record (nm03/measure.h TextureGlcm and its matrix) as a dict: the header integers plus
+// `glcm`, the [levels, levels] uint32 matrix.
+py::dict texture_dict(const measure::Glcm& g) {
+  py::dict d;
+  d["levels"] = g.head.levels;
+  d["key_lo"] = g.head.key_lo;
+  d["key_hi"] = g.head.key_hi;
+  d["samples"] = g.head.samples;
+  d["pairs"] = g.head.pairs;
+  py::array_t<uint32_t> a({(py::ssize_t)g.head.levels, (py::ssize_t)g.head.levels});
+  std::memcpy(a.mutable_data(), g.c.data(), g.c.size() * 4);
+  d["glcm"] = a;
+  return d;
+}
+
+measure::Glcm texture_from(const py::dict& d) {
+  measure::Glcm g;
+  g.head.levels = d["levels"].cast<uint32_t>();
+  g.head.key_lo = d["key_lo"].cast<uint32_t>();
+  g.head.key_hi = d["key_hi"].cast<uint32_t>();
+  g.head.samples = d["samples"].cast<uint64_t>();
+  g.head.pairs = d["pairs"].cast<uint64_t>();
+  auto a = d["glcm"].cast<py::array_t<uint32_t, py::array::c_style | py::array::forcecast>>();
+  if (g.head.levels < 2 || g.head.levels > 64 || a.ndim() != 2 || a.shape(0) != (py::ssize_t)g.head.levels ||
+      a.shape(1) != (py::ssize_t)g.head.levels)
+    throw std::invalid_argument("texture: glcm must be [levels, levels] with 2 <= levels <= 64");
+  g.c.assign(a.data(), a.data() + a.size());
+  return g;
+}
+
+py::dict glcm_features_dict(const measure::GlcmFeatures& f) {
+  py::dict d;
+  d["glcm_levels"] = f.levels;
+  d["glcm_pairs"] = f.pairs;
+  d["glcm_nonzero"] = f.nonzero;
+  d["glcm_max_count"] = f.max_count;
+  d["glcm_sum_abs_d"] = f.sum_abs_d;
+  d["glcm_sum_d2"] = f.sum_d2;
+  d["glcm_sum_sq"] = f.sum_sq;
+  auto put = [&](const char* k, double v, bool defined) { d[k] = defined ? py::object(py::float_(v)) : py::object(py::none()); };
+  put("glcm_joint_max", f.joint_max, f.any);
+  put("glcm_joint_avg", f.joint_avg, f.any);
+  put("glcm_joint_var", f.joint_var, f.any);
+  put("glcm_joint_entropy", f.joint_entropy, f.any);
+  put("glcm_asm", f.asm_, f.any);
+  put("glcm_contrast", f.contrast, f.any);
+  put("glcm_dissimilarity", f.dissimilarity, f.any);
+  put("glcm_inv_diff", f.inv_diff, f.any);
+  put("glcm_inv_diff_moment", f.inv_diff_moment, f.any);
+  put("glcm_correlation", f.correlation, f.any && f.correlation_defined);
+  put("glcm_autocorrelation", f.autocorrelation, f.any);
+  put("glcm_cluster_tendency", f.cluster_tendency, f.any);
+  put("glcm_cluster_shade", f.cluster_shade, f.any);
+  put("glcm_cluster_prominence", f.cluster_prominence, f.any);
+  put("glcm_sum_entropy", f.sum_entropy, f.any);
+  put("glcm_diff_entropy", f.diff_entropy, f.any);
+  return d;
+}
+
 // The integers of a volume record (nm03/measure.h VolumeMeasure) as a dict.
 py::dict volume_measure_dict(const VolumeMeasure& m) {
   py::dict d;
@@ -419,6 +479,8 @@ struct VolumeMeta {
   int measure_connectivity = 26;
   int measure_lesions = 0;
   bool measure_intensity = false;
+  bool measure_texture = false;
+  int texture_levels = 32;
 };
 
 void apply_meta(const VolumeMeta& mt, VolumeInput& v) {
@@ -458,6 +520,8 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
     vp.measure_connectivity = meta->measure_connectivity;
     vp.measure_lesions = meta->measure_lesions;
     vp.measure_intensity = meta->measure_intensity;
+    vp.measure_texture = meta->measure_texture;
+    vp.texture_levels = meta->texture_levels;
   }
   VolumeResult r;
   {
@@ -482,6 +546,12 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
       d["intensity"] = intensity_dict(r.intensity);
       d["measure_json"] = golden::measure_volume_json(r.measure, r.intensity, vp.measure_lesions ? &r.lesions : nullptr,
                                                       vp.measure_lesions, v, vp.pipe.apply_rescale, vp.measure_connectivity);
+    }
+    if (vp.measure_texture) {
+      d["texture"] = texture_dict(r.texture);
+      d["measure_json"] = golden::measure_volume_json(r.measure, vp.measure_intensity ? &r.intensity : nullptr,
+                                                      vp.measure_lesions ? &r.lesions : nullptr, vp.measure_lesions, r.texture, v,
+                                                      vp.pipe.apply_rescale, vp.measure_connectivity);
     }
     d["measure_s"] = r.measure_s;
   }
@@ -516,6 +586,8 @@ PYBIND11_MODULE(_nm03, m) {
       .def_readwrite("measure", &PipelineParams::measure)
       .def_readwrite("measure_diameters", &PipelineParams::measure_diameters)
       .def_readwrite("measure_intensity", &PipelineParams::measure_intensity)
+      .def_readwrite("measure_texture", &PipelineParams::measure_texture)
+      .def_readwrite("texture_levels", &PipelineParams::texture_levels)
       .def_property(
           "measure_connectivity", [](const PipelineParams& p) { return (int)p.measure_connectivity; },
           [](PipelineParams& p, int v) {
@@ -871,7 +943,7 @@ PYBIND11_MODULE(_nm03, m) {
           d["overlay"] = to_np<uint8_t>(j.overlay_canvas, {rp.out_height, rp.out_width, 3});
           d["jpeg_overlay"] = py::bytes((const char*)j.overlay.data(), j.overlay.size());
         }
-        if (p.measure || p.measure_diameters || p.measure_intensity) {
+        if (p.measure || p.measure_diameters || p.measure_intensity || p.measure_texture) {
           const SliceMeasure sm = golden::measure(r.dilated, r.region, s, p.measure_connectivity);
           d["measure"] = measure_dict(sm);
           if (p.measure_intensity) d["intensity"] = intensity_dict(golden::measure_intensity(r.dilated, s));
@@ -882,7 +954,8 @@ PYBIND11_MODULE(_nm03, m) {
           } else {
             d["measure_json"] = golden::measure_json(sm, s, p);
           }
-          if (p.measure_intensity) d["measure_json"] = golden::measure_sidecar(r.dilated, r.region, s, p);
+          if (p.measure_intensity || p.measure_texture) d["measure_json"] = golden::measure_sidecar(r.dilated, r.region, s, p);
+          if (p.measure_texture) d["texture"] = texture_dict(golden::measure_texture(r.dilated, s, p.texture_levels));
         }
         return d;
       },
@@ -1015,7 +1088,14 @@ PYBIND11_MODULE(_nm03, m) {
   m.def(
       "measure_to_json",
       [](const py::dict& rec, int w, int h, float sx, float sy, float slope, float intercept, bool apply_rescale,
-         int connectivity, const py::object& intensity) {
+         int connectivity, const py::object& intensity, const py::object& texture) {
+        if (!texture.is_none()) {  // the text with the texture keys after all the others (a texture dict)
+          IntensityStats st{};
+          if (!intensity.is_none()) st = intensity_from(intensity.cast<py::dict>());
+          return measure::to_json(measure_from(rec), nullptr, intensity.is_none() ? nullptr : &st,
+                                  texture_from(texture.cast<py::dict>()), w, h, sx, sy, slope, intercept, apply_rescale,
+                                  connectivity);
+        }
         if (!intensity.is_none())  // the text with the intensity keys (an IntensityStats dict)
           return measure::to_json(measure_from(rec), intensity_from(intensity.cast<py::dict>()), w, h, sx, sy, slope, intercept,
                                   apply_rescale, connectivity);
@@ -1023,7 +1103,7 @@ PYBIND11_MODULE(_nm03, m) {
       },
       py::arg("record"), py::arg("w"), py::arg("h"), py::arg("spacing_x") = 1.f, py::arg("spacing_y") = 1.f,
       py::arg("slope") = 1.f, py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 8,
-      py::arg("intensity") = py::none());
+      py::arg("intensity") = py::none(), py::arg("texture") = py::none());
 
   // The diameter record (nm03/measure.h SliceDiameters) of a mask [H, W] from the golden model.
   m.def(
@@ -1037,7 +1117,15 @@ PYBIND11_MODULE(_nm03, m) {
   m.def(
       "measure_diameters_to_json",
       [](const py::dict& rec, const py::dict& diam, int w, int h, float sx, float sy, float slope, float intercept,
-         bool apply_rescale, int connectivity, const py::object& intensity) {
+         bool apply_rescale, int connectivity, const py::object& intensity, const py::object& texture) {
+        if (!texture.is_none()) {
+          IntensityStats st{};
+          if (!intensity.is_none()) st = intensity_from(intensity.cast<py::dict>());
+          const SliceDiameters sd = diameters_from(diam);
+          return measure::to_json(measure_from(rec), &sd, intensity.is_none() ? nullptr : &st,
+                                  texture_from(texture.cast<py::dict>()), w, h, sx, sy, slope, intercept, apply_rescale,
+                                  connectivity);
+        }
         if (!intensity.is_none())
           return measure::to_json(measure_from(rec), diameters_from(diam), intensity_from(intensity.cast<py::dict>()), w, h, sx,
                                   sy, slope, intercept, apply_rescale, connectivity);
@@ -1046,7 +1134,7 @@ PYBIND11_MODULE(_nm03, m) {
       },
       py::arg("record"), py::arg("diameters"), py::arg("w"), py::arg("h"), py::arg("spacing_x") = 1.f,
       py::arg("spacing_y") = 1.f, py::arg("slope") = 1.f, py::arg("intercept") = 0.f, py::arg("apply_rescale") = true,
-      py::arg("connectivity") = 8, py::arg("intensity") = py::none());
+      py::arg("connectivity") = 8, py::arg("intensity") = py::none(), py::arg("texture") = py::none());
 
   // ---- volume measurements (nm03/measure.h VolumeMeasure) ----------------------------------------------
   auto volume_arrays = [](const py::array_t<uint8_t, py::array::c_style | py::array::forcecast>& dil,
@@ -1107,8 +1195,22 @@ PYBIND11_MODULE(_nm03, m) {
       "volume_measure_to_json",
       [](const py::dict& rec, int w, int h, int d, double sx, double sy, double sz, const std::string& source, float slope,
          float intercept, bool apply_rescale, int connectivity, const py::object& lesions, int lesions_max,
-         const py::object& intensity) {
+         const py::object& intensity, const py::object& texture) {
         // Pixel spacings pass through float, as VolumeInput holds them.
+        if (!texture.is_none()) {  // the text with the texture keys after the global keys (a texture dict)
+          IntensityStats st{};
+          if (!intensity.is_none()) st = intensity_from(intensity.cast<py::dict>());
+          std::vector<VolumeLesion> ls;
+          if (!lesions.is_none()) {
+            for (const py::handle& l : lesions.cast<py::list>()) ls.push_back(volume_lesion_from(l.cast<py::dict>()));
+            check_max_lesions(lesions_max);
+            if (ls.size() > (size_t)lesions_max) throw std::invalid_argument("more lesions than lesions_max");
+          }
+          return measure::volume_to_json(volume_measure_from(rec), intensity.is_none() ? nullptr : &st, ls.data(), (int)ls.size(),
+                                         lesions.is_none() ? 0 : lesions_max, texture_from(texture.cast<py::dict>()), w, h, d,
+                                         (double)(float)sx, (double)(float)sy, sz, source, slope, intercept, apply_rescale,
+                                         connectivity);
+        }
         if (lesions.is_none()) {
           if (!intensity.is_none())  // the text with the intensity keys (an IntensityStats dict)
             return measure::volume_to_json(volume_measure_from(rec), intensity_from(intensity.cast<py::dict>()), w, h, d,
@@ -1133,7 +1235,8 @@ PYBIND11_MODULE(_nm03, m) {
       py::arg("record"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_x") = 1.0, py::arg("spacing_y") = 1.0,
       py::arg("spacing_z") = 1.0, py::arg("spacing_z_source") = "default", py::arg("slope") = 1.f,
       py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 26,
-      py::arg("lesions") = py::none(), py::arg("lesions_max") = 0, py::arg("intensity") = py::none());
+      py::arg("lesions") = py::none(), py::arg("lesions_max") = 0, py::arg("intensity") = py::none(),
+      py::arg("texture") = py::none());
   // The N largest components of a volume mask (nm03/measure.h VolumeLesion) by the golden model (flood
   // fill per component) → list of dicts of the records' integers, largest first.
   m.def(
@@ -1231,6 +1334,76 @@ PYBIND11_MODULE(_nm03, m) {
                                                        (v.w + 63) / 64, (uint8_t)v.type, (uint8_t)v.stored_bits));
       },
       py::arg("dilated"), py::arg("raw"), py::arg("type") = "u16", py::arg("stored_bits") = 16);
+
+  // ---- texture (nm03/texture_core.h, nm03/measure.h TextureGlcm) -----------------------------------------
+  m.def("texture_level", [](uint32_t key, uint32_t lo, uint32_t hi, uint32_t levels) { return tcore::level(key, lo, hi, levels); });
+  // Everything the sidecar derives from a co-occurrence matrix [levels, levels] (measure::glcm_features):
+  // the 7 integers and the 16 doubles under their sidecar keys, None where the text says null.
+  m.def("glcm_features", [](py::array_t<uint32_t, py::array::c_style | py::array::forcecast> c) {
+    if (c.ndim() != 2 || c.shape(0) != c.shape(1) || c.shape(0) < 2 || c.shape(0) > 64)
+      throw std::invalid_argument("glcm must be [levels, levels] with 2 <= levels <= 64");
+    return glcm_features_dict(measure::glcm_features(c.data(), (int)c.shape(0)));
+  });
+  m.def("texture_keys", [](py::array_t<uint32_t, py::array::c_style | py::array::forcecast> c) {
+    if (c.ndim() != 2 || c.shape(0) != c.shape(1) || c.shape(0) < 2 || c.shape(0) > 64)
+      throw std::invalid_argument("glcm must be [levels, levels] with 2 <= levels <= 64");
+    return measure::texture_keys(c.data(), (int)c.shape(0));
+  });
+  // The golden model (a loop over voxels and directions) on a mask [H, W] and its 16-bit samples.
+  m.def(
+      "golden_measure_texture",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+         py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, int levels, const std::string& type,
+         int stored_bits) {
+        if (dil.ndim() != 2 || raw.ndim() != 2 || raw.shape(0) != dil.shape(0) || raw.shape(1) != dil.shape(1))
+          throw std::invalid_argument("dilated and raw must be [H, W] of one shape");
+        const golden::SliceInput s = slice_from(raw, type, stored_bits, 1.f, 0.f, 1.f, 1.f);
+        return texture_dict(golden::measure_texture(from_np<uint8_t>(dil), s, levels));
+      },
+      py::arg("dilated"), py::arg("raw"), py::arg("levels") = 32, py::arg("type") = "u16", py::arg("stored_bits") = 16);
+  m.def(
+      "golden_measure_volume_texture",
+      [volume_arrays](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+                      py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, int levels, const std::string& type,
+                      int stored_bits) {
+        const VolumeInput v = volume_arrays(dil, dil, raw, type, stored_bits);
+        return texture_dict(golden::measure_texture(from_np<uint8_t>(dil), v, levels));
+      },
+      py::arg("dilated"), py::arg("raw"), py::arg("levels") = 32, py::arg("type") = "u16", py::arg("stored_bits") = 16);
+  // The same records from the K12 kernels' per-word pair logic run on the host over bit planes
+  // (measure::texture_words). `stray_bits`: also set every storage bit past the width, which must not pair.
+  m.def(
+      "texture_words",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+         py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, int levels, const std::string& type,
+         int stored_bits, bool stray_bits) {
+        if (dil.ndim() != 2 || raw.ndim() != 2 || raw.shape(0) != dil.shape(0) || raw.shape(1) != dil.shape(1))
+          throw std::invalid_argument("dilated and raw must be [H, W] of one shape");
+        const golden::SliceInput s = slice_from(raw, type, stored_bits, 1.f, 0.f, 1.f, 1.f);
+        const int wpr = (s.w + 63) / 64;
+        std::vector<uint64_t> plane((size_t)s.h * wpr, 0ull);
+        auto a = dil.unchecked<2>();
+        for (int y = 0; y < s.h; ++y) {
+          for (int x = 0; x < s.w; ++x)
+            if (a(y, x)) plane[(size_t)y * wpr + (x >> 6)] |= 1ull << (x & 63);
+          if (stray_bits) plane[(size_t)y * wpr + wpr - 1] |= ~row_word_mask(wpr - 1, s.w);
+        }
+        return texture_dict(measure::texture_words(plane.data(), s.raw.data(), (size_t)s.w * s.h, s.w, s.h, 1, wpr,
+                                                   (uint8_t)s.type, (uint8_t)s.stored_bits, levels));
+      },
+      py::arg("dilated"), py::arg("raw"), py::arg("levels") = 32, py::arg("type") = "u16", py::arg("stored_bits") = 16,
+      py::arg("stray_bits") = false);
+  m.def(
+      "volume_texture_words",
+      [volume_arrays](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil,
+                      py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw, int levels, const std::string& type,
+                      int stored_bits) {
+        const VolumeInput v = volume_arrays(dil, dil, raw, type, stored_bits);
+        const std::vector<uint64_t> dw = pack_volume(dil);
+        return texture_dict(measure::texture_words(dw.data(), v.raw.data(), (size_t)v.w * v.h, v.w, v.h, v.d, (v.w + 63) / 64,
+                                                   (uint8_t)v.type, (uint8_t)v.stored_bits, levels));
+      },
+      py::arg("dilated"), py::arg("raw"), py::arg("levels") = 32, py::arg("type") = "u16", py::arg("stored_bits") = 16);
 
   // ---- JPEG --------------------------------------------------------------------------------------
   m.def("jpeg_encode_gray420", [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> g, int quality) {
@@ -1424,6 +1597,7 @@ PYBIND11_MODULE(_nm03, m) {
                d["measure_json"] = r.measure_json;
                if (e.config().pipe.measure_diameters) d["diameters"] = diameters_dict(r.diameters);
                if (e.config().pipe.measure_intensity) d["intensity"] = intensity_dict(r.intensity);
+               if (e.config().pipe.measure_texture) d["texture"] = texture_dict(r.texture);
              }
              return d;
            },
@@ -1456,10 +1630,13 @@ PYBIND11_MODULE(_nm03, m) {
              const PipelineParams& p, int connectivity, int dilation,
              const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_connectivity,
              const std::vector<double>& spacing, const std::string& spacing_z_source, const std::string& type,
-             int stored_bits, float slope, float intercept, int measure_lesions, bool measure_intensity) {
+             int stored_bits, float slope, float intercept, int measure_lesions, bool measure_intensity, bool measure_texture,
+             int texture_levels) {
             VolumeMeta mt;
             mt.measure_lesions = measure_lesions;
             mt.measure_intensity = measure_intensity;
+            mt.measure_texture = measure_texture;
+            mt.texture_levels = texture_levels;
             mt.type = type;
             mt.stored_bits = stored_bits;
             mt.slope = slope;
@@ -1476,7 +1653,8 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("measure") = false, py::arg("measure_connectivity") = 26,
           py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0}, py::arg("spacing_z_source") = "default",
           py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f, py::arg("intercept") = 0.f,
-          py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false)
+          py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false, py::arg("measure_texture") = false,
+          py::arg("texture_levels") = 32)
       .def(
           "run_slab",
           // One rank's z-slab (planes [z0, z0 + slab depth) of a `depth`-deep volume) through the
@@ -1484,12 +1662,14 @@ PYBIND11_MODULE(_nm03, m) {
           // coordinates. Returns the slab's masks plus rounds / exchanged bytes.
           [](VolumeRunner& self, Comm& comm, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> slab,
              int z0, int depth, const PipelineParams& p, int connectivity, int dilation,
-             const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_lesions, bool measure_intensity) {
+             const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_lesions, bool measure_intensity,
+             bool measure_texture) {
             SlabStats st;
             VolumeMeta mt;
             mt.measure = measure;  // refused by run_slab (std::invalid_argument) before anything is launched
             mt.measure_lesions = measure_lesions;  // alike
             mt.measure_intensity = measure_intensity;
+            mt.measure_texture = measure_texture;
             py::dict d = volume_call(slab, p, connectivity, dilation, seeds,
                                      [&](const VolumeInput& v, const VolumeParams& vp) {
                                        return self.run_slab(comm, v, z0, depth, vp, true, &st);
@@ -1501,7 +1681,7 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("comm"), py::arg("slab"), py::arg("z0"), py::arg("depth"), py::arg("params") = PipelineParams(),
           py::arg("connectivity") = 6, py::arg("dilation") = 7,
           py::arg("seeds") = std::vector<std::tuple<int, int, int>>{}, py::arg("measure") = false,
-          py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false);
+          py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false, py::arg("measure_texture") = false);
 
   // One-process rehearsal of the z-slab decomposition: `nranks` threads, each with its own
   // VolumeRunner (stream) on `device`, talking over loopback comms — the device-resident exchange
@@ -2261,6 +2441,107 @@ PYBIND11_MODULE(_nm03, m) {
     return intensity_dict(res);
   }, py::arg("dilated"), py::arg("raw"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("type") = "u16",
      py::arg("stored_bits") = 16, py::arg("stream") = 0);
+
+  // K12 on a batch of masks of ANY sizes in one launch (laid out as for k_measure_intensity), mask i at
+  // levels[i] grey levels. Returns one texture record dict per mask.
+  m.def("k_measure_texture", [](uintptr_t planes, uintptr_t raw, const std::vector<int>& hs, const std::vector<int>& ws,
+                                const std::vector<int>& levels, const std::vector<std::string>& types,
+                                const std::vector<int>& stored_bits, uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    const int n = (int)hs.size();
+    if (n <= 0 || ws.size() != hs.size()) throw std::invalid_argument("one height and one width per mask");
+    if (types.size() != hs.size() || stored_bits.size() != hs.size() || levels.size() != hs.size())
+      throw std::invalid_argument("one level count, one pixel type and one stored_bits per mask");
+    for (int b : stored_bits)
+      if (b < 1 || b > 16) throw std::invalid_argument("stored_bits must be 1..16");
+    for (int l : levels)
+      if (l < tcore::kMinLevels || l > tcore::kMaxLevels) throw std::invalid_argument("levels must be 2..64");
+    {
+      // K12's code object, loaded on the current device before this op's first launch there.
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_measure_texture();
+        preloaded.push_back(dev);
+      }
+    }
+    std::vector<gpu::SliceDesc> d((size_t)n);
+    std::vector<gpu::TextureSlot> slots((size_t)n);
+    size_t raw_off = 0, mask_off = 0, word_off = 0;
+    for (int i = 0; i < n; ++i) {
+      const int h = hs[(size_t)i], w = ws[(size_t)i];
+      if (w <= 0 || h <= 0 || w > gpu::kMaxSliceDim || h > gpu::kMaxSliceDim) throw std::invalid_argument("bad mask size");
+      gpu::SliceDesc& s = d[(size_t)i];
+      std::memset(&s, 0, sizeof(s));
+      s.raw_off = (uint32_t)raw_off;
+      s.mask_off = (uint32_t)mask_off;
+      s.w = (uint16_t)w;
+      s.h = (uint16_t)h;
+      s.wpr = (uint16_t)((w + 63) / 64);
+      const PixelType pt = parse_type(types[(size_t)i]);
+      s.type = pt == kU8 ? kU16 : pt;
+      s.stored_bits = (uint8_t)stored_bits[(size_t)i];
+      raw_off += (size_t)h * w;
+      mask_off += (size_t)h * s.wpr;
+      slots[(size_t)i].levels = (uint32_t)levels[(size_t)i];
+      slots[(size_t)i].word_off = (uint32_t)word_off;  // records back to back: odd level counts leave them 4-byte aligned
+      word_off += glcm_record_bytes(levels[(size_t)i]) / 4;
+    }
+    if (raw_off > 0xFFFFFFFFull) throw std::invalid_argument("batch exceeds 2^32 samples");
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t o_desc = 0, o_slots = up(sizeof(gpu::SliceDesc) * n), o_out = o_slots + up(sizeof(gpu::TextureSlot) * n),
+                 out_bytes = word_off * 4, total = o_out + out_bytes;
+    uint8_t* dev = (uint8_t*)scratch().get(total);
+    gpu::check_hip(hipMemcpyAsync(dev + o_desc, d.data(), sizeof(gpu::SliceDesc) * n, hipMemcpyHostToDevice, st), "H2D descriptors");
+    gpu::check_hip(hipMemcpyAsync(dev + o_slots, slots.data(), sizeof(gpu::TextureSlot) * n, hipMemcpyHostToDevice, st), "H2D slots");
+    gpu::check_hip(hipStreamSynchronize(st), "sync descriptors");
+    gpu::launch_measure_texture((const uint64_t*)planes, (const uint16_t*)raw, (const gpu::SliceDesc*)(dev + o_desc), n,
+                                (const gpu::TextureSlot*)(dev + o_slots), 0, dev + o_out, st);
+    std::vector<uint32_t> res(word_off);
+    gpu::check_hip(hipMemcpyAsync(res.data(), dev + o_out, out_bytes, hipMemcpyDeviceToHost, st), "D2H records");
+    gpu::check_hip(hipStreamSynchronize(st), "k_measure_texture");
+    py::list out;
+    for (int i = 0; i < n; ++i) out.append(texture_dict(measure::glcm_from_record(res.data() + slots[(size_t)i].word_off)));
+    return out;
+  }, py::arg("planes"), py::arg("raw"), py::arg("hs"), py::arg("ws"), py::arg("levels"), py::arg("types"),
+     py::arg("stored_bits"), py::arg("stream") = 0);
+
+  // K12's four 3D launches on a bit volume [d][h][ceil(w/64)] (int64 words) and the 16-bit samples `raw`
+  // [d][h][w]. Returns the record dict. Synchronous on `stream`.
+  m.def("k_measure_volume_texture", [](uintptr_t dilated, uintptr_t raw, int w, int h, int d, int levels,
+                                       const std::string& type, int stored_bits, uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    if (stored_bits < 1 || stored_bits > 16) throw std::invalid_argument("stored_bits must be 1..16");
+    if (levels < tcore::kMinLevels || levels > tcore::kMaxLevels) throw std::invalid_argument("levels must be 2..64");
+    if (w <= 0 || h <= 0 || d <= 0) throw std::invalid_argument("empty volume");
+    if (gpu::volume_measure_scratch_words(w, h, d) == 0)
+      throw std::invalid_argument("volume too large to measure: (w + 1) * h * d + 1 must stay below 2^32");
+    const PixelType pt = parse_type(type);
+    {
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_volume_texture();
+        preloaded.push_back(dev);
+      }
+    }
+    const size_t rec = glcm_record_bytes(levels), o_out = 0, o_acc = (rec + 255) / 256 * 256,
+                 total = o_acc + gpu::kVolumeTextureAccBytes;
+    uint8_t* dev = (uint8_t*)scratch().get(total);
+    gpu::launch_volume_texture((const uint64_t*)dilated, (const uint16_t*)raw, (size_t)w * h, w, h, d,
+                               (uint8_t)(pt == kU8 ? kU16 : pt), (uint8_t)stored_bits, levels, dev + o_acc, dev + o_out, st);
+    std::vector<uint32_t> res(rec / 4);
+    gpu::check_hip(hipMemcpyAsync(res.data(), dev + o_out, rec, hipMemcpyDeviceToHost, st), "D2H record");
+    gpu::check_hip(hipStreamSynchronize(st), "k_measure_volume_texture");
+    return texture_dict(measure::glcm_from_record(res.data()));
+  }, py::arg("dilated"), py::arg("raw"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("levels") = 32,
+     py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("stream") = 0);
 
   // ---- comm self-tests (CPU) ------------------------------------------------------------------------
   m.def("loopback_selftest", [](int n) {

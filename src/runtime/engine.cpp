@@ -174,6 +174,10 @@ struct Slot {
   // Intensity statistics (PipelineParams::measure_intensity; null without it): K11's host-mapped records.
   IntensityStats* h_intensity = nullptr;
   IntensityStats* d_intensity = nullptr;
+  // Texture (PipelineParams::measure_texture; null without it): K12's host-mapped records, cap_slices
+  // of glcm_record_bytes(texture_levels) each.
+  uint8_t* h_texture = nullptr;
+  uint8_t* d_texture = nullptr;
 };
 
 // Private fd tables for the host pool's workers. Every open and
@@ -247,6 +251,7 @@ void hip_free_all(Slot& s) {
   if (s.h_measure) (void)hipHostFree(s.h_measure);
   if (s.h_diam) (void)hipHostFree(s.h_diam);
   if (s.h_intensity) (void)hipHostFree(s.h_intensity);
+  if (s.h_texture) (void)hipHostFree(s.h_texture);
   if (s.d_ms_scratch) (void)hipFree(s.d_ms_scratch);
   for (void* p : {(void*)s.d_rgb, (void*)s.ov_jw.look, (void*)s.ov_jw.ticket, (void*)s.ov_jw.spill, (void*)s.d_ov_jd})
     if (p) (void)hipFree(p);
@@ -333,6 +338,12 @@ struct Engine::Impl {
     if (diameters_) cfg.pipe.measure = true;  // the diameters are measured on K7's labelling
     intensity_ = cfg.pipe.measure_intensity;
     if (intensity_) cfg.pipe.measure = true;  // the intensity keys extend K7's sidecar (raw_sum enters std)
+    texture_ = cfg.pipe.measure_texture;
+    if (texture_) {
+      if (cfg.pipe.texture_levels < 2 || cfg.pipe.texture_levels > 64)
+        throw std::invalid_argument("texture_levels must be 2..64 (got " + std::to_string(cfg.pipe.texture_levels) + ")");
+      cfg.pipe.measure = true;  // the texture keys extend K7's sidecar
+    }
     measure_ = cfg.pipe.measure;
     if (measure_ && cfg.host_only)
       throw std::invalid_argument("measure runs on the GPU (the K7 kernel): not available with host_only");
@@ -397,6 +408,7 @@ struct Engine::Impl {
       if (measure_) preload_measure();  // likewise: only an engine that will launch K7 loads it
       if (diameters_) preload_measure_diameters();  // and K9
       if (intensity_) preload_measure_intensity();  // and K11
+      if (texture_) preload_measure_texture();      // and K12
       d_lut_ = dmalloc<float>(kLutArenaFloats, "hipMalloc norm tables");
     }
     const double t1 = now_s();
@@ -784,6 +796,12 @@ struct Engine::Impl {
         check_hip(hipHostMalloc((void**)&s.h_intensity, sizeof(IntensityStats) * n, hipHostMallocMapped), "hipHostMalloc intensity");
         check_hip(hipHostGetDevicePointer((void**)&s.d_intensity, s.h_intensity, 0), "hipHostGetDevicePointer intensity");
         mark("intensity");
+      }
+      if (texture_) {
+        const size_t bytes = glcm_record_bytes(cfg.pipe.texture_levels) * (size_t)s.cap_slices;
+        check_hip(hipHostMalloc((void**)&s.h_texture, bytes, hipHostMallocMapped), "hipHostMalloc texture");
+        check_hip(hipHostGetDevicePointer((void**)&s.d_texture, s.h_texture, 0), "hipHostGetDevicePointer texture");
+        mark("texture");
       }
     } catch (...) {
       hip_free_all(s);
@@ -1239,6 +1257,8 @@ struct Engine::Impl {
     if (diameters_)
       launch_measure_diameters(plane(kPDilated), d_desc, nl, s.d_diam, s.d_ms_scratch, s.max_w, s.max_h, s.stream);
     if (intensity_) launch_measure_intensity(plane(kPDilated), d_raw, d_desc, nl, s.d_intensity, s.stream);
+    if (texture_)
+      launch_measure_texture(plane(kPDilated), d_raw, d_desc, nl, nullptr, cfg.pipe.texture_levels, s.d_texture, s.stream);
     if (s.any_canvas) launch_render(d_raw, s.d_f32, s.d_bits, d_stats, d_rd, ncanv, cw, ch, s.d_canvas, s.stream);
     JpegRenderSrc rsrc;
     rsrc.raw = d_raw;
@@ -1312,6 +1332,16 @@ struct Engine::Impl {
 
   // Sidecar text of the batch's slice c from its K7 record (valid once the batch's kernels are done).
   std::string measure_text(const Slot& s, int c) const {
+    if (!texture_) return measure_text_base(s, c);
+    // The texture keys after all the others: the text without the flag, then they.
+    const measure::Glcm tx = texture_record(s, c);
+    return measure::insert_global_keys(measure_text_base(s, c), measure::texture_keys(tx.c.data(), (int)tx.head.levels));
+  }
+  // K12's record of the batch's slice c (valid once the batch's kernels are done).
+  measure::Glcm texture_record(const Slot& s, int c) const {
+    return measure::glcm_from_record(s.h_texture + glcm_record_bytes(cfg.pipe.texture_levels) * (size_t)c);
+  }
+  std::string measure_text_base(const Slot& s, int c) const {
     const LoadedSlice& L = s.loaded[(size_t)s.live[(size_t)c]];
     const SliceMeasure& m = s.h_measure[c];
     if (m.components == 0xFFFFFFFFu) throw DeviceError("measure: slice exceeds the measurement scratch");
@@ -1862,6 +1892,7 @@ struct Engine::Impl {
       r.measure = s.h_measure[0];
       if (diameters_) r.diameters = s.h_diam[0];
       if (intensity_) r.intensity = s.h_intensity[0];
+      if (texture_) r.texture = texture_record(s, 0);
       r.measure_json = measure_text(s, 0);
     }
     return r;
@@ -1880,6 +1911,7 @@ struct Engine::Impl {
   // Diameters (PipelineParams::measure_diameters): K9 after K7, further keys in the sidecar.
   bool diameters_ = false;
   bool intensity_ = false;
+  bool texture_ = false;  // PipelineParams::measure_texture: K12 after K11, further keys in the sidecar
 };
 
 Engine::Engine(const EngineConfig& cfg) : impl_(std::make_unique<Impl>(cfg)) {}

@@ -168,6 +168,10 @@ struct VolumeDevice {
   // first run that asks for them and kept.
   std::unique_ptr<DevBuf> vi_acc;
   IntensityStats* h_intensity = nullptr;
+  // K12 (VolumeParams::measure_texture): the accumulators and the pinned record (for 64 levels, so any
+  // level count fits), allocated by the first run that asks for them and kept.
+  std::unique_ptr<DevBuf> vt_acc;
+  void* h_texture = nullptr;
   VolumeDevice(const VolumeInput& v)
       : w(v.w), h(v.h), d(v.d), wpr((v.w + 63) / 64), words((size_t)v.h * ((v.w + 63) / 64)),
         ps(((size_t)v.w * v.h + 7) / 8 * 8),
@@ -190,6 +194,7 @@ struct VolumeDevice {
   ~VolumeDevice() {
     if (h_lesions) (void)hipHostFree(h_lesions);
     if (h_intensity) (void)hipHostFree(h_intensity);
+    if (h_texture) (void)hipHostFree(h_texture);
     if (h_measure) (void)hipHostFree(h_measure);
     if (h_tables) (void)hipHostFree(h_tables);
     if (h_flag) (void)hipHostFree(h_flag);
@@ -345,6 +350,7 @@ struct VolumeRunner::Impl {
   bool measure_loaded = false;  // K8's code object (first measuring run)
   bool lesions_loaded = false;  // K10's code object (first run that asks for lesions)
   bool intensity_loaded = false;  // K11's code object (first run that asks for the intensity statistics)
+  bool texture_loaded = false;    // K12's code object (first run that asks for the texture)
   explicit Impl(int dev) : device(dev) {
     check_hip(hipSetDevice(device), "hipSetDevice");
     preload_kernels();  // every code object, before the first launch (kernels.h)
@@ -382,6 +388,9 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
     throw std::invalid_argument("3D lesion count must be in [1, " + std::to_string(kMaxVolumeLesions) + "] (got " +
                                 std::to_string(p.measure_lesions) + ")");
   if (p.measure_intensity && !p.measure) throw std::invalid_argument("3D intensity statistics need measure");
+  if (p.measure_texture && !p.measure) throw std::invalid_argument("3D texture needs measure");
+  if (p.measure_texture && (p.texture_levels < 2 || p.texture_levels > 64))
+    throw std::invalid_argument("3D texture levels must be 2..64 (got " + std::to_string(p.texture_levels) + ")");
   if (p.measure) {
     if (p.measure_connectivity != 6 && p.measure_connectivity != 26)
       throw std::invalid_argument("3D measurement connectivity must be 6 or 26 (got " +
@@ -422,6 +431,16 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
         check_hip(hipHostMalloc((void**)&V.h_intensity, sizeof(IntensityStats), hipHostMallocDefault), "hipHostMalloc intensity");
       }
     }
+    if (p.measure_texture) {  // K12 alike
+      if (!I.texture_loaded) {
+        preload_volume_texture();
+        I.texture_loaded = true;
+      }
+      if (!V.vt_acc) {
+        V.vt_acc = std::make_unique<DevBuf>(kVolumeTextureAccBytes);
+        check_hip(hipHostMalloc(&V.h_texture, glcm_record_bytes(64), hipHostMallocDefault), "hipHostMalloc texture");
+      }
+    }
   }
   const PipeConsts pc = make_consts(p.pipe, 2);
   check_hip(hipEventRecord(I.e0, V.stream), "event");
@@ -446,10 +465,14 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
     if (p.measure_intensity)  // K11's five launches after K8's last one
       launch_volume_intensity(V.dil.as<uint64_t>(), V.raw.as<uint16_t>(), V.ps, v.w, v.h, v.d, (uint8_t)v.type,
                               (uint8_t)v.stored_bits, V.vi_acc->p, V.h_intensity, V.stream);
+    if (p.measure_texture)  // K12's four launches after K11's
+      launch_volume_texture(V.dil.as<uint64_t>(), V.raw.as<uint16_t>(), V.ps, v.w, v.h, v.d, (uint8_t)v.type,
+                            (uint8_t)v.stored_bits, p.texture_levels, V.vt_acc->p, V.h_texture, V.stream);
     check_hip(hipEventRecord(I.e2, V.stream), "event");
     check_hip(hipEventSynchronize(I.e2), "sync");
     r.measure = *V.h_measure;
     if (p.measure_intensity) r.intensity = *V.h_intensity;
+    if (p.measure_texture) r.texture = measure::glcm_from_record(V.h_texture);
     if (p.measure_lesions) {
       const uint32_t count = *lw.out_count;
       if (count > (uint32_t)p.measure_lesions) throw DeviceError("volume lesions: count out of range");
@@ -603,7 +626,7 @@ static SlabStats slab_grow_dilate_gpu(Comm& comm, VolumeDevice& V, int nseeds, i
 VolumeResult VolumeRunner::run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p,
                                     bool want_masks, SlabStats* stats) {
   if (slab.d < 1 || slab.w < 1 || slab.h < 1) throw SliceError("empty slab");
-  if (p.measure || p.measure_lesions || p.measure_intensity)
+  if (p.measure || p.measure_lesions || p.measure_intensity || p.measure_texture)
     throw std::invalid_argument("run_slab: measuring a volume split into slabs is not supported "
                                 "(components that cross slabs need a collective)");
   check_volume_params(p.connectivity, p.dilation_size);
@@ -895,7 +918,8 @@ std::vector<std::vector<uint8_t>> golden_export(const VolumeInput& v, const std:
 std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, const VolumeParams& vp,
                                                       const RenderParams& rp, VolumeMeasure* measured = nullptr,
                                                       std::vector<VolumeLesion>* lesions = nullptr,
-                                                      IntensityStats* intensity = nullptr) {
+                                                      IntensityStats* intensity = nullptr,
+                                                      measure::Glcm* texture = nullptr) {
   const GoldenPlanes gp = golden_preprocess(v, vp);
   std::vector<Seed> seeds = vp.seeds;
   if (seeds.empty()) {
@@ -908,6 +932,7 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
   if (measured && lesions && vp.measure_lesions)
     *lesions = golden::measure_volume_lesions(dil, v, vp.measure_connectivity, vp.measure_lesions);
   if (measured && intensity && vp.measure_intensity) *intensity = golden::measure_intensity(dil, v);
+  if (measured && texture && vp.measure_texture) *texture = golden::measure_texture(dil, v, vp.texture_levels);
   return golden_export(v, gp.vals, dil, rp);
 }
 
@@ -936,6 +961,8 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
   vp.measure_connectivity = cfg.measure_volume_connectivity;
   vp.measure_lesions = cfg.measure_volume_lesions;
   vp.measure_intensity = cfg.measure_volume_intensity;
+  vp.measure_texture = cfg.measure_volume_texture;
+  vp.texture_levels = cfg.engine.pipe.texture_levels;
   const RenderParams& rp = cfg.engine.render;
   const double t_start = wall_now();
   // ---- plan on rank 0 -----------------------------------------------------------------------
@@ -1070,8 +1097,9 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       VolumeMeasure measured = {};
       std::vector<VolumeLesion> lesions;
       IntensityStats intensity = {};
+      measure::Glcm texture;
       if (cfg.cpu) {
-        files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions, &intensity);
+        files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions, &intensity, &texture);
       } else {
         VolumeResult r = runner->run(v, vp, false);
         o.sweeps = r.sweeps;
@@ -1080,6 +1108,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         measured = r.measure;
         lesions = std::move(r.lesions);
         intensity = r.intensity;
+        texture = std::move(r.texture);
         VolumeExportStats xs;
         files = runner->export_jpegs(v, vp, rp, &xs);
         o.export_s = xs.export_s;
@@ -1087,7 +1116,11 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       }
       write_planes(pp, 0, v.d, files);
       if (vp.measure) {  // the sidecar next to the planes; its text travels to rank 0 for the table
-        o.measure_json = vp.measure_intensity
+        o.measure_json = vp.measure_texture
+                             ? golden::measure_volume_json(measured, vp.measure_intensity ? &intensity : nullptr,
+                                                           vp.measure_lesions ? &lesions : nullptr, vp.measure_lesions, texture, v,
+                                                           vp.pipe.apply_rescale, vp.measure_connectivity)
+                         : vp.measure_intensity
                              ? golden::measure_volume_json(measured, intensity, vp.measure_lesions ? &lesions : nullptr,
                                                            vp.measure_lesions, v, vp.pipe.apply_rescale, vp.measure_connectivity)
                          : vp.measure_lesions
@@ -1217,7 +1250,8 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
     std::vector<VolumePatientRow> rows;
     for (size_t i = 0; i < plan.size(); ++i) rows.push_back({plan[i].id, outs[i].ok != 0, outs[i].measure_json});
     try {
-      volume_totals = write_volumes_csv(cfg.out_dir, rows, cfg.measure_volume_intensity);
+      volume_totals = write_volumes_csv(cfg.out_dir, rows, cfg.measure_volume_intensity,
+                                        cfg.measure_volume_texture ? cfg.engine.pipe.texture_levels : 0);
     } catch (const std::exception& e) {
       std::cerr << "Error writing volumes.csv: " << e.what() << std::endl;
     }
