@@ -18,9 +18,11 @@ def main(argv=None):
     ap.add_argument("--series", required=True)
     ap.add_argument("--ball", action="store_true", help="digital ball instead of the 7x7x7 cube")
     ap.add_argument("--measure", action="store_true",
-                    help="also print the volumetry of the dilated volume (K8: mm3, components, cavities, tunnels)")
+                    help="also print the volumetry of the dilated volume (K8: mm3, components, cavities, tunnels) and "
+                         "the largest lesion's diameters (K10 + K13)")
     a = ap.parse_args(argv)
-    vp = nm.VolumePipeline(nm.PipelineConfig(se_shape=int(a.ball)), connectivity=6, dilation=7, measure=a.measure)
+    vp = nm.VolumePipeline(nm.PipelineConfig(se_shape=int(a.ball)), connectivity=6, dilation=7, measure=a.measure,
+                           measure_lesions=int(a.measure), measure_diameters=a.measure)
     res = vp.run_series(a.series)
     band = res["band"]
     region, dil = vp.golden(band, vp.default_seeds(band))
@@ -33,6 +35,10 @@ def main(argv=None):
         print(f"volume {m['volume_ml']:.3f} ml ({m['volume_vox']} voxels, spacing_z {m['spacing_z']} mm from "
               f"{m['spacing_z_source']}), surface {m['surface_mm2']:.1f} mm2, {m['components']} component(s), "
               f"{m['cavities']} cavities, {m['tunnels']} tunnels")
+        for les in m["lesions"][:1]:
+            print(f"largest lesion: {les['voxels']} voxels, 3D diameter {les['diameter_3d_mm']:.1f} mm, axial "
+                  f"{les['axial_major_mm']:.1f} x {les['axial_perp_mm']:.1f} mm in plane {les['axial_z']} "
+                  f"(spacing {m['diameters_spacing_um']} um)")
     return 0 if same else 1
 
 

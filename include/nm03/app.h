@@ -95,6 +95,10 @@ struct AppConfig {
   // --measure-volume-lesions N (implies --measure-volume): the sidecar also lists the N largest
   // lesions (nm03/measure.h VolumeLesion) and rank 0 writes <out>/lesions.csv; 0 = off, else 1 … 64.
   int measure_volume_lesions = 0;
+  // --measure-volume-diameters (3d): --measure-volume and --measure-volume-lesions (N = 1 when none is given)
+  // plus every reported lesion's 3D major diameter, largest axial diameter and its perpendicular (nm03/measure.h
+  // VolumeLesionDiameters): keys in the sidecar's lesion objects and columns in lesions.csv.
+  bool measure_volume_diameters = false;
   // --measure-intensity with --mode 3d (implies --measure-volume): the volume sidecar and volumes.csv
   // also carry the intensity keys (nm03/measure.h IntensityStats). In 2D the flag is
   // engine.pipe.measure_intensity.
@@ -188,6 +192,8 @@ struct VolumeTotals {
   int64_t lesions = -1;  // --measure-volume-lesions: rows of lesions.csv over the job's measured patients (−1: not asked for)
   bool intensity = false;  // --measure-intensity: the table has the intensity columns
   int texture_levels = 0;  // --measure-texture: the table has the texture columns (0: not asked for)
+  bool diameters = false;  // --measure-volume-diameters: lesions.csv has the diameter columns
+  double diameter_3d_mm_max = 0;  // the largest diameter_3d_mm over the job's lesions
 };
 // `intensity` (--measure-intensity): the 13 intensity keys' columns after `mean`; a sidecar without them
 // (written earlier without the flag) leaves them empty.
@@ -198,7 +204,11 @@ VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<Vo
 // then one row per reported lesion (patient, lesion = its 0-based rank, then the lesion object's fields
 // with first and bbox flattened); a failed patient has one row with its status name in `lesion` and
 // empty fields. Returns the number of lesion rows.
-int64_t write_lesions_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows);
+// `diameters` (--measure-volume-diameters): the 22 diameter keys' columns after all of those, arrays flattened; a
+// lesion without them (a sidecar written earlier without the flag) leaves them empty, and without `diameters` a
+// lesion that has them is written without. `totals` (optional) receives diameters / diameter_3d_mm_max.
+int64_t write_lesions_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows, bool diameters = false,
+                          VolumeTotals* totals = nullptr);
 std::string volume_totals_json(const VolumeTotals& t);  // the --json record's "measure_volume" object
 
 // Number of GPUs visible to this process, counted WITHOUT initialising HIP (KFD topology +

@@ -156,6 +156,12 @@ std::vector<VolumeLesion> measure_volume_lesions(const std::vector<uint8_t>& dil
 // The sidecar text with the lesion keys (the matching measure::volume_to_json overload).
 std::string measure_volume_json(const VolumeMeasure& m, const std::vector<VolumeLesion>& lesions, int max_lesions,
                                 const VolumeInput& v, bool apply_rescale, int connectivity);
+// The lengths (nm03/measure.h VolumeLesionDiameters) of the same lesions in the same order, for a
+// d × h × w mask and the spacing `um` in integer micrometres (x, y, z). Independent of the K13 kernels:
+// a flood fill per component, then plain loops over the pairs of its voxels with an open 6-face (of all
+// its voxels when they are few) — not the kernels' row extremes.
+std::vector<VolumeLesionDiameters> measure_volume_diameters(const std::vector<uint8_t>& dilated, int w, int h, int d,
+                                                            int connectivity, int max_lesions, const uint32_t um[3]);
 
 struct SliceResult {
   std::vector<float> clipped, median, sharpened;

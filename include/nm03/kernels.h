@@ -212,11 +212,19 @@ using nm03::volume_measure_scratch_words;
 constexpr int kVolumeMeasureAccWords = 32;
 // `lesions` (optional, --measure-volume-lesions): the K10 launches below are enqueued between the two
 // passes; null leaves the twelve launches as they are.
+// `diameters` (optional, --measure-volume-diameters): the K13 launches follow K10's.
+struct VolumeDiametersWork {
+  void* work = nullptr;                  // volume_diameters_work_bytes(w, h, d, N) of device memory, no initialisation needed
+  VolumeLesionDiameters* out = nullptr;  // N records (device, pinned or host-mapped memory); those past the count are zero
+  uint32_t spacing_um[3] = {1000u, 1000u, 1000u};  // x, y, z in integer micrometres, each ≥ 1
+  bool brute_force = false;              // compare every tile pair (the records are the same; for tests and timing)
+};
 struct VolumeLesionWork {
   int max_lesions = 0;            // N, 1..kMaxVolumeLesions
   void* work = nullptr;           // volume_lesions_work_bytes(w, h, d, N) of device memory, no initialisation needed
   VolumeLesion* out = nullptr;    // N records (device, pinned or host-mapped memory); those past the count are zero
   uint32_t* out_count = nullptr;  // the reported count, min(N, components)
+  const VolumeDiametersWork* diameters = nullptr;  // null = off: the launch sequence stays as it is
 };
 void launch_volume_measure(const uint64_t* dilated, const uint64_t* region, const uint16_t* raw, size_t raw_plane_stride,
                            int w, int h, int d, uint8_t type, uint8_t stored_bits, int connectivity, uint32_t* scratch,
@@ -240,6 +248,26 @@ void launch_volume_lesions(const uint64_t* dilated, const uint16_t* raw, size_t 
 // Loads K10's code object on the current device: only a VolumeRunner's first run that asks for lesions
 // and the Python op load it.
 void preload_volume_lesions();
+
+// K13 (k13_volume_diameters.hip): the VolumeLesionDiameters records (nm03/measure.h) of the lesions K10
+// chose, in K10's order: the 3D major diameter, the largest axial diameter and its perpendicular in
+// integer micrometres. launch_volume_measure enqueues it directly after K10 when
+// VolumeLesionWork::diameters is set, before the complement pass overwrites the labelling. Seven launches
+// on `stream`: init, rows (the extremes of every lesion row, a thread per word), tiles (boxes of 128
+// rows), bound (one workgroup per lesion), planes (the axial bound, a wave per plane), pairs (a fixed grid
+// over the tile pairs, skipping those whose boxes lie strictly below the bounds), final. It reads `scratch`, K10's chosen roots and bounding boxes
+// in `lesions.work`, and writes only its own work buffer and records (plain vector stores). No host
+// round trip, no allocation. Throws DeviceError before any launch when a (dim − 1) · spacing_um reaches
+// 2^31, naming the product. The work buffer is 8 · N · h · d bytes for the row table plus the tile boxes
+// and the partial slots.
+size_t volume_diameters_work_bytes(int w, int h, int d, int max_lesions);
+// The checks of launch_volume_diameters alone (launch_volume_measure makes them before its first launch).
+void validate_volume_diameters(const uint64_t* dilated, int w, int h, int d, const uint32_t* scratch,
+                               const VolumeLesionWork& lesions);
+void launch_volume_diameters(const uint64_t* dilated, int w, int h, int d, const uint32_t* scratch,
+                             const VolumeLesionWork& lesions, hipStream_t stream);
+// Loads K13's code object on the current device: only a run that asks for diameters and the Python op load it.
+void preload_volume_diameters();
 
 // K11 (k11_intensity.hip), 2D: the IntensityStats record (nm03/measure.h) of the samples under every
 // slice's `dilated` plane, one workgroup per slice, slices of different sizes in one launch

@@ -172,6 +172,35 @@ struct alignas(64) VolumeLesion {
 static_assert(sizeof(VolumeLesion) == 128, "VolumeLesion layout");
 constexpr int kMaxVolumeLesions = 64;
 
+// The lengths of one lesion (K13, k13_volume_diameters.hip): one record per VolumeLesion record, in the
+// same order. Exact integers. The spacing enters as integer micrometres u = max(1, llround(mm · 1000))
+// per axis (volume_spacing_um); every (dim − 1) · u stays below 2^31, so a squared distance is a sum of
+// three squares below 2^62 and exact in 64 bits.
+//   major              the pair (a, b) of lesion voxels, centre to centre, that maximises
+//                      major_um2 = (dx·ux)² + (dy·uy)² + (dz·uz)²; a does not follow b in raster
+//                      (z, y, x) order; a tie goes to the smallest (za, ya, xa, zb, yb, xb)
+//   axial              over every plane z and every pair of the lesion's voxels of that plane (connected
+//                      in the plane or not), the pair that maximises axial_um2 = (dx·ux)² + (dy·uy)²; a tie
+//                      goes to the smallest z, then the smallest (ya, xa, yb, xb)
+//   axial_perp         with (dx, dy) = b − a of the axial pair in index units, every lesion voxel of plane
+//                      axial_z projects to p = −dy·x + dx·y; axial_perp_extent = max p − min p, and c / d
+//                      are the smallest (y, x) voxels at the minimum / maximum. (The physical normal is
+//                      (−dy·uy, dx·ux), whose product with (x·ux, y·uy) is ux·uy·p.)
+// A one-voxel lesion has a = b = c = d and zeros; a lesion with one voxel per plane has axial_um2 = 0
+// in its first plane. Worked example: the box x 0…9, y 0…3, z 0…2 at 1 mm gives major_um2 = 94 000 000,
+// major = [0,0,0, 9,3,2] (four body diagonals tie), axial_z = 0, axial_um2 = 90 000 000,
+// axial = [0,0, 9,3], axial_perp_extent = 54, axial_perp = [9,0, 0,3].
+struct alignas(64) VolumeLesionDiameters {
+  uint64_t major_um2, axial_um2;
+  int64_t axial_perp_extent;
+  int32_t major[6];       // xa, ya, za, xb, yb, zb
+  int32_t axial_z;
+  int32_t axial[4];       // xa, ya, xb, yb
+  int32_t axial_perp[4];  // xc, yc, xd, yd
+  int32_t pad[11];
+};
+static_assert(sizeof(VolumeLesionDiameters) == 128, "VolumeLesionDiameters layout");
+
 // Euler number of a bit volume from window counts over the zero-padded volume: n3 = set voxels,
 // n2 = pairs of face-adjacent positions, n1 = 2×2 windows (three orientations), n0 = 2×2×2 windows.
 // At 26-connectivity a pair or window counts when ANY of its voxels is set and
@@ -267,6 +296,36 @@ std::string volume_to_json(const VolumeMeasure& m, const VolumeLesion* lesions, 
 // union-find, one word after the other. Returns the reported count, min(max_lesions, components).
 int volume_lesions_words(const uint64_t* dilated, const uint16_t* raw, size_t raw_plane_stride, int w, int h, int d,
                          int wpr, uint8_t type, uint8_t stored_bits, int connectivity, int max_lesions, VolumeLesion* out);
+
+// The spacing of a volume in integer micrometres, max(1, llround(mm · 1000)) per axis (x, y, z).
+void volume_spacing_um(double spacing_x, double spacing_y, double spacing_z, uint32_t um[3]);
+// Empty when every (dim − 1) · u stays below 2^31, else the message that names the offending product.
+std::string volume_diameters_extent_error(int w, int h, int d, const uint32_t um[3]);
+
+// The VolumeLesionDiameters records of the `max_lesions` largest components of a bit volume computed on
+// the host with the K13 kernels' logic (nm03/volume_diameters_core.h: the row extremes of every in-word
+// stretch, the direction bound, the tile boxes and the tile rule) on K8's run union-find and K10's
+// selection, one word / tile pair after the other. `brute_force` compares every tile pair. Returns the
+// reported count; `skipped` (optional) receives the number of tile pairs the bound skipped.
+int volume_diameters_words(const uint64_t* dilated, int w, int h, int d, int wpr, int connectivity, int max_lesions,
+                           const uint32_t um[3], bool brute_force, VolumeLesionDiameters* out,
+                           uint64_t* skipped = nullptr);
+
+// The sidecar text with --measure-volume-diameters: `text` (any volume_to_json text with the lesion keys)
+// with one top-level key directly before lesions_max — diameters_spacing_um [ux, uy, uz] — and inside
+// lesion object i, after `mean`, the integers of dia[i] in fixed order — major_um2, major
+// [xa, ya, za, xb, yb, zb], axial_z, axial_um2, axial [xa, ya, xb, yb], axial_perp_extent, axial_perp
+// [xc, yc, xd, yd] — then the derived doubles (%.9g), from the integers and the quantised spacing alone:
+//   diameter_3d_mm = √major_um2 / 1000, axial_major_mm = √axial_um2 / 1000,
+//   axial_perp_mm = ux · uy · axial_perp_extent / √axial_um2 / 1000 (0 when axial_um2 is 0),
+//   axial_bidimensional_mm2 = axial_major_mm · axial_perp_mm
+// Removing the new keys gives `text` back byte for byte. `count` must be the text's lesion count.
+std::string insert_diameter_keys(std::string text, const VolumeLesionDiameters* dia, int count, const uint32_t um[3]);
+// The four doubles of a record.
+struct DiameterLengths {
+  double diameter_3d_mm, axial_major_mm, axial_perp_mm, axial_bidimensional_mm2;
+};
+DiameterLengths diameter_lengths(const VolumeLesionDiameters& r, const uint32_t um[3]);
 
 inline const char* volume_sidecar_name() { return "volume_measure.json"; }
 

@@ -62,6 +62,8 @@ struct VolumeResult {
   // VolumeParams::measure_lesions: the K10 records of the largest components, largest first
   // (min(measure_lesions, measure.components) of them).
   std::vector<VolumeLesion> lesions;
+  // VolumeParams::measure_diameters: the K13 records of the same lesions, in the same order.
+  std::vector<VolumeLesionDiameters> diameters;
   // VolumeParams::measure_intensity: the K11 record of the samples under the dilated volume.
   IntensityStats intensity = {};
   // VolumeParams::measure_texture: the K12 record of the samples under the dilated volume.
@@ -84,6 +86,12 @@ struct VolumeParams {
   // With measure: also one record per lesion for the N largest components (K10, nm03/measure.h
   // VolumeLesion); 0 = off, else 1 … kMaxVolumeLesions.
   int measure_lesions = 0;
+  // With measure and measure_lesions ≥ 1: also the lengths of every reported lesion (K13, nm03/measure.h
+  // VolumeLesionDiameters), maximised in `spacing_um` (x, y, z in integer micrometres,
+  // measure::volume_spacing_um of the volume's spacing). A (dim − 1) · spacing_um ≥ 2^31 is refused.
+  bool measure_diameters = false;
+  uint32_t spacing_um[3] = {1000u, 1000u, 1000u};
+  bool diameters_brute_force = false;  // K13 compares every tile pair: the same records, for tests and timing
   // With measure: also the first-order intensity statistics (K11, nm03/measure.h IntensityStats).
   bool measure_intensity = false;
   // With measure: also the grey-level co-occurrence matrix at `texture_levels` (2 … 64) grey levels over
@@ -104,7 +112,8 @@ class VolumeRunner {
   // With p.measure the K8 kernels run after the segmentation (first use loads their code object and
   // allocates their scratch, kept like the other buffers); without it nothing of K8 is touched. The
   // same holds for p.measure_lesions and K10, for p.measure_intensity and K11 (after K8's last launch)
-  // and for p.measure_texture and K12 (after K11's).
+  // and for p.measure_texture and K12 (after K11's), and for p.measure_diameters and K13 (directly after
+  // K10's launches; its work buffer is sized by the N asked for and regrown when a later run asks for more).
   VolumeResult run(const VolumeInput& v, const VolumeParams& p, bool want_masks);
   // After run() on the same volume: the 2·d exported JPEG files of the 3D cohort mode, in plane
   // order (original, processed), rendered and encoded on the GPU (K3/K4) from the volume still on
@@ -116,7 +125,7 @@ class VolumeRunner {
   // coordinates. Preprocesses the slab's planes, runs the global region-growing fixpoint and the
   // halo cube dilation with the other ranks of `comm` (collective), leaving the slab on the device:
   // export_jpegs(slab, ...) then exports its planes. Masks (when requested) are the slab's.
-  // p.measure, p.measure_lesions, p.measure_intensity or p.measure_texture throws std::invalid_argument: components that cross slabs would
+  // p.measure, p.measure_lesions, p.measure_diameters, p.measure_intensity or p.measure_texture throws std::invalid_argument: components that cross slabs would
   // need a collective.
   VolumeResult run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p, bool want_masks,
                         struct SlabStats* stats = nullptr);

@@ -14,7 +14,11 @@ volume: the result gains `intensity` (the record's integers) and `measure_json` 
 keys after `mean` (before the lesion keys). With `measure_texture=True` (needs `measure`) the K12 kernels
 also report the grey-level co-occurrence matrix of those samples at `texture_levels` grey levels over the
 thirteen forward directions: the result gains `texture` (the header integers plus `glcm`) and
-`measure_json` carries the 23 texture keys after the intensity keys (before the lesion keys)."""
+`measure_json` carries the 23 texture keys after the intensity keys (before the lesion keys). With
+`measure_diameters=True` (needs `measure` and `measure_lesions` ≥ 1) the K13 kernels also report every
+lesion's 3D major diameter, largest axial diameter and its perpendicular, maximised in the spacing quantised
+to integer micrometres: the result gains `diameters` (a list of dicts of each record's integers, in the
+lesions' order) and `measure_json` carries `diameters_spacing_um` and the diameter keys of every lesion."""
 import numpy as np
 
 from .._native import native
@@ -30,7 +34,7 @@ def _meta_args(meta):
 class VolumePipeline:
     def __init__(self, config: PipelineConfig = None, connectivity: int = 6, dilation: int = 7, measure: bool = False,
                  measure_connectivity: int = 26, measure_lesions: int = 0, measure_intensity: bool = False, measure_texture: bool = False,
-                 texture_levels: int = 32):
+                 texture_levels: int = 32, measure_diameters: bool = False):
         self.config = config or PipelineConfig()
         self.connectivity = connectivity
         self.dilation = dilation
@@ -52,6 +56,9 @@ class VolumePipeline:
             raise ValueError("measure_texture needs measure=True")
         if self.measure_texture and not 2 <= self.texture_levels <= 64:
             raise ValueError(f"texture_levels must be 2..64 (got {texture_levels})")
+        self.measure_diameters = bool(measure_diameters)
+        if self.measure_diameters and not (self.measure and self.measure_lesions >= 1):
+            raise ValueError("measure_diameters needs measure=True and measure_lesions >= 1")
         self._runners = {}  # device -> native VolumeRunner (buffers/stream reused across volumes)
 
     def default_seeds(self, volume):
@@ -74,7 +81,8 @@ class VolumePipeline:
                           measure_connectivity=self.measure_connectivity, spacing=[float(v) for v in spacing],
                           spacing_z_source=str(spacing_z_source), measure_lesions=self.measure_lesions,
                           measure_intensity=self.measure_intensity, measure_texture=self.measure_texture,
-                          texture_levels=self.texture_levels, **_meta_args(meta))
+                          texture_levels=self.texture_levels, measure_diameters=self.measure_diameters,
+                          **_meta_args(meta))
 
     def run_series(self, series_dir, seeds=None, device=None):
         """A DICOM series directory as one volume (utils.read_series: the reference's file-number
@@ -115,7 +123,29 @@ class VolumePipeline:
         one and the tuple has a third member, the list of lesion dicts (`run`'s `lesions`). With
         measure_intensity the text carries the intensity keys and the tuple's last member is the intensity
         dict (`run`'s `intensity`). With measure_texture the text carries the texture keys too and the
-        texture dict (`run`'s `texture`) comes last of all."""
+        texture dict (`run`'s `texture`) comes last of all. With measure_diameters the text carries the diameter
+        keys as well and the list of diameter dicts (`run`'s `diameters`) is a further last member."""
+        out = self._golden_measure(dilated, region, raw, spacing, spacing_z_source, meta)
+        if not self.measure_diameters:
+            return out
+        n = native()
+        um = n.volume_spacing_um(float(np.float32(spacing[0])), float(np.float32(spacing[1])), float(spacing[2]))
+        dia = n.golden_measure_volume_diameters(np.ascontiguousarray(dilated, dtype=np.uint8), self.measure_lesions, list(um),
+                                                self.measure_connectivity)
+        a = _meta_args(meta)
+        d, h, w = np.asarray(dilated).shape
+        kw = {}
+        if self.measure_intensity:
+            kw["intensity"] = out[3]
+        if self.measure_texture:
+            kw["texture"] = out[-1]
+        text = n.volume_measure_to_json(out[0], w, h, d, float(spacing[0]), float(spacing[1]), float(spacing[2]),
+                                        str(spacing_z_source), a["slope"], a["intercept"],
+                                        bool(self.config.pipeline_params().apply_rescale), self.measure_connectivity,
+                                        out[2], self.measure_lesions, diameters=dia, **kw)
+        return (out[0], text) + tuple(out[2:]) + (dia,)
+
+    def _golden_measure(self, dilated, region, raw, spacing, spacing_z_source, meta):
         n = native()
         a = _meta_args(meta)
         d, h, w = np.asarray(dilated).shape

@@ -1,6 +1,6 @@
 """torch-tensor entry points of the gfx950 kernels (K1a median, K1b sharpen+band, K2 SRG+morph,
 K3 overlay render, K4 JPEG (gray and colour), K5 3D SRG + cube / ball dilation + per-plane border, K6 threshold, K7 mask measurements,
-K8 volume measurements, K10 per-lesion volume measurements,
+K8 volume measurements, K10 per-lesion volume measurements, K13 per-lesion 3D and axial diameters,
 K9 lesion diameters, K11 intensity percentiles and Σ v² of slices and volumes, K12 grey-level co-occurrence
 matrices of slices and volumes) and
 plain-PyTorch fp32 references of the same ops (ops.reference).
@@ -10,7 +10,8 @@ the native launcher and returns torch tensors — there is no CPU/Python fallbac
 native extension the call raises.
 """
 from .kernels import (border3d, dilate3d, jpeg_encode, jpeg_encode_rgb, measure_diameters, measure_intensity,  # noqa: F401
-                      measure_mask, measure_texture, measure_volume, measure_volume_intensity, measure_volume_lesions,
+                      measure_mask, measure_texture, measure_volume, measure_volume_diameters, measure_volume_intensity,
+                      measure_volume_lesions,
                       measure_volume_texture, median2d, pack_bits,
                       region_grow, region_grow3d, render_overlay, sharpen_band, threshold, unpack_bits)
 from . import reference  # noqa: F401

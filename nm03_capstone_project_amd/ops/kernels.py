@@ -366,6 +366,46 @@ def measure_volume_lesions(dilated, region, raw, max_lesions, connectivity=26, p
     return rec, lesions
 
 
+def measure_volume_diameters(dilated, max_lesions, spacing_um=(1000, 1000, 1000), connectivity=26, brute_force=False):
+    """The lengths of the `max_lesions` (1 … 64) largest connected components of a volume mask (K13,
+    nm03/measure.h VolumeLesionDiameters) → list of dicts of exact integers, in measure_volume_lesions'
+    order: major_um2 and major [xa, ya, za, xb, yb, zb] (the pair of lesion voxels at the largest distance,
+    squared micrometres), axial_z, axial_um2 and axial [xa, ya, xb, yb] (the largest distance inside one
+    plane), axial_perp_extent and axial_perp [xc, yc, xd, yd] (the extent of that plane's voxels on the
+    normal of b − a, in index units, and the voxels at its ends). `spacing_um` is (ux, uy, uz) in integer
+    micrometres; the maximisation is exact, ties go to the pair that comes first in raster order.
+
+    `dilated` is a bool CUDA tensor [D, H, W]. Runs K8's mask pass, K10's selection and K13's seven launches.
+    `brute_force` compares every tile pair instead of skipping those the bound excludes: the same records.
+    A volume with (dim − 1)·u ≥ 2³¹ on an axis raises."""
+    _check_conn3d(connectivity)
+    if not 1 <= int(max_lesions) <= 64:
+        raise ValueError("max_lesions must be 1..64")
+    if dilated.dim() != 3:
+        raise ValueError("dilated must be [D, H, W]")
+    if not dilated.is_cuda:
+        raise ValueError("masks must be CUDA (HIP) tensors")
+    um = [int(v) for v in spacing_um]
+    if len(um) != 3 or min(um) < 1:
+        raise ValueError("spacing_um must be three integers of at least 1")
+    d, h, w = (int(v) for v in dilated.shape)
+    if d < 1 or h < 1 or w < 1:
+        raise ValueError("empty volume")
+    for dim, u, name in ((w, um[0], "(w - 1) * ux"), (h, um[1], "(h - 1) * uy"), (d, um[2], "(d - 1) * uz")):
+        if (dim - 1) * u >= 2 ** 31:
+            raise ValueError(f"the volume is too long to measure in micrometres: {name} = {dim - 1} * {u} must stay "
+                             "below 2^31")
+    dw = pack_bits(dilated.bool()).contiguous()
+    # K8 and K10 also read the samples under the mask; their values do not enter the diameters
+    samples = torch.zeros((d, h, w), dtype=torch.int16, device=dw.device)
+    _, diameters, rest = native().k_measure_volume_diameters(dw.data_ptr(), samples.data_ptr(), w, h, d, int(max_lesions), um,
+                                                             int(connectivity), bool(brute_force), _stream())
+    zero = {k: ([0] * len(v) if isinstance(v, list) else 0) for r in rest[:1] for k, v in r.items()}
+    if any(r != zero for r in rest):  # the kernel's contract: records past the count are zero
+        raise RuntimeError("measure_volume_diameters: a record past the count is not zero")
+    return diameters
+
+
 def measure_intensity(dilated, raw, pixel_type="u16", stored_bits=16):
     """First-order intensity statistics of the stored samples of `raw` under masks (K11, nm03/measure.h
     IntensityStats) → list of dicts of the record's exact integers: count (= area_px), raw_sum_sq (Σ v²)

@@ -149,11 +149,14 @@ def read_volume_lesions(out_dir):
     """Rows of <out_dir>/lesions.csv (written by the 3D CLI with --measure-volume-lesions) as dicts keyed
     by the header: one per reported lesion, patients in plan order, `lesion` the 0-based rank (largest
     first). A failed patient has one row with its status name in `lesion` and None in every field.
-    Integer columns come back as int, the derived ones as float."""
+    Integer columns come back as int, the derived ones as float. With --measure-volume-diameters the table
+    also has the diameter columns (major_um2 … axial_perp_yd as int, diameter_3d_mm, axial_major_mm,
+    axial_perp_mm and axial_bidimensional_mm2 as float; None for a lesion measured without the flag)."""
     import csv
     import os
     floats = {"volume_mm3", "volume_ml", "surface_mm2", "equivalent_diameter_mm", "centroid_x", "centroid_y", "centroid_z",
-              "centroid_x_mm", "centroid_y_mm", "centroid_z_mm", "mean"}
+              "centroid_x_mm", "centroid_y_mm", "centroid_z_mm", "mean", "diameter_3d_mm", "axial_major_mm", "axial_perp_mm",
+              "axial_bidimensional_mm2"}
     rows = []
     with open(os.path.join(out_dir, "lesions.csv"), newline="") as f:
         for r in csv.DictReader(f):

@@ -2,6 +2,7 @@
 // (<out>/<patient>/<stem>_measure.json, measure::to_json) in patient / slice order and writes
 // <out>/measurements.csv. Reading the files — not gathering records over the comm — keeps the
 // table identical at any rank count and batch size, and under --resume.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -109,10 +110,21 @@ const char* const kLesionColumns[] = {
     "centroid_x", "centroid_y", "centroid_z", "centroid_x_mm", "centroid_y_mm", "centroid_z_mm", "mean"};
 constexpr size_t kNumLesionColumns = sizeof(kLesionColumns) / sizeof(kLesionColumns[0]);
 const char* const kLesionsKey = ",\"lesions_max\":";
+// --measure-volume-diameters: the columns after those — a lesion object's diameter keys in their order, arrays flattened.
+const char* const kLesionDiameterColumns[] = {
+    "major_um2",     "major_xa",      "major_ya",         "major_za",      "major_xb",      "major_yb",      "major_zb",
+    "axial_z",       "axial_um2",     "axial_xa",         "axial_ya",      "axial_xb",      "axial_yb",      "axial_perp_extent",
+    "axial_perp_xc", "axial_perp_yc", "axial_perp_xd",    "axial_perp_yd", "diameter_3d_mm", "axial_major_mm", "axial_perp_mm",
+    "axial_bidimensional_mm2"};
+constexpr size_t kNumLesionDiameterColumns = sizeof(kLesionDiameterColumns) / sizeof(kLesionDiameterColumns[0]);
+constexpr size_t kLesionColDiameter3d = kNumLesionColumns + 18;
+const char* const kDiametersSpacingKey = ",\"diameters_spacing_um\":";
 
-// The volume sidecar's text without the lesion keys: what --measure-volume alone writes.
+// The volume sidecar's text without the lesion keys (and the diameters' spacing key in front of them): what
+// --measure-volume alone writes.
 std::string without_lesions(const std::string& text) {
-  const size_t at = text.find(kLesionsKey);
+  size_t at = text.find(kDiametersSpacingKey);
+  if (at == std::string::npos) at = text.find(kLesionsKey);
   return at == std::string::npos ? text : text.substr(0, at) + "}\n";
 }
 
@@ -198,18 +210,27 @@ std::string volume_totals_json(const VolumeTotals& t) {
   std::string s = buf;
   if (t.intensity) s.insert(s.size() - 1, ", \"intensity\": true");
   put_texture_totals(s, t.texture_levels);
+  if (t.diameters) {
+    std::snprintf(buf, sizeof buf, ", \"diameters\": true, \"diameter_3d_mm_max\": %.9g", t.diameter_3d_mm_max);
+    s.insert(s.size() - 1, buf);
+  }
   return s;
 }
 
-int64_t write_lesions_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows) {
+int64_t write_lesions_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows, bool diameters,
+                          VolumeTotals* totals) {
   int64_t total = 0;
+  double d3max = 0;
+  const size_t ncols = kNumLesionColumns + (diameters ? kNumLesionDiameterColumns : 0);
   std::ostringstream o;
   o << "patient,lesion";
   for (const char* c : kLesionColumns) o << "," << c;
+  if (diameters)
+    for (const char* c : kLesionDiameterColumns) o << "," << c;
   o << "\n";
   auto empty_row = [&](const std::string& id, const char* status) {
     o << id << "," << status;
-    for (size_t c = 0; c < kNumLesionColumns; ++c) o << ",";
+    for (size_t c = 0; c < ncols; ++c) o << ",";
     o << "\n";
   };
   for (const auto& r : rows) {
@@ -229,7 +250,12 @@ int64_t write_lesions_csv(const std::string& out_root, const std::vector<VolumeP
       const size_t end = r.sidecar.find('}', i);
       if (end == std::string::npos) break;
       std::vector<std::string> v;
-      if (!parse_sidecar(r.sidecar.substr(i, end - i + 1), v, kNumLesionColumns)) break;
+      // A lesion object has the diameter keys or not, whatever this run asked for (a sidecar of an earlier run).
+      const std::string obj = r.sidecar.substr(i, end - i + 1);
+      if (!parse_sidecar(obj, v, kNumLesionColumns + kNumLesionDiameterColumns) && !parse_sidecar(obj, v, kNumLesionColumns)) break;
+      if (diameters && v.size() == ncols && !v[kLesionColDiameter3d].empty())
+        d3max = std::max(d3max, std::strtod(v[kLesionColDiameter3d].c_str(), nullptr));
+      v.resize(ncols);
       o << r.id << "," << rank++;
       for (const auto& x : v) o << "," << x;
       o << "\n";
@@ -241,6 +267,7 @@ int64_t write_lesions_csv(const std::string& out_root, const std::vector<VolumeP
   std::ofstream f(cohort::with_slash(out_root) + "lesions.csv", std::ios::binary | std::ios::trunc);
   f.write(text.data(), (std::streamsize)text.size());
   if (!f) throw std::runtime_error("Cannot write " + cohort::with_slash(out_root) + "lesions.csv");
+  if (totals) totals->diameters = diameters, totals->diameter_3d_mm_max = d3max;
   return total;
 }
 

@@ -81,6 +81,9 @@ void usage(const std::string& which) {
             << "  --measure-volume-lesions N  3d: --measure-volume plus one record per lesion for the N largest connected\n"
             << "                         components (1..64; voxels, first voxel, bbox, sums, surface, intensities), largest\n"
             << "                         first: keys lesions_max / lesions in the sidecar, and <out>/lesions.csv\n"
+            << "  --measure-volume-diameters  3d: --measure-volume-lesions (N = 1 unless given) plus every lesion's 3D major\n"
+            << "                         diameter, largest axial diameter and its perpendicular, maximised in micrometres:\n"
+            << "                         keys in the sidecar's lesion objects, columns in <out>/lesions.csv\n"
             << "  --mode 2d|3d           3d: whole series as a volume (SRG 6-conn + cube dilation)\n"
             << "  --split-volume         3d: each volume split into z-slabs over all ranks (halo exchange)\n"
             << "  --input FILE           test_pipeline: slice to process\n"
@@ -302,6 +305,7 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
       c.measure_volume_lesions = (int)n;
       c.measure_volume = true;
     }
+    else if (a == "--measure-volume-diameters") c.measure_volume_diameters = true;
     else if (a == "--measure-connectivity") {
       const std::string v = val();
       if (v != "4" && v != "8") {
@@ -368,6 +372,18 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
   if (c.engine.pipe.measure && c.mode == "3d") {
     std::cerr << "--measure is not available with --mode 3d (use --measure-volume)" << std::endl;
     std::exit(2);
+  }
+  if (c.measure_volume_diameters && c.mode != "3d") {
+    std::cerr << "--measure-volume-diameters needs --mode 3d (per-slice diameters: --measure-diameters)" << std::endl;
+    std::exit(2);
+  }
+  if (c.measure_volume_diameters && c.split_volume) {
+    std::cerr << "--measure-volume-diameters is not available with --split-volume" << std::endl;
+    std::exit(2);
+  }
+  if (c.measure_volume_diameters) {  // implies --measure-volume, and --measure-volume-lesions 1 when no N is given
+    c.measure_volume = true;
+    if (!c.measure_volume_lesions) c.measure_volume_lesions = 1;
   }
   if (c.measure_volume_lesions && c.mode != "3d") {
     std::cerr << "--measure-volume-lesions needs --mode 3d" << std::endl;

@@ -42,6 +42,8 @@ int main(int argc, char** argv) {
   bool measure_volume = false;  // volume: also K8 (the volumetry of the dilated volume) per run
   int measure_volume_conn = 26;
   int measure_volume_lesions = 0;  // volume: also K10 (one record per lesion, the N largest) per run
+  bool measure_volume_diameters = false;  // volume: also K13 (every reported lesion's diameters) per run
+  bool diameters_brute_force = false;     // volume: K13 compares every tile pair (the same records; for comparison)
   bool measure_texture = false;    // cohort with --measure / volume with --measure-volume: also K12 (co-occurrence matrix)
   int texture_levels = 32;
   bool measure_intensity = false;  // cohort with --measure / volume with --measure-volume: also K11 (percentiles, sum of squares)
@@ -83,6 +85,8 @@ int main(int argc, char** argv) {
       }
       measure_volume = true;
     }
+    else if (a == "--measure-volume-diameters") measure_volume_diameters = true;
+    else if (a == "--volume-diameters-brute-force") diameters_brute_force = true;
     else if (a == "--se-shape") ec.pipe.se_shape = v() == "disc" ? nm03::kSeDisc : nm03::kSeSquare;
     else if (a == "--render-filter") ec.render.filter = v() == "nearest" ? nm03::kFilterNearest : nm03::kFilterBilinear;
     else {
@@ -90,6 +94,11 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if ((measure_volume_diameters || diameters_brute_force) && !measure_volume_lesions) {
+    std::cerr << "--measure-volume-diameters needs --measure-volume-lesions N" << std::endl;
+    return 2;
+  }
+  if (diameters_brute_force) measure_volume_diameters = true;
   // --measure-intensity implies the measurement it extends: --measure (cohort) or --measure-volume (volume).
   if (measure_intensity && config == "cohort") ec.pipe.measure = ec.pipe.measure_intensity = true;
   if (measure_intensity && config == "volume") measure_volume = true;
@@ -185,6 +194,9 @@ int main(int argc, char** argv) {
       vp.measure = measure_volume;
       vp.measure_connectivity = measure_volume_conn;
       vp.measure_lesions = measure_volume_lesions;
+      vp.measure_diameters = measure_volume_diameters;
+      vp.diameters_brute_force = diameters_brute_force;
+      if (measure_volume_diameters) nm03::measure::volume_spacing_um((double)v.spacing_x, (double)v.spacing_y, v.spacing_z, vp.spacing_um);
       vp.measure_intensity = measure_intensity;
       vp.measure_texture = measure_texture;
       vp.texture_levels = texture_levels;
@@ -194,7 +206,7 @@ int main(int argc, char** argv) {
       int sweeps = 0;
       nm03::VolumeMeasure vm = {};
       size_t lesions = 0;
-      uint64_t lesion0_vox = 0;
+      uint64_t lesion0_vox = 0, lesion0_major_um2 = 0;
       nm03::IntensityStats vi = {};
       uint64_t glcm_pairs = 0;
       const double t0 = now_s();
@@ -208,6 +220,7 @@ int main(int argc, char** argv) {
         glcm_pairs = r.texture.head.pairs;
         lesions = r.lesions.size();
         lesion0_vox = lesions ? r.lesions[0].voxels : 0;
+        lesion0_major_um2 = r.diameters.empty() ? 0 : r.diameters[0].major_um2;
       }
       const double dt = now_s() - t0;
       // + the GPU export of every plane (render + JPEG, both images), as the 3D CLI does
@@ -229,6 +242,9 @@ int main(int argc, char** argv) {
       if (measure_volume_lesions)
         std::cout << ", \"lesions_max\": " << measure_volume_lesions << ", \"lesions\": " << lesions
                   << ", \"largest_lesion_vox\": " << lesion0_vox;
+      if (measure_volume_diameters)
+        std::cout << ", \"diameters\": true, \"diameters_brute_force\": " << (diameters_brute_force ? "true" : "false")
+                  << ", \"largest_lesion_major_um2\": " << lesion0_major_um2;
       if (measure_intensity) std::cout << ", \"intensity\": true, \"raw_p50\": " << vi.pct[2];
       if (measure_texture)
         std::cout << ", \"texture\": true, \"texture_levels\": " << texture_levels << ", \"glcm_pairs\": " << glcm_pairs;

@@ -47,29 +47,10 @@ namespace nm03::gpu {
 namespace {
 
 constexpr int kVlSelectThreads = 1024;
-constexpr int kVlAccWords = 16;  // u64 per lesion: 8 sums, then 8 i32 extrema, then unused
-
-// Sums: u64 index in a lesion's accumulator. Extrema: i32 index after the sums — minima, then maxima.
-enum : int { kLsVox = 0, kLsSumX, kLsSumY, kLsSumZ, kLsFacesX, kLsFacesY, kLsFacesZ, kLsRawSum, kLsNumSums };
-enum : int { kLeX0 = 0, kLeY0, kLeZ0, kLeRawMin, kLeX1, kLeY1, kLeZ1, kLeRawMax, kLeNum };
-static_assert(kLsNumSums == 8 && kLeNum == 8 && kLsNumSums + kLeNum / 2 <= kVlAccWords, "lesion accumulator layout");
 
 __device__ __forceinline__ int32_t ext_identity(int j) {
   return j < kLeX1 ? 0x7FFFFFFF : (j == kLeRawMax ? (int32_t)0x80000000 : -1);
 }
-
-// Control words and the chosen roots, after the accumulators in the work buffer.
-struct LesionCtl {
-  uint32_t candidates;  // keys in the candidate list
-  uint32_t count;       // reported lesions, min(N, components)
-  uint32_t pad[14];
-  uint32_t sel_slot[kMaxVolumeLesions], sel_vox[kMaxVolumeLesions];  // in rank order
-  uint32_t srt_slot[kMaxVolumeLesions], srt_rank[kMaxVolumeLesions];  // the same roots ascending by slot, and their rank
-};
-
-constexpr size_t kVlAccBytes = (size_t)kMaxVolumeLesions * kVlAccWords * sizeof(uint64_t);
-constexpr size_t kVlCandOffset = kVlAccBytes + sizeof(LesionCtl);
-static_assert(kVlCandOffset % 8 == 0, "candidate list alignment");
 
 }  // namespace
 

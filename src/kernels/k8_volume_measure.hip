@@ -24,7 +24,8 @@
 //            atomic per wave, not one per stretch
 //   D        roots are counted and their areas maximised
 //   (lesions  optional, --measure-volume-lesions: K10's launches (k10_volume_lesions.hip) go here, between the
-//            mask pass's root count and the complement pass, which overwrites the labelling they read)
+//            mask pass's root count and the complement pass, which overwrites the labelling they read; with
+//            --measure-volume-diameters K13's (k13_volume_diameters.hip) follow them directly)
 //   cavities the scratch is reused for the COMPLEMENT inside the frame (~word & row_word_mask) at the
 //            dual connectivity: init runs, B, runs pointed at their roots, then every stretch on a
 //            frame face marks its root (second slot = 1; one store per root and wave) and the
@@ -302,6 +303,7 @@ void launch_volume_measure(const uint64_t* dilated, const uint64_t* region, cons
     throw DeviceError("launch_volume_measure: a " + std::to_string(w) + " x " + std::to_string(h) + " x " +
                       std::to_string(d) + " volume is too large to measure: (w + 1) * h * d + 1 must stay below 2^32");
   if (!dilated || !region || !raw || !scratch || !acc || !out) throw DeviceError("launch_volume_measure: null buffer");
+  if (lesions && lesions->diameters) validate_volume_diameters(dilated, w, h, d, scratch, *lesions);
   const int n = (w + 63) / 64;
   const uint64_t words = (uint64_t)n * (uint64_t)h * (uint64_t)d;  // ≤ voxels < 2^32
   const uint32_t grid = (uint32_t)((words + kVmThreads - 1) / kVmThreads);
@@ -323,8 +325,11 @@ void launch_volume_measure(const uint64_t* dilated, const uint64_t* region, cons
   check_launch("vm_roots_kernel");
   // The per-lesion phase (K10) reads the mask pass's labelling — every run at its root, the area in the
   // slot after a root — before the complement pass overwrites the scratch.
-  if (lesions)
+  if (lesions) {
     launch_volume_lesions(dilated, raw, raw_plane_stride, w, h, d, type, stored_bits, scratch, *lesions, stream);
+    // The lesions' lengths (K13) need the same labelling, and K10's chosen roots and bounding boxes.
+    if (lesions->diameters) launch_volume_diameters(dilated, w, h, d, scratch, *lesions, stream);
+  }
   // Cavities: the complement at the dual connectivity, on the same scratch.
   vm_init_runs_kernel<<<grid, kVmThreads, 0, stream>>>(C, scratch);
   check_launch("vm_init_runs_kernel");

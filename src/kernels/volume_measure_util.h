@@ -1,6 +1,6 @@
-// Device-side helpers shared by the volume measurement kernels K8 (k8_volume_measure.hip) and K10
-// (k10_volume_lesions.hip): the relaxed agent-scope accesses to the run union-find's scratch, wave64
-// reductions and the thread-per-word mapping.
+// Device-side helpers shared by the volume measurement kernels K8 (k8_volume_measure.hip), K10
+// (k10_volume_lesions.hip) and K13 (k13_volume_diameters.hip): the relaxed agent-scope accesses to the run
+// union-find's scratch, wave64 reductions, the thread-per-word mapping and the layout of K10's work buffer.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -82,6 +82,28 @@ __device__ __forceinline__ WordIndex my_word(const BitVolume& V) {
   w.y = (int)(row - (uint32_t)w.z * (uint32_t)V.h);
   return w;
 }
+
+// ---- K10's work buffer, read by K13 (k13_volume_diameters.hip) as well: the accumulators, then the control
+// words and the chosen roots, then the candidate list.
+constexpr int kVlAccWords = 16;  // u64 per lesion: 8 sums, then 8 i32 extrema, then unused
+
+// Sums: u64 index in a lesion's accumulator. Extrema: i32 index after the sums — minima, then maxima.
+enum : int { kLsVox = 0, kLsSumX, kLsSumY, kLsSumZ, kLsFacesX, kLsFacesY, kLsFacesZ, kLsRawSum, kLsNumSums };
+enum : int { kLeX0 = 0, kLeY0, kLeZ0, kLeRawMin, kLeX1, kLeY1, kLeZ1, kLeRawMax, kLeNum };
+static_assert(kLsNumSums == 8 && kLeNum == 8 && kLsNumSums + kLeNum / 2 <= kVlAccWords, "lesion accumulator layout");
+
+// Control words and the chosen roots, after the accumulators in the work buffer.
+struct LesionCtl {
+  uint32_t candidates;  // keys in the candidate list
+  uint32_t count;       // reported lesions, min(N, components)
+  uint32_t pad[14];
+  uint32_t sel_slot[kMaxVolumeLesions], sel_vox[kMaxVolumeLesions];  // in rank order
+  uint32_t srt_slot[kMaxVolumeLesions], srt_rank[kMaxVolumeLesions];  // the same roots ascending by slot, and their rank
+};
+
+constexpr size_t kVlAccBytes = (size_t)kMaxVolumeLesions * kVlAccWords * sizeof(uint64_t);
+constexpr size_t kVlCandOffset = kVlAccBytes + sizeof(LesionCtl);
+static_assert(kVlCandOffset % 8 == 0, "candidate list alignment");
 
 }  // namespace
 }  // namespace nm03::gpu

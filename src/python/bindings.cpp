@@ -451,6 +451,52 @@ VolumeLesion volume_lesion_from(const py::dict& d) {
   return l;
 }
 
+// The integers of a lesion's diameter record (nm03/measure.h VolumeLesionDiameters) as a dict.
+py::dict volume_diameters_dict(const VolumeLesionDiameters& r) {
+  py::dict d;
+  d["major_um2"] = r.major_um2;
+  py::list mj, ax, pp;
+  for (int k = 0; k < 6; ++k) mj.append(r.major[k]);
+  for (int k = 0; k < 4; ++k) ax.append(r.axial[k]), pp.append(r.axial_perp[k]);
+  d["major"] = mj;
+  d["axial_z"] = r.axial_z;
+  d["axial_um2"] = r.axial_um2;
+  d["axial"] = ax;
+  d["axial_perp_extent"] = r.axial_perp_extent;
+  d["axial_perp"] = pp;
+  return d;
+}
+
+VolumeLesionDiameters volume_diameters_from(const py::dict& d) {
+  VolumeLesionDiameters r{};
+  r.major_um2 = d["major_um2"].cast<uint64_t>();
+  r.axial_um2 = d["axial_um2"].cast<uint64_t>();
+  r.axial_perp_extent = d["axial_perp_extent"].cast<int64_t>();
+  r.axial_z = d["axial_z"].cast<int32_t>();
+  const std::vector<int> mj = d["major"].cast<std::vector<int>>(), ax = d["axial"].cast<std::vector<int>>(),
+                         pp = d["axial_perp"].cast<std::vector<int>>();
+  if (mj.size() != 6 || ax.size() != 4 || pp.size() != 4)
+    throw std::invalid_argument("major must have six values, axial and axial_perp four");
+  for (int k = 0; k < 6; ++k) r.major[k] = mj[(size_t)k];
+  for (int k = 0; k < 4; ++k) r.axial[k] = ax[(size_t)k], r.axial_perp[k] = pp[(size_t)k];
+  return r;
+}
+
+py::list volume_diameters_list(const VolumeLesionDiameters* r, size_t n) {
+  py::list out;
+  for (size_t i = 0; i < n; ++i) out.append(volume_diameters_dict(r[i]));
+  return out;
+}
+
+// (ux, uy, uz) in integer micrometres, each 1 … 2^32 − 1.
+void spacing_um_from(const std::vector<int64_t>& v, uint32_t um[3]) {
+  if (v.size() != 3) throw std::invalid_argument("spacing_um must be (ux, uy, uz)");
+  for (int a = 0; a < 3; ++a) {
+    if (v[(size_t)a] < 1 || v[(size_t)a] > 0xFFFFFFFFll) throw std::invalid_argument("spacing_um: every value must be 1 .. 2^32 - 1");
+    um[a] = (uint32_t)v[(size_t)a];
+  }
+}
+
 void check_max_lesions(int n) {
   if (n < 1 || n > kMaxVolumeLesions)
     throw std::invalid_argument("max_lesions must be 1.." + std::to_string(kMaxVolumeLesions));
@@ -478,6 +524,7 @@ struct VolumeMeta {
   bool measure = false;
   int measure_connectivity = 26;
   int measure_lesions = 0;
+  bool measure_diameters = false;
   bool measure_intensity = false;
   bool measure_texture = false;
   int texture_levels = 32;
@@ -519,6 +566,9 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
     vp.measure = meta->measure;
     vp.measure_connectivity = meta->measure_connectivity;
     vp.measure_lesions = meta->measure_lesions;
+    vp.measure_diameters = meta->measure_diameters;
+    // The spacing the lengths are maximised in: the sidecar's (float pixel spacings), in integer micrometres.
+    if (vp.measure_diameters) measure::volume_spacing_um((double)v.spacing_x, (double)v.spacing_y, v.spacing_z, vp.spacing_um);
     vp.measure_intensity = meta->measure_intensity;
     vp.measure_texture = meta->measure_texture;
     vp.texture_levels = meta->texture_levels;
@@ -552,6 +602,11 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
       d["measure_json"] = golden::measure_volume_json(r.measure, vp.measure_intensity ? &r.intensity : nullptr,
                                                       vp.measure_lesions ? &r.lesions : nullptr, vp.measure_lesions, r.texture, v,
                                                       vp.pipe.apply_rescale, vp.measure_connectivity);
+    }
+    if (vp.measure_diameters) {
+      d["diameters"] = volume_diameters_list(r.diameters.data(), r.diameters.size());
+      d["measure_json"] = measure::insert_diameter_keys(d["measure_json"].cast<std::string>(), r.diameters.data(),
+                                                        (int)r.diameters.size(), vp.spacing_um);
     }
     d["measure_s"] = r.measure_s;
   }
@@ -1195,7 +1250,20 @@ PYBIND11_MODULE(_nm03, m) {
       "volume_measure_to_json",
       [](const py::dict& rec, int w, int h, int d, double sx, double sy, double sz, const std::string& source, float slope,
          float intercept, bool apply_rescale, int connectivity, const py::object& lesions, int lesions_max,
-         const py::object& intensity, const py::object& texture) {
+         const py::object& intensity, const py::object& texture, const py::object& diameters, const py::object& spacing_um) {
+        // `diameters` (a list of diameter dicts, one per lesion): the text below with the diameter keys, at
+        // `spacing_um` (ux, uy, uz) or, when that is None, the quantised spacings.
+        auto with_diameters = [&](std::string text) {
+          if (diameters.is_none()) return text;
+          if (lesions.is_none()) throw std::invalid_argument("diameters need lesions");
+          std::vector<VolumeLesionDiameters> ds;
+          for (const py::handle& x : diameters.cast<py::list>()) ds.push_back(volume_diameters_from(x.cast<py::dict>()));
+          if (ds.size() != py::len(lesions)) throw std::invalid_argument("one diameter dict per lesion");
+          uint32_t um[3];
+          if (spacing_um.is_none()) measure::volume_spacing_um((double)(float)sx, (double)(float)sy, sz, um);
+          else spacing_um_from(spacing_um.cast<std::vector<int64_t>>(), um);
+          return measure::insert_diameter_keys(std::move(text), ds.data(), (int)ds.size(), um);
+        };
         // Pixel spacings pass through float, as VolumeInput holds them.
         if (!texture.is_none()) {  // the text with the texture keys after the global keys (a texture dict)
           IntensityStats st{};
@@ -1206,18 +1274,18 @@ PYBIND11_MODULE(_nm03, m) {
             check_max_lesions(lesions_max);
             if (ls.size() > (size_t)lesions_max) throw std::invalid_argument("more lesions than lesions_max");
           }
-          return measure::volume_to_json(volume_measure_from(rec), intensity.is_none() ? nullptr : &st, ls.data(), (int)ls.size(),
+          return with_diameters(measure::volume_to_json(volume_measure_from(rec), intensity.is_none() ? nullptr : &st, ls.data(), (int)ls.size(),
                                          lesions.is_none() ? 0 : lesions_max, texture_from(texture.cast<py::dict>()), w, h, d,
                                          (double)(float)sx, (double)(float)sy, sz, source, slope, intercept, apply_rescale,
-                                         connectivity);
+                                         connectivity));
         }
         if (lesions.is_none()) {
           if (!intensity.is_none())  // the text with the intensity keys (an IntensityStats dict)
-            return measure::volume_to_json(volume_measure_from(rec), intensity_from(intensity.cast<py::dict>()), w, h, d,
+            return with_diameters(measure::volume_to_json(volume_measure_from(rec), intensity_from(intensity.cast<py::dict>()), w, h, d,
                                            (double)(float)sx, (double)(float)sy, sz, source, slope, intercept, apply_rescale,
-                                           connectivity);
-          return measure::volume_to_json(volume_measure_from(rec), w, h, d, (double)(float)sx, (double)(float)sy, sz, source,
-                                         slope, intercept, apply_rescale, connectivity);
+                                           connectivity));
+          return with_diameters(measure::volume_to_json(volume_measure_from(rec), w, h, d, (double)(float)sx, (double)(float)sy, sz, source,
+                                         slope, intercept, apply_rescale, connectivity));
         }
         // With `lesions` (a list of lesion dicts, as many as are reported): the text with the lesion keys.
         std::vector<VolumeLesion> ls;
@@ -1225,18 +1293,18 @@ PYBIND11_MODULE(_nm03, m) {
         check_max_lesions(lesions_max);
         if (ls.size() > (size_t)lesions_max) throw std::invalid_argument("more lesions than lesions_max");
         if (!intensity.is_none())
-          return measure::volume_to_json(volume_measure_from(rec), intensity_from(intensity.cast<py::dict>()), ls.data(),
+          return with_diameters(measure::volume_to_json(volume_measure_from(rec), intensity_from(intensity.cast<py::dict>()), ls.data(),
                                          (int)ls.size(), lesions_max, w, h, d, (double)(float)sx, (double)(float)sy, sz, source,
-                                         slope, intercept, apply_rescale, connectivity);
-        return measure::volume_to_json(volume_measure_from(rec), ls.data(), (int)ls.size(), lesions_max, w, h, d,
+                                         slope, intercept, apply_rescale, connectivity));
+        return with_diameters(measure::volume_to_json(volume_measure_from(rec), ls.data(), (int)ls.size(), lesions_max, w, h, d,
                                        (double)(float)sx, (double)(float)sy, sz, source, slope, intercept, apply_rescale,
-                                       connectivity);
+                                       connectivity));
       },
       py::arg("record"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_x") = 1.0, py::arg("spacing_y") = 1.0,
       py::arg("spacing_z") = 1.0, py::arg("spacing_z_source") = "default", py::arg("slope") = 1.f,
       py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 26,
       py::arg("lesions") = py::none(), py::arg("lesions_max") = 0, py::arg("intensity") = py::none(),
-      py::arg("texture") = py::none());
+      py::arg("texture") = py::none(), py::arg("diameters") = py::none(), py::arg("spacing_um") = py::none());
   // The N largest components of a volume mask (nm03/measure.h VolumeLesion) by the golden model (flood
   // fill per component) → list of dicts of the records' integers, largest first.
   m.def(
@@ -1273,6 +1341,60 @@ PYBIND11_MODULE(_nm03, m) {
       },
       py::arg("dilated"), py::arg("raw"), py::arg("max_lesions"), py::arg("type") = "u16", py::arg("stored_bits") = 16,
       py::arg("connectivity") = 26);
+  // The lengths of the same lesions (nm03/measure.h VolumeLesionDiameters) by the golden model: flood fill,
+  // then plain loops over the pairs of open-face voxels → list of dicts of the records' integers.
+  m.def(
+      "golden_measure_volume_diameters",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil, int max_lesions,
+         const std::vector<int64_t>& spacing_um, int connectivity) {
+        check_max_lesions(max_lesions);
+        if (dil.ndim() != 3) throw std::invalid_argument("dilated must be [D, H, W]");
+        uint32_t um[3];
+        spacing_um_from(spacing_um, um);
+        const int d = (int)dil.shape(0), h = (int)dil.shape(1), w = (int)dil.shape(2);
+        const std::vector<uint8_t> dv = from_np<uint8_t>(dil);
+        std::vector<VolumeLesionDiameters> r;
+        {
+          py::gil_scoped_release nogil;
+          r = golden::measure_volume_diameters(dv, w, h, d, connectivity, max_lesions, um);
+        }
+        return volume_diameters_list(r.data(), r.size());
+      },
+      py::arg("dilated"), py::arg("max_lesions"), py::arg("spacing_um") = std::vector<int64_t>{1000, 1000, 1000},
+      py::arg("connectivity") = 26);
+  // The same records from the K13 kernels' logic run on the host (measure::volume_diameters_words);
+  // with_skipped = true → (records, tile pairs the bound skipped).
+  m.def(
+      "volume_diameters_words",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dil, int max_lesions,
+         const std::vector<int64_t>& spacing_um, int connectivity, bool brute_force, bool with_skipped) -> py::object {
+        check_max_lesions(max_lesions);
+        if (dil.ndim() != 3) throw std::invalid_argument("dilated must be [D, H, W]");
+        uint32_t um[3];
+        spacing_um_from(spacing_um, um);
+        const int d = (int)dil.shape(0), h = (int)dil.shape(1), w = (int)dil.shape(2);
+        if (w <= 0 || h <= 0 || d <= 0) throw std::invalid_argument("empty volume");
+        const std::vector<uint64_t> dw = pack_volume(dil);
+        std::vector<VolumeLesionDiameters> r((size_t)max_lesions);
+        uint64_t skipped = 0;
+        int n = 0;
+        {
+          py::gil_scoped_release nogil;
+          n = measure::volume_diameters_words(dw.data(), w, h, d, (w + 63) / 64, connectivity, max_lesions, um, brute_force,
+                                              r.data(), &skipped);
+        }
+        py::list out = volume_diameters_list(r.data(), (size_t)n);
+        if (with_skipped) return py::make_tuple(out, skipped);
+        return out;
+      },
+      py::arg("dilated"), py::arg("max_lesions"), py::arg("spacing_um") = std::vector<int64_t>{1000, 1000, 1000},
+      py::arg("connectivity") = 26, py::arg("brute_force") = false, py::arg("with_skipped") = false);
+  // The spacing in integer micrometres the diameters are maximised in: max(1, llround(mm · 1000)) per axis.
+  m.def("volume_spacing_um", [](double sx, double sy, double sz) {
+    uint32_t um[3];
+    measure::volume_spacing_um(sx, sy, sz, um);
+    return py::make_tuple(um[0], um[1], um[2]);
+  }, py::arg("spacing_x"), py::arg("spacing_y"), py::arg("spacing_z"));
   m.attr("MAX_VOLUME_LESIONS") = kMaxVolumeLesions;
 
   // ---- intensity statistics (nm03/measure.h IntensityStats) ----------------------------------------------
@@ -1631,8 +1753,9 @@ PYBIND11_MODULE(_nm03, m) {
              const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_connectivity,
              const std::vector<double>& spacing, const std::string& spacing_z_source, const std::string& type,
              int stored_bits, float slope, float intercept, int measure_lesions, bool measure_intensity, bool measure_texture,
-             int texture_levels) {
+             int texture_levels, bool measure_diameters) {
             VolumeMeta mt;
+            mt.measure_diameters = measure_diameters;
             mt.measure_lesions = measure_lesions;
             mt.measure_intensity = measure_intensity;
             mt.measure_texture = measure_texture;
@@ -1654,7 +1777,7 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0}, py::arg("spacing_z_source") = "default",
           py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f, py::arg("intercept") = 0.f,
           py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false, py::arg("measure_texture") = false,
-          py::arg("texture_levels") = 32)
+          py::arg("texture_levels") = 32, py::arg("measure_diameters") = false)
       .def(
           "run_slab",
           // One rank's z-slab (planes [z0, z0 + slab depth) of a `depth`-deep volume) through the
@@ -1663,9 +1786,10 @@ PYBIND11_MODULE(_nm03, m) {
           [](VolumeRunner& self, Comm& comm, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> slab,
              int z0, int depth, const PipelineParams& p, int connectivity, int dilation,
              const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_lesions, bool measure_intensity,
-             bool measure_texture) {
+             bool measure_texture, bool measure_diameters) {
             SlabStats st;
             VolumeMeta mt;
+            mt.measure_diameters = measure_diameters;
             mt.measure = measure;  // refused by run_slab (std::invalid_argument) before anything is launched
             mt.measure_lesions = measure_lesions;  // alike
             mt.measure_intensity = measure_intensity;
@@ -1681,7 +1805,8 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("comm"), py::arg("slab"), py::arg("z0"), py::arg("depth"), py::arg("params") = PipelineParams(),
           py::arg("connectivity") = 6, py::arg("dilation") = 7,
           py::arg("seeds") = std::vector<std::tuple<int, int, int>>{}, py::arg("measure") = false,
-          py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false, py::arg("measure_texture") = false);
+          py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false, py::arg("measure_texture") = false,
+          py::arg("measure_diameters") = false);
 
   // One-process rehearsal of the z-slab decomposition: `nranks` threads, each with its own
   // VolumeRunner (stream) on `device`, talking over loopback comms — the device-resident exchange
@@ -2349,6 +2474,68 @@ PYBIND11_MODULE(_nm03, m) {
     return py::make_tuple(volume_measure_dict(res), volume_lesion_list(les.data(), count));
   }, py::arg("dilated"), py::arg("region"), py::arg("raw"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("max_lesions"),
      py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("connectivity") = 26, py::arg("stream") = 0);
+
+  // K8 with the K10 and K13 launches between its two passes: (lesion dicts, diameter dicts), both in K10's
+  // order. `raw` holds the samples K8 and K10 read; their values do not enter the diameters.
+  m.def("k_measure_volume_diameters", [](uintptr_t dilated, uintptr_t raw, int w, int h, int d, int max_lesions,
+                                         const std::vector<int64_t>& spacing_um, int connectivity, bool brute_force,
+                                         uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    if (connectivity != 6 && connectivity != 26) throw std::invalid_argument("connectivity must be 6 or 26");
+    if (w <= 0 || h <= 0 || d <= 0) throw std::invalid_argument("empty volume");
+    check_max_lesions(max_lesions);
+    const size_t slots = gpu::volume_measure_scratch_words(w, h, d);
+    if (slots == 0) throw std::invalid_argument("volume too large to measure: (w + 1) * h * d + 1 must stay below 2^32");
+    gpu::VolumeDiametersWork dw;
+    spacing_um_from(spacing_um, dw.spacing_um);
+    const std::string ext = measure::volume_diameters_extent_error(w, h, d, dw.spacing_um);
+    if (!ext.empty()) throw std::invalid_argument(ext);
+    {
+      // K8's, K10's and K13's code objects, loaded on the current device before this op's first launch there.
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_volume_measure();
+        gpu::preload_volume_lesions();
+        gpu::preload_volume_diameters();
+        preloaded.push_back(dev);
+      }
+    }
+    const size_t n_out = sizeof(VolumeLesion) * (size_t)(kMaxVolumeLesions + 1);  // records, then the count
+    const size_t n_dia = sizeof(VolumeLesionDiameters) * (size_t)kMaxVolumeLesions;
+    const size_t work = (gpu::volume_lesions_work_bytes(w, h, d, max_lesions) + 255) / 256 * 256;
+    const size_t dwork = (gpu::volume_diameters_work_bytes(w, h, d, max_lesions) + 255) / 256 * 256;
+    const size_t o_acc = 0, o_out = 256, o_les = 512, o_dia = o_les + n_out, o_work = o_dia + n_dia, o_dwork = o_work + work,
+                 o_par = o_dwork + dwork, total = o_par + slots * sizeof(uint32_t);
+    uint8_t* dev = (uint8_t*)scratch().get(total);
+    dw.work = dev + o_dwork;
+    dw.out = (VolumeLesionDiameters*)(dev + o_dia);
+    dw.brute_force = brute_force;
+    gpu::VolumeLesionWork lw;
+    lw.max_lesions = max_lesions;
+    lw.work = dev + o_work;
+    lw.out = (VolumeLesion*)(dev + o_les);
+    lw.out_count = (uint32_t*)(dev + o_les + sizeof(VolumeLesion) * kMaxVolumeLesions);
+    lw.diameters = &dw;
+    gpu::launch_volume_measure((const uint64_t*)dilated, (const uint64_t*)dilated, (const uint16_t*)raw, (size_t)w * h, w, h, d,
+                               (uint8_t)kU16, (uint8_t)16, connectivity, (uint32_t*)(dev + o_par), (uint64_t*)(dev + o_acc),
+                               (VolumeMeasure*)(dev + o_out), st, &lw);
+    std::vector<VolumeLesion> les((size_t)kMaxVolumeLesions + 1);
+    std::vector<VolumeLesionDiameters> dia((size_t)kMaxVolumeLesions);
+    gpu::check_hip(hipMemcpyAsync(les.data(), dev + o_les, n_out, hipMemcpyDeviceToHost, st), "D2H lesions");
+    gpu::check_hip(hipMemcpyAsync(dia.data(), dev + o_dia, sizeof(VolumeLesionDiameters) * (size_t)max_lesions,
+                                  hipMemcpyDeviceToHost, st), "D2H diameters");
+    gpu::check_hip(hipStreamSynchronize(st), "k_measure_volume_diameters");
+    const uint32_t count = *reinterpret_cast<const uint32_t*>(&les[(size_t)kMaxVolumeLesions]);
+    if (count > (uint32_t)max_lesions) throw std::runtime_error("k_measure_volume_diameters: count out of range");
+    return py::make_tuple(volume_lesion_list(les.data(), count), volume_diameters_list(dia.data(), count),
+                          volume_diameters_list(dia.data() + count, (size_t)max_lesions - count));
+  }, py::arg("dilated"), py::arg("raw"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("max_lesions"),
+     py::arg("spacing_um") = std::vector<int64_t>{1000, 1000, 1000}, py::arg("connectivity") = 26,
+     py::arg("brute_force") = false, py::arg("stream") = 0);
 
   // K11 on a batch of masks of ANY sizes in one launch: planes = the masks' bit planes back to back
   // (mask i: hs[i] × ceil(ws[i] / 64) words); raw = the slices' u16 samples back to back; one pixel type

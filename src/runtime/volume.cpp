@@ -164,6 +164,11 @@ struct VolumeDevice {
   // allocated by the first run that asks for lesions (for kMaxVolumeLesions, so any N fits) and kept.
   std::unique_ptr<DevBuf> vl_work;
   VolumeLesion* h_lesions = nullptr;  // kMaxVolumeLesions records, then the count
+  // K13 (VolumeParams::measure_diameters): the work buffer for `vd_lesions` lesions (regrown when a run
+  // asks for more) and the pinned records, allocated by the first run that asks for them and kept.
+  std::unique_ptr<DevBuf> vd_work;
+  int vd_lesions = 0;
+  VolumeLesionDiameters* h_diameters = nullptr;  // kMaxVolumeLesions records
   // K11 (VolumeParams::measure_intensity): the accumulators and the pinned record, allocated by the
   // first run that asks for them and kept.
   std::unique_ptr<DevBuf> vi_acc;
@@ -193,6 +198,7 @@ struct VolumeDevice {
   }
   ~VolumeDevice() {
     if (h_lesions) (void)hipHostFree(h_lesions);
+    if (h_diameters) (void)hipHostFree(h_diameters);
     if (h_intensity) (void)hipHostFree(h_intensity);
     if (h_texture) (void)hipHostFree(h_texture);
     if (h_measure) (void)hipHostFree(h_measure);
@@ -349,6 +355,7 @@ struct VolumeRunner::Impl {
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   bool measure_loaded = false;  // K8's code object (first measuring run)
   bool lesions_loaded = false;  // K10's code object (first run that asks for lesions)
+  bool diameters_loaded = false;  // K13's code object (first run that asks for diameters)
   bool intensity_loaded = false;  // K11's code object (first run that asks for the intensity statistics)
   bool texture_loaded = false;    // K12's code object (first run that asks for the texture)
   explicit Impl(int dev) : device(dev) {
@@ -387,6 +394,14 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
   if (p.measure_lesions < 0 || p.measure_lesions > kMaxVolumeLesions)
     throw std::invalid_argument("3D lesion count must be in [1, " + std::to_string(kMaxVolumeLesions) + "] (got " +
                                 std::to_string(p.measure_lesions) + ")");
+  if (p.measure_diameters && (!p.measure || p.measure_lesions < 1))
+    throw std::invalid_argument("3D lesion diameters need measure and a lesion count of at least 1");
+  if (p.measure_diameters) {
+    for (int a = 0; a < 3; ++a)
+      if (p.spacing_um[a] < 1u) throw std::invalid_argument("3D lesion diameters: a spacing must be at least 1 um");
+    const std::string ext = measure::volume_diameters_extent_error(v.w, v.h, v.d, p.spacing_um);
+    if (!ext.empty()) throw std::invalid_argument("3D lesion diameters: " + ext);
+  }
   if (p.measure_intensity && !p.measure) throw std::invalid_argument("3D intensity statistics need measure");
   if (p.measure_texture && !p.measure) throw std::invalid_argument("3D texture needs measure");
   if (p.measure_texture && (p.texture_levels < 2 || p.texture_levels > 64))
@@ -420,6 +435,20 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
         check_hip(hipHostMalloc((void**)&V.h_lesions, sizeof(VolumeLesion) * (kMaxVolumeLesions + 1), hipHostMallocDefault),
                   "hipHostMalloc lesions");
       }
+    }
+    if (p.measure_diameters) {  // K13 alike; its row table grows with N
+      if (!I.diameters_loaded) {
+        preload_volume_diameters();
+        I.diameters_loaded = true;
+      }
+      if (!V.vd_work || V.vd_lesions < p.measure_lesions) {
+        V.vd_work.reset();
+        V.vd_work = std::make_unique<DevBuf>(volume_diameters_work_bytes(v.w, v.h, v.d, p.measure_lesions));
+        V.vd_lesions = p.measure_lesions;
+      }
+      if (!V.h_diameters)
+        check_hip(hipHostMalloc((void**)&V.h_diameters, sizeof(VolumeLesionDiameters) * kMaxVolumeLesions, hipHostMallocDefault),
+                  "hipHostMalloc diameters");
     }
     if (p.measure_intensity) {  // K11 alike
       if (!I.intensity_loaded) {
@@ -459,6 +488,14 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
       lw.out = V.h_lesions;
       lw.out_count = reinterpret_cast<uint32_t*>(V.h_lesions + kMaxVolumeLesions);
     }
+    VolumeDiametersWork dw;
+    if (p.measure_diameters) {  // K13's seven launches directly after K10's
+      dw.work = V.vd_work->p;
+      dw.out = V.h_diameters;
+      for (int a = 0; a < 3; ++a) dw.spacing_um[a] = p.spacing_um[a];
+      dw.brute_force = p.diameters_brute_force;
+      lw.diameters = &dw;
+    }
     launch_volume_measure(V.dil.as<uint64_t>(), V.region.as<uint64_t>(), V.raw.as<uint16_t>(), V.ps, v.w, v.h, v.d,
                           (uint8_t)v.type, (uint8_t)v.stored_bits, p.measure_connectivity, V.vm_scratch->as<uint32_t>(),
                           V.vm_acc->as<uint64_t>(), V.h_measure, V.stream, p.measure_lesions ? &lw : nullptr);
@@ -477,6 +514,7 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
       const uint32_t count = *lw.out_count;
       if (count > (uint32_t)p.measure_lesions) throw DeviceError("volume lesions: count out of range");
       r.lesions.assign(V.h_lesions, V.h_lesions + count);
+      if (p.measure_diameters) r.diameters.assign(V.h_diameters, V.h_diameters + count);
     }
     float mms = 0;
     (void)hipEventElapsedTime(&mms, I.e1, I.e2);
@@ -626,7 +664,7 @@ static SlabStats slab_grow_dilate_gpu(Comm& comm, VolumeDevice& V, int nseeds, i
 VolumeResult VolumeRunner::run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p,
                                     bool want_masks, SlabStats* stats) {
   if (slab.d < 1 || slab.w < 1 || slab.h < 1) throw SliceError("empty slab");
-  if (p.measure || p.measure_lesions || p.measure_intensity || p.measure_texture)
+  if (p.measure || p.measure_lesions || p.measure_diameters || p.measure_intensity || p.measure_texture)
     throw std::invalid_argument("run_slab: measuring a volume split into slabs is not supported "
                                 "(components that cross slabs need a collective)");
   check_volume_params(p.connectivity, p.dilation_size);
@@ -919,7 +957,8 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
                                                       const RenderParams& rp, VolumeMeasure* measured = nullptr,
                                                       std::vector<VolumeLesion>* lesions = nullptr,
                                                       IntensityStats* intensity = nullptr,
-                                                      measure::Glcm* texture = nullptr) {
+                                                      measure::Glcm* texture = nullptr,
+                                                      std::vector<VolumeLesionDiameters>* diameters = nullptr) {
   const GoldenPlanes gp = golden_preprocess(v, vp);
   std::vector<Seed> seeds = vp.seeds;
   if (seeds.empty()) {
@@ -931,6 +970,8 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
   if (measured) *measured = golden::measure_volume(dil, region, v, vp.measure_connectivity);
   if (measured && lesions && vp.measure_lesions)
     *lesions = golden::measure_volume_lesions(dil, v, vp.measure_connectivity, vp.measure_lesions);
+  if (measured && diameters && vp.measure_lesions && vp.measure_diameters)
+    *diameters = golden::measure_volume_diameters(dil, v.w, v.h, v.d, vp.measure_connectivity, vp.measure_lesions, vp.spacing_um);
   if (measured && intensity && vp.measure_intensity) *intensity = golden::measure_intensity(dil, v);
   if (measured && texture && vp.measure_texture) *texture = golden::measure_texture(dil, v, vp.texture_levels);
   return golden_export(v, gp.vals, dil, rp);
@@ -960,6 +1001,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
   vp.measure = cfg.measure_volume;
   vp.measure_connectivity = cfg.measure_volume_connectivity;
   vp.measure_lesions = cfg.measure_volume_lesions;
+  vp.measure_diameters = cfg.measure_volume_diameters;
   vp.measure_intensity = cfg.measure_volume_intensity;
   vp.measure_texture = cfg.measure_volume_texture;
   vp.texture_levels = cfg.engine.pipe.texture_levels;
@@ -1098,8 +1140,14 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       std::vector<VolumeLesion> lesions;
       IntensityStats intensity = {};
       measure::Glcm texture;
+      std::vector<VolumeLesionDiameters> diameters;
+      if (vp.measure_diameters) {  // the spacing the lengths are maximised in: the sidecar's, in integer micrometres
+        measure::volume_spacing_um((double)v.spacing_x, (double)v.spacing_y, v.spacing_z, vp.spacing_um);
+        const std::string ext = measure::volume_diameters_extent_error(v.w, v.h, v.d, vp.spacing_um);
+        if (!ext.empty()) throw std::runtime_error("--measure-volume-diameters: " + ext);
+      }
       if (cfg.cpu) {
-        files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions, &intensity, &texture);
+        files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions, &intensity, &texture, &diameters);
       } else {
         VolumeResult r = runner->run(v, vp, false);
         o.sweeps = r.sweeps;
@@ -1107,6 +1155,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         o.measure_s = r.measure_s;
         measured = r.measure;
         lesions = std::move(r.lesions);
+        diameters = std::move(r.diameters);
         intensity = r.intensity;
         texture = std::move(r.texture);
         VolumeExportStats xs;
@@ -1127,6 +1176,9 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
                              ? golden::measure_volume_json(measured, lesions, vp.measure_lesions, v, vp.pipe.apply_rescale,
                                                            vp.measure_connectivity)
                              : golden::measure_volume_json(measured, v, vp.pipe.apply_rescale, vp.measure_connectivity);
+        if (vp.measure_diameters)  // last, so that diameters_spacing_um stands directly before lesions_max
+          o.measure_json = measure::insert_diameter_keys(std::move(o.measure_json), diameters.data(), (int)diameters.size(),
+                                                         vp.spacing_um);
         const std::string path = pp.out_dir + "/" + measure::volume_sidecar_name();
         std::ofstream f(path, std::ios::binary | std::ios::trunc);
         f.write(o.measure_json.data(), (std::streamsize)o.measure_json.size());
@@ -1257,7 +1309,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
     }
     if (cfg.measure_volume_lesions) {
       try {
-        volume_totals.lesions = write_lesions_csv(cfg.out_dir, rows);
+        volume_totals.lesions = write_lesions_csv(cfg.out_dir, rows, cfg.measure_volume_diameters, &volume_totals);
       } catch (const std::exception& e) {
         std::cerr << "Error writing lesions.csv: " << e.what() << std::endl;
       }

@@ -1,0 +1,134 @@
+"""Per-lesion 3D and axial diameters on the CPU: the golden model (flood fill, plain loops over open-face
+voxels), the NumPy / SciPy reference and the host run of the K13 kernels' logic (row extremes, direction
+bound, tile rule; skipping on and off) against each other; the worked example, the tie rules, the physical
+maximisation and the refusals."""
+import functools
+
+import numpy as np
+import pytest
+
+import volume_diameter_cases as vdc
+import volume_lesion_cases as vlc
+
+CASES = vdc.cpu_cases()
+
+
+@functools.lru_cache(maxsize=None)
+def _mask(name):
+    return next(build for cid, build, _ in CASES if cid == name)()
+
+
+@pytest.mark.parametrize("conn", vdc.CONNS)
+@pytest.mark.parametrize("um", vdc.SPACINGS, ids=["x".join(map(str, s)) for s in vdc.SPACINGS])
+@pytest.mark.parametrize("name,n", [(c[0], c[2]) for c in CASES], ids=[c[0] for c in CASES])
+def test_word_logic_equals_golden_and_reference(native, name, n, um, conn):
+    from nm03_capstone_project_amd import ops
+    mask = _mask(name)
+    golden = native.golden_measure_volume_diameters(mask, n, um, conn)
+    assert native.volume_diameters_words(mask, n, um, conn) == golden
+    assert native.volume_diameters_words(mask, n, um, conn, brute_force=True) == golden
+    assert ops.reference.measure_volume_diameters(mask, n, um, conn) == golden
+    lesions = native.golden_measure_volume_lesions(mask, np.zeros(mask.shape, np.uint16), n, "u16", 16, conn)
+    assert len(golden) == len(lesions)
+    for rec, les in zip(golden, lesions):
+        assert list(rec) == list(vdc.INT_KEYS)
+        assert vdc.pair_holds(rec, um)
+        x0, y0, z0, x1, y1, z1 = les["bbox"]
+        for x, y, z in (rec["major"][:3], rec["major"][3:]):
+            assert x0 <= x <= x1 and y0 <= y <= y1 and z0 <= z <= z1 and mask[z, y, x]
+        for x, y in (rec["axial"][:2], rec["axial"][2:], rec["axial_perp"][:2], rec["axial_perp"][2:]):
+            assert mask[rec["axial_z"], y, x]
+        assert rec["axial_um2"] <= rec["major_um2"]
+        if les["voxels"] == 1:
+            assert rec == {"major_um2": 0, "major": les["first"] * 2, "axial_z": les["first"][2], "axial_um2": 0,
+                           "axial": les["first"][:2] * 2, "axial_perp_extent": 0, "axial_perp": les["first"][:2] * 2}
+
+
+def test_hand_worked_example(native):
+    for fn in (native.golden_measure_volume_diameters, native.volume_diameters_words):
+        assert fn(vdc.hand_box(), 1, (1000, 1000, 1000), 26) == [vdc.HAND]
+    # axial_perp_mm = ux · uy · extent / √axial_um2 / 1000
+    assert 1000 * 1000 * 54 / np.sqrt(90e6) / 1000 == pytest.approx(5.6921, abs=1e-4)
+
+
+def test_edge_cases(native):
+    one = native.golden_measure_volume_diameters(vdc.one_voxel(), 2, (977, 1020, 3300), 26)
+    assert one == [{"major_um2": 0, "major": [65, 2, 1, 65, 2, 1], "axial_z": 1, "axial_um2": 0, "axial": [65, 2, 65, 2],
+                    "axial_perp_extent": 0, "axial_perp": [65, 2, 65, 2]}]
+    ndl = native.golden_measure_volume_diameters(vdc.needle(), 1, (500, 500, 5000), 6)
+    assert ndl == [{"major_um2": (6 * 5000) ** 2, "major": [3, 2, 2, 3, 2, 8], "axial_z": 2, "axial_um2": 0,
+                    "axial": [3, 2, 3, 2], "axial_perp_extent": 0, "axial_perp": [3, 2, 3, 2]}]
+    assert native.golden_measure_volume_diameters(np.zeros((3, 5, 70), np.uint8), 3, (1000, 1000, 1000), 26) == []
+
+
+def test_ties_go_to_the_first_pair_in_raster_order(native):
+    """A cube's four body diagonals, and in every plane two face diagonals, tie: a is the first voxel; of
+    the planes the first wins. The perpendicular's ends are the other diagonal's."""
+    (rec,) = native.golden_measure_volume_diameters(vdc.cube(), 1, (1000, 1000, 1000), 26)
+    assert rec["major"] == [1, 1, 1, 12, 12, 12] and rec["major_um2"] == 3 * 11000 ** 2
+    assert rec["axial_z"] == 1 and rec["axial"] == [1, 1, 12, 12]
+    assert rec["axial_perp"] == [12, 1, 1, 12] and rec["axial_perp_extent"] == 2 * 11 * 11
+    # two equal boxes: equal figures, each at its own place, in K10's order
+    for build in (vlc.equal_boxes, vlc.equal_boxes_swapped):
+        a, b = native.golden_measure_volume_diameters(build(), 2, (1000, 1000, 1000), 26)
+        assert a["major_um2"] == b["major_um2"] == (3 ** 2 + 2 ** 2 + 1) * 10 ** 6 and a["major"][2] < b["major"][2]
+    # a row parallel to the axial pair ties as a whole: c is its smallest voxel
+    m = np.zeros((1, 3, 9), np.uint8)
+    m[0, 0, 0:9] = 1
+    m[0, 2, 3:6] = 1
+    m[0, 1, 4] = 1
+    (rec,) = native.volume_diameters_words(m, 1, (1000, 1000, 1000), 6)
+    assert rec["axial"] == [0, 0, 8, 0] and rec["axial_perp"] == [0, 0, 3, 2] and rec["axial_perp_extent"] == 16
+
+
+def test_the_maximum_is_physical_not_in_voxels(native):
+    m = vdc.l_shape()
+    (iso,) = native.golden_measure_volume_diameters(m, 1, (1000, 1000, 1000), 26)
+    (aniso,) = native.golden_measure_volume_diameters(m, 1, (500, 500, 5000), 26)
+    assert iso["major"] == [0, 0, 0, 19, 0, 0]
+    assert aniso["major"] == [0, 0, 0, 12, 0, 5] and aniso["major_um2"] == 6000 ** 2 + 25000 ** 2
+    assert aniso["axial"] == iso["axial"] == [0, 0, 19, 0]
+
+
+def test_a_split_section_counts_as_one_set(native):
+    (rec,) = native.golden_measure_volume_diameters(vdc.split_section(), 1, (1000, 1000, 1000), 26)
+    assert rec["axial_z"] == 0 and rec["axial"] == [60, 1, 68, 4]
+
+
+def test_the_bound_skips_tile_pairs_of_the_ellipsoid(native):
+    """Several tiles per lesion, some of them skipped — and the brute-force switch skips none."""
+    m = vdc.ellipsoid()
+    rec, skipped = native.volume_diameters_words(m, 1, (1000, 1000, 1000), 26, with_skipped=True)
+    brute, none = native.volume_diameters_words(m, 1, (1000, 1000, 1000), 26, brute_force=True, with_skipped=True)
+    assert rec == brute and skipped > 0 and none == 0
+    rows = int(m.any(axis=2).sum())
+    assert 2 * rows > 1024
+
+
+def test_refusals(native):
+    from nm03_capstone_project_amd import ops
+    m = np.ones((2, 2, 3), np.uint8)
+    for fn in (native.golden_measure_volume_diameters, native.volume_diameters_words, ops.reference.measure_volume_diameters):
+        with pytest.raises(ValueError):
+            fn(m, 0, (1000, 1000, 1000), 26)
+        with pytest.raises(ValueError):
+            fn(m, 65, (1000, 1000, 1000), 26)
+        with pytest.raises(ValueError):
+            fn(m, 1, (1000, 0, 1000), 26)
+        with pytest.raises(ValueError):
+            fn(m, 1, (2 ** 30, 1000, 1000), 26)  # (w − 1) · ux = 2^31
+        assert len(fn(m, 1, (2 ** 30 - 1, 2 ** 31 - 1, 2 ** 31 - 1), 26)) == 1  # just below, on every axis
+    for fn in (native.golden_measure_volume_diameters, native.volume_diameters_words):
+        with pytest.raises(ValueError, match=r"\(w - 1\) \* ux = 2 \* 1073741824"):
+            fn(m, 1, (2 ** 30, 1000, 1000), 26)
+        with pytest.raises(ValueError, match=r"\(d - 1\) \* uz"):
+            fn(m, 1, (1000, 1000, 2 ** 31), 26)
+        with pytest.raises(ValueError):
+            fn(m, 1, (1000, 1000, 1000), 18)
+        with pytest.raises(ValueError):
+            fn(m, 1, (1000, 1000), 26)
+
+
+def test_spacing_in_micrometres(native):
+    assert native.volume_spacing_um(0.977, 1.02, 3.3) == (977, 1020, 3300)
+    assert native.volume_spacing_um(0.0004, 1.0006, 5.0) == (1, 1001, 5000)
