@@ -73,7 +73,10 @@ static_assert(sizeof(IntensityStats) == 64, "IntensityStats layout");
 // values under the DILATED mask, discretised to `levels` grey levels between the smallest and the largest
 // of them; C is merged over the forward directions (4 in 2D, 13 in 3D) and symmetric, Σ C = 2 · pairs.
 // A record may lie at any 4-byte aligned address (odd `levels`): it is written and read as 32-bit words,
-// the 64-bit fields low word first.
+// the 64-bit fields low word first. The cells are exact while 2 · directions · samples ≤ 2^32 − 1: always
+// in 2D, and for samples ≤ 165 191 049 in 3D (tcore::cells_exact). `samples` and `pairs` are 64-bit and
+// stay right beyond that; a 3D record beyond it is refused by every host that reads one
+// (measure::check_glcm_exact), since a cell of it may have wrapped.
 struct TextureGlcm {
   uint32_t levels;   // Ng
   uint32_t key_lo;   // icore::sample_key of the smallest sample (0 for an empty mask)
@@ -395,6 +398,10 @@ struct Glcm {
 };
 // A record as the kernels write it (header, then the matrix) read from 32-bit words at `p`.
 Glcm glcm_from_record(const void* p);
+// Throws std::invalid_argument when a 3D record of `samples` voxels may hold a wrapped 32-bit cell
+// (tcore::cells_exact over the thirteen directions): one message, naming the bound, for the volume
+// runner, the ops binding, the golden model and texture_words.
+void check_glcm_exact(uint64_t samples);
 
 // Everything the sidecar derives from a matrix, by ONE function in a fixed loop order (i, then j,
 // row-major), so equal matrices give equal text whoever computed them. With p = C / Σ C and IBSI's

@@ -46,6 +46,20 @@ constexpr int kMinLevels = 2;
 constexpr int kMaxLevels = 64;
 constexpr int kDefaultLevels = 32;
 
+// The 32-bit cells. A voxel is the first member of at most `dirs` forward pairs and every pair adds 2 to
+// a diagonal cell when both levels are equal, so a cell can reach 2 · dirs · samples (a homogeneous full
+// mask comes close). The matrix is exact while that fits a uint32: always in 2D (8 · 4096² < 2^32), and
+// for samples ≤ kMaxExactSamples3D = 165 191 049 over the thirteen directions of 3D. Beyond it a cell may
+// have wrapped, in the kernels and in the golden model alike, so such a record is refused
+// (measure::check_glcm_exact) wherever one becomes a result, never turned into features.
+constexpr uint32_t kDirections2D = 4u;
+constexpr uint32_t kDirections3D = 13u;
+NM03_HD bool cells_exact(uint64_t samples, uint32_t dirs) {  // samples < 2^32 (voxels of a volume)
+  return samples <= 0xFFFFFFFFull / (2ull * (uint64_t)dirs);
+}
+constexpr uint64_t kMaxExactSamples3D = 0xFFFFFFFFull / (2ull * kDirections3D);
+static_assert(kMaxExactSamples3D == 165191049ull, "the 3D bound of the 32-bit cells");
+
 NM03_HD uint32_t level(uint32_t key, uint32_t lo, uint32_t hi, uint32_t ng) {
   if (hi == lo) return 0u;
   const uint32_t l = ((key - lo) * ng) / (hi - lo);

@@ -521,7 +521,8 @@ def measure_volume_texture(dilated, raw, levels=32, pixel_type="u16", stored_bit
     dy = 1, or dz = dy = 0 and dx = 1. Index steps: the voxel spacing is not consulted.
 
     `dilated` (bool) and `raw` (16-bit storage) are CUDA tensors [D, H, W] of one shape; a volume with
-    (W + 1)·H·D + 1 ≥ 2³² raises, as for measure_volume."""
+    (W + 1)·H·D + 1 ≥ 2³² raises, as for measure_volume, and so does a mask of more than 165 191 049 voxels:
+    a 32-bit cell of the matrix can reach 2 · 13 · samples (nm03/texture_core.h cells_exact)."""
     if dilated.dim() != 3 or raw.shape != dilated.shape:
         raise ValueError("dilated and raw must be [D, H, W] of one shape")
     if not dilated.is_cuda:

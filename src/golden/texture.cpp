@@ -31,7 +31,7 @@ namespace golden {
 
 namespace {
 measure::Glcm cooccurrence(const std::vector<uint8_t>& dilated, const std::vector<uint16_t>& raw, int w, int h, int d,
-                           PixelType type, int stored_bits, int levels) {
+                           PixelType type, int stored_bits, int levels, bool volume) {
   const size_t n = (size_t)w * h * d;
   if (dilated.size() != n || raw.size() != n) throw std::invalid_argument("measure_texture: mask and samples must have one shape");
   if (stored_bits < 1 || stored_bits > 16) throw std::invalid_argument("measure_texture: stored bits must be 1..16");
@@ -51,6 +51,7 @@ measure::Glcm cooccurrence(const std::vector<uint8_t>& dilated, const std::vecto
       ++g.head.samples;
     }
   if (g.head.samples == 0) return g;
+  if (volume) measure::check_glcm_exact(g.head.samples);  // the cells below are 32-bit as the kernels' are
   g.head.key_lo = lo;
   g.head.key_hi = hi;
   // The forward directions: dz = 1, or dz = 0 and dy = 1, or dz = dy = 0 and dx = 1.
@@ -85,12 +86,12 @@ measure::Glcm cooccurrence(const std::vector<uint8_t>& dilated, const std::vecto
 
 measure::Glcm measure_texture(const std::vector<uint8_t>& dilated, const SliceInput& s, int levels) {
   if (s.w <= 0 || s.h <= 0) throw std::invalid_argument("measure_texture: empty slice");
-  return cooccurrence(dilated, s.raw, s.w, s.h, 1, s.type, s.stored_bits, levels);
+  return cooccurrence(dilated, s.raw, s.w, s.h, 1, s.type, s.stored_bits, levels, false);
 }
 
 measure::Glcm measure_texture(const std::vector<uint8_t>& dilated, const VolumeInput& v, int levels) {
   if (v.w <= 0 || v.h <= 0 || v.d <= 0) throw std::invalid_argument("measure_texture: empty volume");
-  return cooccurrence(dilated, v.raw, v.w, v.h, v.d, v.type, v.stored_bits, levels);
+  return cooccurrence(dilated, v.raw, v.w, v.h, v.d, v.type, v.stored_bits, levels, true);
 }
 
 std::string measure_volume_json(const VolumeMeasure& m, const IntensityStats* st, const std::vector<VolumeLesion>* lesions,
@@ -112,6 +113,13 @@ Glcm glcm_from_record(const void* p) {
   g.c.resize((size_t)g.head.levels * g.head.levels);
   std::memcpy(g.c.data(), static_cast<const uint8_t*>(p) + sizeof(TextureGlcm), g.c.size() * 4);
   return g;
+}
+
+void check_glcm_exact(uint64_t samples) {
+  if (!tcore::cells_exact(samples, tcore::kDirections3D))
+    throw std::invalid_argument("3D texture: " + std::to_string(samples) + " samples under the mask exceed " +
+                                std::to_string(tcore::kMaxExactSamples3D) +
+                                ", the most whose 13-direction co-occurrence counts fit the matrix's 32-bit cells");
 }
 
 Glcm texture_words(const uint64_t* dilated, const uint16_t* raw, size_t raw_plane_stride, int w, int h, int d, int wpr,
@@ -143,6 +151,7 @@ Glcm texture_words(const uint64_t* dilated, const uint16_t* raw, size_t raw_plan
           ++g.head.samples;
         }
   if (g.head.samples == 0) return g;
+  check_glcm_exact(g.head.samples);  // the 3D bound: a slice of the engine (at most 4096²) never reaches it
   g.head.key_lo = lo;
   g.head.key_hi = hi;
   // Walk 2: directed counts, word by word, over the five partner rows.

@@ -440,7 +440,11 @@ void launch_volume_texture(const uint64_t* dilated, const uint16_t* raw, size_t 
   if (w <= 0 || h <= 0 || d <= 0) throw DeviceError("launch_volume_texture: empty volume");
   if (stored_bits < 1 || stored_bits > 16) throw DeviceError("launch_volume_texture: stored bits must be 1..16");
   check_texture_levels(levels, "launch_volume_texture");
-  // The samples are addressed by 32-bit offsets and counted in 32-bit cells, as K8 names its runs.
+  // The samples are addressed by 32-bit offsets, as K8 names its runs. That bounds the voxels, not the
+  // 32-bit cells of the matrix: a cell can reach 2 · 13 · samples and is exact only for samples ≤
+  // 165 191 049 (tcore::cells_exact). `samples` in the header is 64-bit and right in any case; the hosts
+  // that read the record refuse one beyond the bound (measure::check_glcm_exact). Sparse masks in
+  // larger volumes are fine, so nothing is refused by w · h · d here.
   if (volume_measure_scratch_words(w, h, d) == 0 || raw_plane_stride < (size_t)w * (size_t)h ||
       raw_plane_stride * (size_t)d > 0xFFFFFFFFull)
     throw DeviceError("launch_volume_texture: a " + std::to_string(w) + " x " + std::to_string(h) + " x " + std::to_string(d) +

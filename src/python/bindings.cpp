@@ -2726,7 +2726,9 @@ PYBIND11_MODULE(_nm03, m) {
     std::vector<uint32_t> res(rec / 4);
     gpu::check_hip(hipMemcpyAsync(res.data(), dev + o_out, rec, hipMemcpyDeviceToHost, st), "D2H record");
     gpu::check_hip(hipStreamSynchronize(st), "k_measure_volume_texture");
-    return texture_dict(measure::glcm_from_record(res.data()));
+    const measure::Glcm g = measure::glcm_from_record(res.data());
+    measure::check_glcm_exact(g.head.samples);
+    return texture_dict(g);
   }, py::arg("dilated"), py::arg("raw"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("levels") = 32,
      py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("stream") = 0);
 

@@ -509,7 +509,10 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
     check_hip(hipEventSynchronize(I.e2), "sync");
     r.measure = *V.h_measure;
     if (p.measure_intensity) r.intensity = *V.h_intensity;
-    if (p.measure_texture) r.texture = measure::glcm_from_record(V.h_texture);
+    if (p.measure_texture) {
+      r.texture = measure::glcm_from_record(V.h_texture);
+      measure::check_glcm_exact(r.texture.head.samples);  // a cell may have wrapped: no result, as on the CPU
+    }
     if (p.measure_lesions) {
       const uint32_t count = *lw.out_count;
       if (count > (uint32_t)p.measure_lesions) throw DeviceError("volume lesions: count out of range");

@@ -33,8 +33,10 @@
 #include "nm03/jpeg.h"
 #include "nm03/jpeg_common.h"
 #include "nm03/numa.h"
+#include "nm03/measure.h"
 #include "nm03/pack12.h"
 #include "nm03/params.h"
+#include "nm03/texture_core.h"
 #include "nm03/thread_pool.h"
 
 namespace {
@@ -737,6 +739,25 @@ TEST(numa_cpulist) {
   CHECK((parse_cpulist("0-3,8,10-11") == std::vector<int>{0, 1, 2, 3, 8, 10, 11}));
   CHECK(parse_cpulist("").empty());
   CHECK((parse_cpulist("5") == std::vector<int>{5}));
+}
+
+TEST(glcm_cells_exact_bound) {
+  // 2 · dirs · samples ≤ 2^32 − 1 (nm03/texture_core.h): 2 · 13 · 165 191 049 = 4 294 967 274, and 26 more wraps.
+  using namespace nm03::tcore;
+  CHECK(cells_exact(165191049ull, kDirections3D));
+  CHECK(!cells_exact(165191050ull, kDirections3D));
+  CHECK(2ull * 13ull * 165191049ull <= 0xFFFFFFFFull && 2ull * 13ull * 165191050ull > 0xFFFFFFFFull);
+  CHECK(cells_exact(1ull << 24, kDirections2D));  // the largest slice, 4096², in 2D
+  CHECK(cells_exact(0ull, kDirections3D) && !cells_exact(0xFFFFFFFFull, kDirections3D));
+  CHECK(kMaxExactSamples3D == 165191049ull);
+  nm03::measure::check_glcm_exact(165191049ull);
+  bool threw = false;
+  try {
+    nm03::measure::check_glcm_exact(165191050ull);
+  } catch (const std::invalid_argument& e) {
+    threw = std::string(e.what()).find("165191049") != std::string::npos;  // the message names the bound
+  }
+  CHECK(threw);
 }
 
 TEST(cli_defaults_are_reference_literals) {

@@ -1,7 +1,7 @@
 """GPU tests (MI355X) on 2D slices with a side between 1025 and kMaxSliceDim = 4096: the K2 global-memory
 path with rows and columns beyond its 1024 threads, K7's 64-bit sums, K9's 12-bit key fields at 0xFFF,
-K1 / K3 / K4 on more than 16 tiles a side and at 8× minification, and the engine end to end, in mixed
-batches and at its limits. Inputs and their CPU checks: large_slice_cases.py, test_large_slice_cases.py.
+K11's bins and K12's cells at 2²⁴ samples, K1 / K3 / K4 on more than 16 tiles a side and at 8× minification,
+and the engine end to end, in mixed batches and at its limits. Inputs and their CPU checks: large_slice_cases.py, test_large_slice_cases.py.
 Every comparison is of integers, bits or bytes (the sharpen against float64 keeps param_cases.sharpen_bound)."""
 import functools
 import io
@@ -17,6 +17,7 @@ import large_slice_cases as lc
 import measure_masks as mm
 import nm03_capstone_project_amd as nm
 import param_cases as pcs
+import texture_cases as tc
 from nm03_capstone_project_amd import ops
 from nm03_capstone_project_amd.ops import reference as R
 
@@ -158,6 +159,69 @@ def test_measure_4096_square(native, names, conn):
             assert min(g["sum_x"], g["sum_y"], g["raw_sum"]) > 2 ** 32
         if name.startswith("diag"):
             assert g["components"] == (4096 if conn == 4 else 1) and g["sum_y"] == 4095 * 4096 // 2
+
+
+# ---------------------------------------------------------------------------------------------
+# 2b. K11 / K12: intensity and texture
+# ---------------------------------------------------------------------------------------------
+def test_intensity_and_texture_4096_square(native):
+    """Two slices of 4096 × 4096 in ONE launch of each op. The full homogeneous one: K11 has a single bin of
+    2²⁴ samples, every percentile is the value and Σv² = 2²⁴ · v²; K12 a single cell 2 · (H(W − 1) + W(H − 1) +
+    2(H − 1)(W − 1)) = 134 168 580 with half as many pairs: closed forms, and the golden model. Density 0.5
+    with 16-bit noise: the golden model, and the NumPy references at this size too (3.4 s of CPU, measured
+    once: sort + Python-integer squares 1.4 s, np.add.at 2 s), so no smaller stand-in is needed."""
+    h, w = lc.SHAPES["square_limit"]
+    v = 30000
+    r = np.random.default_rng(4096)
+    masks = [np.ones((h, w), bool), r.random((h, w)) < 0.5]
+    raws = [np.full((h, w), v, np.uint16), r.integers(0, 65536, size=(h, w)).astype(np.uint16)]
+    dm_, dr = [_dev(k) for k in masks], [_cuda16(x) for x in raws]
+    gi = ops.measure_intensity(dm_, dr)
+    gt = ops.measure_texture(dm_, dr, [32, 64])
+    assert len(gi) == len(gt) == 2
+    n = h * w
+    assert n == 2 ** 24
+    assert gi[0] == {"count": n, "raw_sum_sq": n * v * v, **{f"raw_p{p}": v for p in (10, 25, 50, 75, 90)}}
+    cell = 2 * (h * (w - 1) + w * (h - 1) + 2 * (h - 1) * (w - 1))
+    assert cell == 134168580
+    assert gt[0]["glcm"][0, 0] == cell and np.count_nonzero(gt[0]["glcm"]) == 1
+    assert (gt[0]["samples"], gt[0]["pairs"], gt[0]["key_lo"], gt[0]["key_hi"], gt[0]["levels"]) == (n, cell // 2, v, v, 32)
+    for i, levels in enumerate((32, 64)):
+        assert gi[i] == native.golden_measure_intensity(masks[i], raws[i], "u16", 16), i
+        assert tc.same(gt[i], native.golden_measure_texture(masks[i], raws[i], levels, "u16", 16)), i
+    assert gi[1] == R.measure_intensity(masks[1], raws[1])
+    assert tc.same(gt[1], R.glcm(masks[1], raws[1], 64))
+    assert gt[1]["samples"] == int(masks[1].sum()) and gt[1]["pairs"] > 2 ** 23  # about a quarter of the 4 · 2²⁴ neighbour pairs
+
+
+K12_LARGE_SHAPES = ("both_wrap", "rows_wrap")  # 1100 × 1040 and 1030 × 70
+K12_LARGE_MASKS = ("noise_0.593", "spiral", "comb")
+K12_LARGE_LEVELS = (2, 63, 64)
+
+
+def test_intensity_and_texture_ragged_masks_beyond_1024_rows(native):
+    """large_slice_cases' ragged bands (a line across the wrap boundary, an island near the far corner) at
+    1100 × 1040 and 1030 × 70 over 16-bit noise: every (shape, mask, level count) in ONE launch of
+    ops.measure_texture and every (shape, mask) in one of ops.measure_intensity, against the golden model and
+    the NumPy references."""
+    r = np.random.default_rng(1100)
+    raw = {s: r.integers(0, 65536, size=lc.SHAPES[s]).astype(np.uint16) for s in K12_LARGE_SHAPES}
+    pairs = [(s, name) for s in K12_LARGE_SHAPES for name in K12_LARGE_MASKS]
+    mask = {c: lc.k2_band(c[1], *lc.SHAPES[c[0]]) for c in pairs}
+    dmask, draw = {c: _dev(mask[c]) for c in pairs}, {s: _cuda16(raw[s]) for s in K12_LARGE_SHAPES}
+    gi = ops.measure_intensity([dmask[c] for c in pairs], [draw[c[0]] for c in pairs])
+    cases = [(c, lv) for c in pairs for lv in K12_LARGE_LEVELS]
+    gt = ops.measure_texture([dmask[c] for c, _ in cases], [draw[c[0]] for c, _ in cases], [lv for _, lv in cases])
+    assert len(gi) == len(pairs) and len(gt) == len(cases)
+    for c, g in zip(pairs, gi):
+        ys = np.nonzero(mask[c])[0]
+        assert ys.min() < lc.WRAP <= ys.max(), c
+        assert g == native.golden_measure_intensity(mask[c], raw[c[0]], "u16", 16), c
+        assert g == R.measure_intensity(mask[c], raw[c[0]]), c
+    for (c, lv), g in zip(cases, gt):
+        assert tc.same(g, native.golden_measure_texture(mask[c], raw[c[0]], lv, "u16", 16)), (c, lv)
+        assert tc.same(g, R.glcm(mask[c], raw[c[0]], lv)), (c, lv)
+        assert g["pairs"] > 0 and g["samples"] == int(mask[c].sum()), (c, lv)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -313,7 +377,7 @@ def _engine_case(shape, out_w=512, out_h=512):
 
 def _engine_cfg(out_w=512, out_h=512, **kw):
     return nm.PipelineConfig(max_dim=lc.LIMIT, batch_size=2, streams=1, threads=2, measure=True, measure_diameters=True,
-                             overlay=True, out_width=out_w, out_height=out_h, **kw)
+                             measure_intensity=True, measure_texture=True, overlay=True, out_width=out_w, out_height=out_h, **kw)
 
 
 @pytest.mark.parametrize("nearest", [False, True], ids=["bilinear", "nearest"])
@@ -380,6 +444,8 @@ def test_engine_end_to_end_large_slice(native, big_pipe, tmp_path, shape):
     for k in ("band", "region", "dilated", "eroded"):
         assert np.array_equal(gpu[k], ref[k].astype(bool)), k
     assert gpu["measure"] == ref["measure"] and dict(gpu["diameters"]) == dict(ref["diameters"])
+    assert gpu["intensity"] == ref["intensity"] and tc.same(gpu["texture"], ref["texture"])
+    assert ref["texture"]["pairs"] > 0 and ref["intensity"]["count"] == ref["measure"]["area_px"] > 0
     assert gpu["measure_json"] == ref["measure_json"]
     assert max(ref["diameters"]["major"]) >= lc.WRAP
     assert gpu["jpegs"][0] == ref["jpeg_original"] and gpu["jpegs"][4] == ref["jpeg_processed"]
@@ -419,6 +485,8 @@ def test_engine_end_to_end_nearest_and_384x512_canvas(native):
     assert gpu["jpegs"][0] == ref["jpeg_original"] and gpu["jpegs"][4] == ref["jpeg_processed"]
     assert np.array_equal(gpu["overlay"], ref["overlay"]) and gpu["jpeg_overlay"] == ref["jpeg_overlay"]
     assert gpu["measure_json"] == ref["measure_json"]
+    assert gpu["intensity"] == ref["intensity"] and tc.same(gpu["texture"], ref["texture"])
+    assert ref["texture"]["pairs"] > 0
     lo, hi = ref["window"]
     want = R.render_gray(torch.from_numpy(raw.astype(np.float32)), lo, hi, 384, 512, nearest=True).numpy()
     assert np.array_equal(np.asarray(gpu["canvases"][0]), want)
@@ -439,7 +507,7 @@ def test_engine_mixed_batch_with_large_slices(native, tmp_path, monkeypatch):
         slices.append(lc.bridged(native.phantom_slice(h, w, 3, 12, 25, 7), h, w))
     files = _write_dicoms(native, tmp_path / "in", slices)
     cfg = nm.PipelineConfig(max_dim=lc.LIMIT, batch_size=4, streams=1, threads=2, measure_diameters=True,
-                            min_dim=lc.MIXED_MIN_DIM)  # the 70-pixel sides are below the default minimum of 100
+                            measure_intensity=True, measure_texture=True, min_dim=lc.MIXED_MIN_DIM)  # the 70-pixel sides are below the default minimum of 100
     runs = []
     for i, flag in enumerate(["1", "0"]):
         monkeypatch.setenv("NM03_PACK12", flag)

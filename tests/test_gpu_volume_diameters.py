@@ -83,6 +83,21 @@ def test_refusals_on_the_gpu(native):
     assert len(ops.measure_volume_diameters(t, 1, (2 ** 30 - 1, 2 ** 31 - 1, 2 ** 31 - 1))) == 1
 
 
+@pytest.mark.parametrize("conn", vdc.CONNS)
+def test_the_largest_admissible_spacings_on_the_ellipsoid(native, conn):
+    """vdc.ELLIPSOID_MAX_UM: squared distances above 2^61 and tile bounds towards 3 · 2^62, which only
+    unsigned 64-bit integers order right. Equal to golden with the tile skipping on and off,
+    and consistent in Python integers."""
+    mask, um = vdc.ellipsoid(), vdc.ELLIPSOID_MAX_UM
+    t = _dev(mask)
+    golden = native.golden_measure_volume_diameters(mask, 2, um, conn)
+    assert len(golden) == 1 and golden[0]["major_um2"] > 2 ** 61
+    for brute in (False, True):
+        got = ops.measure_volume_diameters(t, 2, um, conn, brute_force=brute)
+        assert got == golden, brute
+        assert all(vdc.pair_holds(d, um) for d in got)
+
+
 # ---------------------------------------------------------------------------------------------
 # VolumePipeline(measure=True, measure_lesions=N, measure_diameters=True)
 # ---------------------------------------------------------------------------------------------

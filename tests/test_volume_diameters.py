@@ -105,6 +105,19 @@ def test_the_bound_skips_tile_pairs_of_the_ellipsoid(native):
     assert 2 * rows > 1024
 
 
+@pytest.mark.parametrize("conn", vdc.CONNS)
+def test_the_largest_admissible_spacings_on_the_ellipsoid(native, conn):
+    """The ellipsoid at vdc.ELLIPSOID_MAX_UM: the major and the axial diameter squared exceed 2^61, the bounds of
+    tile pairs more (no float and no 63-bit arithmetic orders them exactly). Golden, the word logic with and without tile skipping, and the NumPy reference."""
+    from nm03_capstone_project_amd import ops
+    m, um = vdc.ellipsoid(), vdc.ELLIPSOID_MAX_UM
+    golden = native.golden_measure_volume_diameters(m, 2, um, conn)
+    assert len(golden) == 1 and golden[0]["major_um2"] > 2 ** 61 and vdc.pair_holds(golden[0], um)
+    assert native.volume_diameters_words(m, 2, um, conn) == golden
+    assert native.volume_diameters_words(m, 2, um, conn, brute_force=True) == golden
+    assert ops.reference.measure_volume_diameters(m, 2, um, conn) == golden
+
+
 def test_refusals(native):
     from nm03_capstone_project_amd import ops
     m = np.ones((2, 2, 3), np.uint8)

@@ -87,6 +87,11 @@ def ellipsoid():
     return (((x - 64) / 14.0) ** 2 + ((y - 19) / 18.0) ** 2 + ((z - 31) / 30.0) ** 2 <= 1.0).astype(np.uint8)
 
 
+# The largest spacings the ellipsoid's frame (80 × 39 × 63) admits: every axis extent just below 2^31 um, so
+# a squared distance across the frame approaches 3 · 2^62 and is ordered right only as an unsigned 64-bit number.
+ELLIPSOID_MAX_UM = ((2 ** 31 - 1) // 79, (2 ** 31 - 1) // 38, (2 ** 31 - 1) // 62)
+
+
 def split_section():
     """Two pillars joined by a bridge on top: the section of plane 0 … 2 is two separate blobs, and the
     axial pair spans both."""
