@@ -1,7 +1,7 @@
 """One DICOM series as a 3D volume on the MI355X: per-slice preprocessing, 6-connected 3D region
 growing and a 7×7×7 dilation (BASELINE config 5), checked against the golden 3D model.
 
-    python examples/volume_3d.py --series path/to/series_dir [--ball] [--measure]
+    python examples/volume_3d.py --series path/to/series_dir [--ball] [--measure] [--views DIR]
 """
 import argparse
 import os
@@ -20,9 +20,12 @@ def main(argv=None):
     ap.add_argument("--measure", action="store_true",
                     help="also print the volumetry of the dilated volume (K8: mm3, components, cavities, tunnels) and "
                          "the largest lesion's diameters (K10 + K13)")
+    ap.add_argument("--views", metavar="DIR",
+                    help="also write the axial / coronal / sagittal planes through the lesion and the three projections "
+                         "(K14): twelve JPEGs and views.json into DIR")
     a = ap.parse_args(argv)
     vp = nm.VolumePipeline(nm.PipelineConfig(se_shape=int(a.ball)), connectivity=6, dilation=7, measure=a.measure,
-                           measure_lesions=int(a.measure), measure_diameters=a.measure)
+                           measure_lesions=int(a.measure), measure_diameters=a.measure, views=bool(a.views))
     res = vp.run_series(a.series)
     band = res["band"]
     region, dil = vp.golden(band, vp.default_seeds(band))
@@ -39,6 +42,14 @@ def main(argv=None):
             print(f"largest lesion: {les['voxels']} voxels, 3D diameter {les['diameter_3d_mm']:.1f} mm, axial "
                   f"{les['axial_major_mm']:.1f} x {les['axial_perp_mm']:.1f} mm in plane {les['axial_z']} "
                   f"(spacing {m['diameters_spacing_um']} um)")
+    if a.views:
+        os.makedirs(a.views, exist_ok=True)
+        for name, data in res["views_jpeg"].items():
+            with open(os.path.join(a.views, name), "wb") as f:
+                f.write(data)
+        with open(os.path.join(a.views, "views.json"), "w") as f:
+            f.write(res["views_json"])
+        print(f"views through {res['views_at']}: {len(res['views_jpeg'])} files and views.json in {a.views}")
     return 0 if same else 1
 
 

@@ -18,6 +18,7 @@
 
 #include "nm03/comm.h"
 #include "nm03/engine.h"
+#include "nm03/volume_views.h"
 
 namespace nm03::app {
 
@@ -107,6 +108,11 @@ struct AppConfig {
   // carry the texture keys (nm03/texture_core.h) at engine.pipe.texture_levels grey levels
   // (--texture-levels). In 2D the flag is engine.pipe.measure_texture.
   bool measure_volume_texture = false;
+  // --volume-views (3d): twelve further JPEGs and views.json per patient — the axial, coronal and sagittal
+  // plane through a point and the projections along the three axes (nm03/volume_views.h). The point:
+  // --volume-views-at mask|centre|X,Y,Z (default mask).
+  bool volume_views = false;
+  ViewsAt volume_views_at;
   // CLOCK_REALTIME when parse_args began (the --json record's "main_unix_s"): with the launcher's
   // own clock it splits a cold run's wall into process start-up (exec → main) and the rest.
   double main_unix_s = 0;

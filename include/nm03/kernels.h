@@ -10,6 +10,7 @@
 #include "nm03/gpu_types.h"
 #include "nm03/measure.h"
 #include "nm03/pixel_math.h"
+#include "nm03/volume_views.h"
 
 namespace nm03::gpu {
 
@@ -317,6 +318,48 @@ void launch_volume_texture(const uint64_t* dilated, const uint16_t* raw, size_t 
 // VolumeRunner built with the feature on and the Python ops (before their first launch) load it.
 void preload_measure_texture();
 void preload_volume_texture();
+
+// K14 (k14_volume_views.hip): the six views of nm03/volume_views.h from the samples `raw` (plane z at raw
+// + z · raw_plane_stride) and the `dilated` bit volume (d planes of h rows of ceil(w / 64) words), in the
+// buffers K3 / K4 render from. Five launches on `stream`, separated by kernel boundaries: init (zero the
+// projection scratch and the shadows), project (ONE read of the volume and of the bit planes: a workgroup
+// owns 128 columns × 16 rows × 8 planes and combines its partial maxima / ORs with integer
+// atomicMax / atomicOr where more than one workgroup contributes), point (one workgroup: the box of the
+// mask from the shadows, then P), extract (the three planes through P, the projections narrowed to
+// samples, every gray view's key min / max by atomicMin / atomicMax), count (every mask's popcount by one
+// workgroup each). No grid barrier, flag, spin, host round trip or allocation; the result does not depend on the
+// order in which workgroups run.
+struct VolumeViewsLayout {
+  int w = 0, h = 0, d = 0;
+  int vw[kVolumeViewCount], vh[kVolumeViewCount], wpr[kVolumeViewCount];  // view i: width, height, mask words per row
+  uint32_t sample_off[kVolumeViewCount];  // u16 elements into `samples` (multiples of 8)
+  // u64 words into `bits`: the mask of view i; its renderer border goes border_off words further. Views of
+  // one size are neighbours (0, 3 | 1, 4 | 2, 5), so border_volume takes each pair as a two-plane volume.
+  uint32_t mask_off[kVolumeViewCount];
+  uint32_t border_off = 0;        // = the words of all six masks
+  uint32_t proj_off[3] = {0, 0, 0};  // u32 elements into `proj`: the projection along z, y, x
+  size_t samples = 0, bit_words = 0, proj = 0;  // buffer sizes: u16 elements, u64 words (masks + borders), u32 elements
+};
+// Throws DeviceError for an empty volume or one whose views do not fit 32-bit offsets.
+VolumeViewsLayout volume_views_layout(int w, int h, int d);
+// What the kernels leave for the host, copied back once: P, the box and the per-view integers.
+struct VolumeViewsHead {
+  int32_t at[3];
+  int32_t has_box;
+  int32_t box[6];
+  uint32_t mask_px[kVolumeViewCount];
+  SliceStats stats[kVolumeViewCount];  // key_min / key_max of every gray view (K3's window); s_* unused
+};
+// `inverted`: the smallest key wins a projection. `at` must have passed views::at_error. `samples`,
+// `bits`, `proj`: L.samples u16, L.bit_words u64, L.proj u32 of device memory, no initialisation needed;
+// `head`: device memory. Throws DeviceError before any launch for a null buffer, stored bits outside
+// 1..16, a plane stride below w · h or a volume of more than 2^32 − 1 samples.
+void launch_volume_views(const uint16_t* raw, size_t raw_plane_stride, const uint64_t* dilated, uint8_t type,
+                         uint8_t stored_bits, bool inverted, const ViewsAt& at, const VolumeViewsLayout& L, uint16_t* samples,
+                         uint64_t* bits, uint32_t* proj, VolumeViewsHead* head, hipStream_t stream);
+// Loads K14's code object on the current device: only a VolumeRunner's first export_views and the Python
+// op load it.
+void preload_volume_views();
 
 // K6: binary threshold lo ≤ x ≤ hi → u8 0/1 (in 16-byte aligned, out 4-byte aligned).
 void launch_threshold(const float* in, uint8_t* out, size_t n, float lo, float hi, hipStream_t stream);

@@ -12,6 +12,7 @@
 #include "nm03/comm.h"
 #include "nm03/engine.h"
 #include "nm03/measure.h"
+#include "nm03/volume_views.h"
 
 namespace nm03 {
 
@@ -75,6 +76,16 @@ struct VolumeExportStats {
   int64_t jpeg_fallbacks = 0;  // images re-encoded on the host (GPU capacity overflow)
 };
 
+// VolumeRunner::export_views: the views of nm03/volume_views.h, rendered and encoded.
+struct VolumeViewsExport {
+  // P, the box and every view's size, raw_min / raw_max and mask_px; the sample and mask planes only
+  // when they were asked for (else empty).
+  VolumeViews views;
+  std::vector<std::vector<uint8_t>> files;  // the twelve JPEG files in views::file_name order
+  double k14_s = 0;     // GPU time of K14's launches
+  double render_s = 0;  // GPU time of the borders, K3 and K4 behind them
+};
+
 struct VolumeParams {
   PipelineParams pipe;        // median/sharpen/band per slice, then 3D SRG
   int connectivity = 6;       // 6 | 26
@@ -120,6 +131,15 @@ class VolumeRunner {
   // the device — byte-identical to the golden host renderer + encoder.
   std::vector<std::vector<uint8_t>> export_jpegs(const VolumeInput& v, const VolumeParams& p, const RenderParams& rp,
                                                  struct VolumeExportStats* stats = nullptr);
+  // After run() on the same volume (--volume-views): the six views through `at` from the volume and the
+  // dilated bit planes still on the device (K14), each rendered into the rp canvas at the view's own
+  // spacing with the renderer border of its own 2D image and encoded by K4 — byte-identical to
+  // golden::volume_view_jpegs of golden::volume_views. The first call loads K14's code object and
+  // allocates the view buffers, kept like the others and rebuilt with the volume shape; without a call
+  // nothing of K14 is touched. Throws std::invalid_argument for a point outside the volume.
+  // `want_planes`: also copy the sample and mask planes back.
+  VolumeViewsExport export_views(const VolumeInput& v, const VolumeParams& p, const RenderParams& rp, const ViewsAt& at,
+                                 bool want_planes = false, struct VolumeExportStats* stats = nullptr);
   // One rank's z-slab of a `depth`-deep volume (volume_slabs.h): `slab` holds planes
   // [z0, z0 + slab.d); seeds (p.seeds, or the reference pattern on plane depth / 2) are in volume
   // coordinates. Preprocesses the slab's planes, runs the global region-growing fixpoint and the

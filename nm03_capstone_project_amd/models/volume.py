@@ -18,7 +18,15 @@ thirteen forward directions: the result gains `texture` (the header integers plu
 `measure_diameters=True` (needs `measure` and `measure_lesions` ≥ 1) the K13 kernels also report every
 lesion's 3D major diameter, largest axial diameter and its perpendicular, maximised in the spacing quantised
 to integer micrometres: the result gains `diameters` (a list of dicts of each record's integers, in the
-lesions' order) and `measure_json` carries `diameters_spacing_um` and the diameter keys of every lesion."""
+lesions' order) and `measure_json` carries `diameters_spacing_um` and the diameter keys of every lesion.
+
+With `views=True` every run also exports the views that use the third axis (K14, nm03/volume_views.h): the
+axial, coronal and sagittal plane through a point and the projections along z, y and x, from the volume
+still on the device. `views_at` is "mask" (default: the centre of the dilated mask's bounding box, the
+volume's centre when the mask is empty), "centre" or a voxel (x, y, z). The result gains `views` (a dict
+name → {width, height, raw, mask, raw_min, raw_max, mask_px}), `views_at` (x, y, z), `views_json` (the text
+of the CLI's views.json, from the one native writer) and `views_jpeg` (file name → the bytes of the twelve
+JPEGs the CLI writes, rendered at the config's canvas, quality, sampling and filter)."""
 import numpy as np
 
 from .._native import native
@@ -34,7 +42,7 @@ def _meta_args(meta):
 class VolumePipeline:
     def __init__(self, config: PipelineConfig = None, connectivity: int = 6, dilation: int = 7, measure: bool = False,
                  measure_connectivity: int = 26, measure_lesions: int = 0, measure_intensity: bool = False, measure_texture: bool = False,
-                 texture_levels: int = 32, measure_diameters: bool = False):
+                 texture_levels: int = 32, measure_diameters: bool = False, views: bool = False, views_at="mask"):
         self.config = config or PipelineConfig()
         self.connectivity = connectivity
         self.dilation = dilation
@@ -59,6 +67,12 @@ class VolumePipeline:
         self.measure_diameters = bool(measure_diameters)
         if self.measure_diameters and not (self.measure and self.measure_lesions >= 1):
             raise ValueError("measure_diameters needs measure=True and measure_lesions >= 1")
+        self.views = bool(views)
+        self.views_at = views_at if isinstance(views_at, str) else tuple(int(v) for v in views_at)
+        if self.views_at not in ("mask", "centre") and not (isinstance(self.views_at, tuple) and len(self.views_at) == 3):
+            raise ValueError(f"views_at must be 'mask', 'centre' or (x, y, z) (got {views_at!r})")
+        if self.views and self.config.host_only:
+            raise ValueError("views are extracted, rendered and encoded on the GPU: not available with host_only")
         self._runners = {}  # device -> native VolumeRunner (buffers/stream reused across volumes)
 
     def default_seeds(self, volume):
@@ -75,14 +89,30 @@ class VolumePipeline:
         runner = self._runners.get(dev)
         if runner is None:
             runner = self._runners[dev] = native().VolumeRunner(dev)
+        if self.views and isinstance(self.views_at, tuple):  # before anything is launched
+            d, h, w = vol.shape
+            x, y, z = self.views_at
+            if not (0 <= x < w and 0 <= y < h and 0 <= z < d):
+                raise ValueError(f"views_at: the point ({x}, {y}, {z}) lies outside the volume of {w} x {h} x {d}")
         if not self.measure and meta is None:
-            return runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s)
-        return runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s, measure=self.measure,
-                          measure_connectivity=self.measure_connectivity, spacing=[float(v) for v in spacing],
-                          spacing_z_source=str(spacing_z_source), measure_lesions=self.measure_lesions,
-                          measure_intensity=self.measure_intensity, measure_texture=self.measure_texture,
-                          texture_levels=self.texture_levels, measure_diameters=self.measure_diameters,
-                          **_meta_args(meta))
+            res = runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s)
+        else:
+            res = runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s, measure=self.measure,
+                             measure_connectivity=self.measure_connectivity, spacing=[float(v) for v in spacing],
+                             spacing_z_source=str(spacing_z_source), measure_lesions=self.measure_lesions,
+                             measure_intensity=self.measure_intensity, measure_texture=self.measure_texture,
+                             texture_levels=self.texture_levels, measure_diameters=self.measure_diameters,
+                             **_meta_args(meta))
+        if self.views:  # K14 on the volume the run left on the device
+            d, h, w = vol.shape
+            a = _meta_args(meta)
+            x = runner.export_views(w, h, d, self.config.pipeline_params(), self.config.render_params(), self.views_at,
+                                    [float(v) for v in spacing], a["type"], a["stored_bits"], a["slope"], a["intercept"])
+            res["views"] = x["views"]
+            res["views_at"] = tuple(x["at"])
+            res["views_json"] = x["views_json"]
+            res["views_jpeg"] = x["views_jpeg"]
+        return res
 
     def run_series(self, series_dir, seeds=None, device=None):
         """A DICOM series directory as one volume (utils.read_series: the reference's file-number
@@ -90,7 +120,7 @@ class VolumePipeline:
         (utils.series_geometry) and the first slice's storage format go with it."""
         from ..utils.dicom import read_series, series_geometry
         vol, slices = read_series(series_dir)
-        if not self.measure:
+        if not self.measure and not self.views:
             return self.run(vol, seeds=seeds, device=device)
         g = series_geometry(series_dir)
         return self.run(vol, seeds=seeds, device=device, spacing=(g["spacing_x"], g["spacing_y"], g["spacing_z"]),

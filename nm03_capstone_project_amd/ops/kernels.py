@@ -539,3 +539,52 @@ def measure_volume_texture(dilated, raw, levels=32, pixel_type="u16", stored_bit
     dw = pack_bits(dilated.bool()).contiguous()
     return native().k_measure_volume_texture(dw.data_ptr(), x.data_ptr(), w, h, d, int(levels), pixel_type,
                                              int(stored_bits), _stream())
+
+
+def volume_views(raw, dilated, at="mask", pixel_type="u16", stored_bits=16, inverted=False, plane_stride=None, shape=None):
+    """The six views of a volume that use its third axis (K14 alone, nm03/volume_views.h) → dict: width, height,
+    depth, at_mode, at (x, y, z), mask_bbox ([x0, y0, z0, x1, y1, z1] or None for an empty mask), inverted and
+    `views`, a dict name → {width, height, raw (uint16 [h, w]), mask (uint8 [h, w]), raw_min, raw_max, mask_px}
+    for view_axial, view_coronal, view_sagittal (the planes z = at.z, y = at.y, x = at.x; the sagittal one has
+    column = y, row = z) and mip_axial, mip_coronal, mip_sagittal (per pixel the sample that is largest as
+    displayed along z, y, x — the smallest key when `inverted` — and the OR of the mask along the axis).
+
+    `raw` (16-bit storage) and `dilated` (bool) are CUDA tensors [D, H, W]; `at` is "mask" (the centre of the
+    mask's bounding box, the volume's centre when the mask is empty), "centre" or a voxel (x, y, z), which must
+    lie inside the volume. With `plane_stride` (≥ H·W samples) and `shape` = (D, H, W), `raw` is instead a flat
+    tensor whose plane z starts at sample z · plane_stride, as the 3D runner lays its planes out. Five launches
+    (init, project, point, extract, count) on the current stream; the planes are copied back."""
+    if dilated.dim() != 3:
+        raise ValueError("dilated must be [D, H, W]")
+    if not dilated.is_cuda:
+        raise ValueError("masks must be CUDA (HIP) tensors")
+    if not 1 <= int(stored_bits) <= 16:
+        raise ValueError("stored_bits must be 1..16")
+    if pixel_type not in ("u16", "i16", "u8"):
+        raise ValueError("pixel_type must be u16, i16 or u8")
+    d, h, w = (int(v) for v in dilated.shape)
+    if d < 1 or h < 1 or w < 1:
+        raise ValueError("empty volume")
+    x = raw.contiguous()
+    _check(x, _U16, "raw")
+    if plane_stride is None:
+        if tuple(raw.shape) != (d, h, w):
+            raise ValueError("raw and dilated must be [D, H, W] of one shape")
+        stride = h * w
+    else:
+        stride = int(plane_stride)
+        if shape is None or tuple(int(v) for v in shape) != (d, h, w):
+            raise ValueError("plane_stride needs shape = (D, H, W), the shape of dilated")
+        if stride < h * w or x.numel() < (d - 1) * stride + h * w:
+            raise ValueError("plane_stride must cover a plane and raw must hold every plane")
+    if stride * d >= 2 ** 32:
+        raise ValueError("volume too large: plane_stride * D must stay below 2^32")
+    if not isinstance(at, str):
+        at = tuple(int(v) for v in at)
+        if len(at) != 3 or not (0 <= at[0] < w and 0 <= at[1] < h and 0 <= at[2] < d):
+            raise ValueError(f"the point {at} lies outside the volume of {w} x {h} x {d}")
+    elif at not in ("mask", "centre"):
+        raise ValueError("at must be 'mask', 'centre' or (x, y, z)")
+    dw = pack_bits(dilated.bool()).contiguous()
+    return native().k_volume_views(x.data_ptr(), dw.data_ptr(), w, h, d, stride, at, pixel_type, int(stored_bits),
+                                   bool(inverted), _stream())

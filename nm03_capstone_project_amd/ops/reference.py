@@ -630,3 +630,70 @@ def glcm_features(c):
 def psnr(a, b):
     mse = ((a.double() - b.double()) ** 2).mean().item()
     return math.inf if mse == 0 else 10 * math.log10(255.0 ** 2 / mse)
+
+
+def volume_views(raw, dilated, at="mask", pixel_type="u16", stored_bits=16, inverted=False):
+    """The dict ops.volume_views gives, in plain NumPy: slicing for the three planes, max(axis=…) (min when
+    `inverted`) on the order-preserving keys for the projections, any(axis=…) for the shadows. The key of a
+    sample is its value masked to `stored_bits` (sign-extended, then the sign bit flipped, for i16); a
+    projection pixel is the canonical sample of the winning key (the key itself, or the sign-extended value)."""
+    import numpy as np
+
+    x = raw.detach().cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
+    x = np.ascontiguousarray(x).view(np.uint16) if x.dtype == np.int16 else x.astype(np.uint16)
+    m = (dilated.detach().cpu().numpy() if isinstance(dilated, torch.Tensor) else np.asarray(dilated)).astype(bool)
+    if x.ndim != 3 or m.shape != x.shape:
+        raise ValueError("raw and dilated must be [D, H, W] of one shape")
+    d, h, w = x.shape
+    bits = int(stored_bits)
+    sh = 16 - bits
+    if pixel_type == "i16":
+        value = ((x.astype(np.int32) << sh) & 0xFFFF).astype(np.uint16).view(np.int16).astype(np.int32) >> sh
+        key = value + 32768
+    else:
+        value = x.astype(np.int32) & (0xFFFF >> sh)
+        key = value
+
+    def sample(k):  # the canonical stored sample of a key
+        v = k - 32768 if pixel_type == "i16" else k
+        return (v & 0xFFFF).astype(np.uint16)
+
+    if m.any():
+        zs, ys, xs = np.nonzero(m)
+        box = [int(xs.min()), int(ys.min()), int(zs.min()), int(xs.max()), int(ys.max()), int(zs.max())]
+    else:
+        box = None
+    if isinstance(at, str):
+        if at not in ("mask", "centre"):
+            raise ValueError("at must be 'mask', 'centre' or (x, y, z)")
+        mode = at
+        if at == "mask" and box is not None:
+            p = ((box[0] + box[3]) // 2, (box[1] + box[4]) // 2, (box[2] + box[5]) // 2)
+        else:
+            p = (w // 2, h // 2, d // 2)
+    else:
+        mode = "point"
+        p = tuple(int(v) for v in at)
+        if len(p) != 3 or not (0 <= p[0] < w and 0 <= p[1] < h and 0 <= p[2] < d):
+            raise ValueError(f"the point {p} lies outside the volume of {w} x {h} x {d}")
+    best = np.min if inverted else np.max
+    planes = {
+        "view_axial": (x[p[2]], m[p[2]]),
+        "view_coronal": (x[:, p[1], :], m[:, p[1], :]),
+        "view_sagittal": (x[:, :, p[0]], m[:, :, p[0]]),
+        "mip_axial": (sample(best(key, axis=0)), m.any(axis=0)),
+        "mip_coronal": (sample(best(key, axis=1)), m.any(axis=1)),
+        "mip_sagittal": (sample(best(key, axis=2)), m.any(axis=2)),
+    }
+    views = {}
+    for name, (r, k) in planes.items():
+        r = np.ascontiguousarray(r, dtype=np.uint16)
+        if pixel_type == "i16":
+            v = ((r.astype(np.int32) << sh) & 0xFFFF).astype(np.uint16).view(np.int16).astype(np.int32) >> sh
+        else:
+            v = r.astype(np.int32) & (0xFFFF >> sh)
+        views[name] = {"width": int(r.shape[1]), "height": int(r.shape[0]), "raw": r,
+                       "mask": np.ascontiguousarray(k, dtype=np.uint8), "raw_min": int(v.min()), "raw_max": int(v.max()),
+                       "mask_px": int(k.sum())}
+    return {"width": w, "height": h, "depth": d, "at_mode": mode, "at": p, "mask_bbox": box, "inverted": bool(inverted),
+            "views": views}

@@ -170,3 +170,26 @@ def read_volume_lesions(out_dir):
                     row[k] = None if v == "" else float(v) if k in floats else int(v)
             rows.append(row)
     return rows
+
+
+VOLUME_VIEW_NAMES = ("view_axial", "view_coronal", "view_sagittal", "mip_axial", "mip_coronal", "mip_sagittal")
+
+
+def read_volume_views(out_dir):
+    """The views of one patient directory written by the 3D CLI with --volume-views: the parsed views.json
+    (width, height, depth, at_mode, at, mask_bbox, inverted, spacing, views) with two keys added — `json`, the
+    sidecar's text, and `files`, a dict of the twelve file names (<view>_original.jpg, <view>_processed.jpg
+    in the sidecar's view order) → their bytes."""
+    import json
+    import os
+    with open(os.path.join(out_dir, "views.json")) as f:
+        text = f.read()
+    rec = json.loads(text)
+    rec["json"] = text
+    rec["files"] = {}
+    for v in rec["views"]:
+        for kind in ("original", "processed"):
+            name = f"{v['name']}_{kind}.jpg"
+            with open(os.path.join(out_dir, name), "rb") as f:
+                rec["files"][name] = f.read()
+    return rec

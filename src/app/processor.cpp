@@ -84,6 +84,12 @@ void usage(const std::string& which) {
             << "  --measure-volume-diameters  3d: --measure-volume-lesions (N = 1 unless given) plus every lesion's 3D major\n"
             << "                         diameter, largest axial diameter and its perpendicular, maximised in micrometres:\n"
             << "                         keys in the sidecar's lesion objects, columns in <out>/lesions.csv\n"
+            << "  --volume-views         3d: also write the axial, coronal and sagittal plane through a point and the\n"
+            << "                         projections along z, y and x (maximum intensity; the mask's shadow): twelve\n"
+            << "                         <patient>/{view,mip}_{axial,coronal,sagittal}_{original,processed}.jpg and\n"
+            << "                         <patient>/views.json (needs --mode 3d; not with --split-volume)\n"
+            << "  --volume-views-at mask|centre|X,Y,Z  the point of --volume-views: the centre of the dilated mask's box\n"
+            << "                         (default; the volume's centre when the mask is empty), the volume's centre, or a voxel\n"
             << "  --mode 2d|3d           3d: whole series as a volume (SRG 6-conn + cube dilation)\n"
             << "  --split-volume         3d: each volume split into z-slabs over all ranks (halo exchange)\n"
             << "  --input FILE           test_pipeline: slice to process\n"
@@ -167,6 +173,7 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
   bool measure_intensity = false;  // --measure-intensity
   bool measure_texture = false;    // --measure-texture
   bool texture_levels_given = false;
+  bool volume_views_at_given = false;
   c.main_unix_s = main_unix;
   c.data_root = cohort::default_data_root();
   c.out_dir = which == "test_pipeline" ? "../out-test" : which == "img_processing_sequential" ? "../out-sequential" : "../out-parallel";
@@ -306,6 +313,16 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
       c.measure_volume = true;
     }
     else if (a == "--measure-volume-diameters") c.measure_volume_diameters = true;
+    else if (a == "--volume-views") c.volume_views = true;
+    else if (a == "--volume-views-at") {
+      const std::string v = val();
+      if (!views::parse_at(v, &c.volume_views_at)) {
+        std::cerr << "--volume-views-at must be mask, centre or X,Y,Z with three non-negative integers (got " << v << ")"
+                  << std::endl;
+        std::exit(2);
+      }
+      volume_views_at_given = true;
+    }
     else if (a == "--measure-connectivity") {
       const std::string v = val();
       if (v != "4" && v != "8") {
@@ -399,6 +416,20 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
   }
   if (c.measure_volume && c.split_volume) {
     std::cerr << "--measure-volume is not available with --split-volume" << std::endl;
+    std::exit(2);
+  }
+  if (volume_views_at_given && !c.volume_views) {
+    std::cerr << "--volume-views-at needs --volume-views" << std::endl;
+    std::exit(2);
+  }
+  if (c.volume_views && c.mode != "3d") {
+    std::cerr << "--volume-views needs --mode 3d" << std::endl;
+    std::exit(2);
+  }
+  if (c.volume_views && c.split_volume) {
+    std::cerr << "--volume-views is not available with --split-volume: a view crosses the slabs (drop --split-volume to "
+                 "get the views, or --volume-views to split the volume)"
+              << std::endl;
     std::exit(2);
   }
   if (c.engine.render.overlay && c.mode == "3d") {

@@ -47,6 +47,7 @@ int main(int argc, char** argv) {
   bool measure_texture = false;    // cohort with --measure / volume with --measure-volume: also K12 (co-occurrence matrix)
   int texture_levels = 32;
   bool measure_intensity = false;  // cohort with --measure / volume with --measure-volume: also K11 (percentiles, sum of squares)
+  bool volume_views = false;       // volume: also K14 and the render + encode of the twelve view files per run
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto v = [&] { return std::string(argv[++i]); };
@@ -87,6 +88,7 @@ int main(int argc, char** argv) {
     }
     else if (a == "--measure-volume-diameters") measure_volume_diameters = true;
     else if (a == "--volume-diameters-brute-force") diameters_brute_force = true;
+    else if (a == "--volume-views") volume_views = true;
     else if (a == "--se-shape") ec.pipe.se_shape = v() == "disc" ? nm03::kSeDisc : nm03::kSeSquare;
     else if (a == "--render-filter") ec.render.filter = v() == "nearest" ? nm03::kFilterNearest : nm03::kFilterBilinear;
     else {
@@ -99,6 +101,10 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (diameters_brute_force) measure_volume_diameters = true;
+  if (volume_views && (config != "volume" || ec.host_only)) {
+    std::cerr << "--volume-views needs --config volume and the GPU (not --host-only)" << std::endl;
+    return 2;
+  }
   // --measure-intensity implies the measurement it extends: --measure (cohort) or --measure-volume (volume).
   if (measure_intensity && config == "cohort") ec.pipe.measure = ec.pipe.measure_intensity = true;
   if (measure_intensity && config == "volume") measure_volume = true;
@@ -232,6 +238,22 @@ int main(int argc, char** argv) {
         runner.export_jpegs(v, vp, ec.render, &xs);
       }
       const double dt2 = now_s() - t1;
+      // + the views (K14, then borders + render + encode of the twelve files), as the 3D CLI does with --volume-views
+      double views_ms = 0, k14_ms = 0, views_render_ms = 0;
+      size_t view_bytes = 0;
+      if (volume_views) {
+        const nm03::ViewsAt at;  // mask
+        for (int w = 0; w < warmup + 1; ++w) runner.export_views(v, vp, ec.render, at);
+        const double t2 = now_s();
+        for (int k = 0; k < steps; ++k) {
+          const auto x = runner.export_views(v, vp, ec.render, at);
+          k14_ms += x.k14_s * 1e3;
+          views_render_ms += x.render_s * 1e3;
+          view_bytes = 0;
+          for (const auto& f : x.files) view_bytes += f.size();
+        }
+        views_ms = (now_s() - t2) * 1e3;
+      }
       std::cout << "{\"config\": \"volume\", \"dims\": [" << v.w << ", " << v.h << ", " << v.d << "], \"steps\": " << steps
                 << ", \"ms_per_volume\": " << dt * 1e3 / steps << ", \"gpu_ms_per_volume\": " << ks * 1e3 / steps
                 << ", \"sweeps\": " << sweeps << ", \"ms_per_volume_with_export\": " << dt2 * 1e3 / steps
@@ -245,6 +267,9 @@ int main(int argc, char** argv) {
       if (measure_volume_diameters)
         std::cout << ", \"diameters\": true, \"diameters_brute_force\": " << (diameters_brute_force ? "true" : "false")
                   << ", \"largest_lesion_major_um2\": " << lesion0_major_um2;
+      if (volume_views)
+        std::cout << ", \"views_ms_per_volume\": " << views_ms / steps << ", \"views_k14_ms\": " << k14_ms / steps
+                  << ", \"views_render_encode_ms\": " << views_render_ms / steps << ", \"views_jpeg_bytes\": " << view_bytes;
       if (measure_intensity) std::cout << ", \"intensity\": true, \"raw_p50\": " << vi.pct[2];
       if (measure_texture)
         std::cout << ", \"texture\": true, \"texture_levels\": " << texture_levels << ", \"glcm_pairs\": " << glcm_pairs;

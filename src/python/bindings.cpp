@@ -544,6 +544,96 @@ void apply_meta(const VolumeMeta& mt, VolumeInput& v) {
   v.spacing_z_source = mt.spacing_z_source;
 }
 
+// --volume-views-at from Python: "mask", "centre", "X,Y,Z" or a sequence of three integers.
+ViewsAt views_at_from(const py::object& o) {
+  ViewsAt at;
+  if (py::isinstance<py::str>(o)) {
+    if (!views::parse_at(o.cast<std::string>(), &at)) throw std::invalid_argument("at must be 'mask', 'centre' or (x, y, z)");
+    return at;
+  }
+  const auto p = o.cast<std::vector<int64_t>>();
+  if (p.size() != 3) throw std::invalid_argument("at must be 'mask', 'centre' or (x, y, z)");
+  for (int64_t c : p)
+    if (c < -0x7FFFFFFFll || c > 0x7FFFFFFFll) throw std::invalid_argument("at: coordinate out of range");
+  at.mode = kViewsAtPoint;
+  at.x = (int)p[0], at.y = (int)p[1], at.z = (int)p[2];
+  return at;
+}
+
+// A VolumeViews record as Python sees it: width, height, depth, at_mode, at, mask_bbox (None when the mask
+// is empty), inverted and `views`, a dict name → {width, height, raw_min, raw_max, mask_px} plus the planes
+// raw (uint16 [h, w]) and mask (uint8 [h, w]) when the record holds them.
+py::dict views_dict(const VolumeViews& v) {
+  py::dict d;
+  d["width"] = v.w;
+  d["height"] = v.h;
+  d["depth"] = v.d;
+  d["at_mode"] = std::string(views::at_mode_name(v.at_mode));
+  d["at"] = py::make_tuple(v.at[0], v.at[1], v.at[2]);
+  if (v.has_box) {
+    py::list b;
+    for (int k = 0; k < 6; ++k) b.append(v.box[k]);
+    d["mask_bbox"] = b;
+  } else {
+    d["mask_bbox"] = py::none();
+  }
+  d["inverted"] = v.inverted;
+  py::dict vs;
+  for (int i = 0; i < kVolumeViewCount; ++i) {
+    const VolumeView& q = v.view[i];
+    py::dict e;
+    e["width"] = q.w;
+    e["height"] = q.h;
+    e["raw_min"] = q.raw_min;
+    e["raw_max"] = q.raw_max;
+    e["mask_px"] = q.mask_px;
+    if (!q.raw.empty()) e["raw"] = to_np<uint16_t>(q.raw, {q.h, q.w});
+    if (!q.mask.empty()) e["mask"] = to_np<uint8_t>(q.mask, {q.h, q.w});
+    vs[views::view_name(i)] = e;
+  }
+  d["views"] = vs;
+  return d;
+}
+
+VolumeViews views_from(const py::dict& d) {
+  VolumeViews v;
+  v.w = d["width"].cast<int>();
+  v.h = d["height"].cast<int>();
+  v.d = d["depth"].cast<int>();
+  const std::string mode = d["at_mode"].cast<std::string>();
+  v.at_mode = mode == "mask" ? kViewsAtMask : mode == "centre" ? kViewsAtCentre : kViewsAtPoint;
+  const auto at = d["at"].cast<std::vector<int>>();
+  if (at.size() != 3) throw std::invalid_argument("views: at must be (x, y, z)");
+  for (int a = 0; a < 3; ++a) v.at[a] = at[(size_t)a];
+  v.has_box = !d["mask_bbox"].is_none();
+  if (v.has_box) {
+    const auto b = d["mask_bbox"].cast<std::vector<int>>();
+    if (b.size() != 6) throw std::invalid_argument("views: mask_bbox must hold six integers");
+    for (int a = 0; a < 6; ++a) v.box[a] = b[(size_t)a];
+  }
+  v.inverted = d["inverted"].cast<bool>();
+  const py::dict vs = d["views"].cast<py::dict>();
+  for (int i = 0; i < kVolumeViewCount; ++i) {
+    const py::dict e = vs[views::view_name(i)].cast<py::dict>();
+    VolumeView& q = v.view[i];
+    q.w = e["width"].cast<int>();
+    q.h = e["height"].cast<int>();
+    q.raw_min = e["raw_min"].cast<int32_t>();
+    q.raw_max = e["raw_max"].cast<int32_t>();
+    q.mask_px = e["mask_px"].cast<uint32_t>();
+    if (e.contains("raw")) q.raw = from_np<uint16_t>(e["raw"].cast<py::array_t<uint16_t, py::array::c_style | py::array::forcecast>>());
+    if (e.contains("mask")) q.mask = from_np<uint8_t>(e["mask"].cast<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>>());
+  }
+  return v;
+}
+
+py::dict view_files_dict(const std::vector<std::vector<uint8_t>>& files) {
+  py::dict d;
+  for (int k = 0; k < (int)files.size(); ++k)
+    d[py::str(views::file_name(k / 2, k & 1))] = py::bytes((const char*)files[(size_t)k].data(), files[(size_t)k].size());
+  return d;
+}
+
 }  // namespace
 
 template <class Fn>
@@ -1779,6 +1869,40 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false, py::arg("measure_texture") = false,
           py::arg("texture_levels") = 32, py::arg("measure_diameters") = false)
       .def(
+          "export_views",
+          // After run() on a volume of this shape: the views of nm03/volume_views.h from the volume still on
+          // the device (K14, K3, K4). Returns the views_dict keys plus views_json (the sidecar text),
+          // views_jpeg (file name → bytes), k14_s and render_s.
+          [](VolumeRunner& self, int w, int h, int d, const PipelineParams& p, const RenderParams& rp, const py::object& at,
+             const std::vector<double>& spacing, const std::string& type, int stored_bits, float slope, float intercept) {
+            VolumeMeta mt;
+            mt.type = type;
+            mt.stored_bits = stored_bits;
+            mt.slope = slope;
+            mt.intercept = intercept;
+            mt.spacing = spacing;
+            VolumeInput v;
+            v.w = w, v.h = h, v.d = d;
+            apply_meta(mt, v);
+            VolumeParams vp;
+            vp.pipe = p;
+            const ViewsAt a = views_at_from(at);
+            VolumeViewsExport x;
+            {
+              py::gil_scoped_release nogil;
+              x = self.export_views(v, vp, rp, a, true);
+            }
+            py::dict out = views_dict(x.views);
+            out["views_json"] = views::to_json(x.views, v.spacing_x, v.spacing_y, v.spacing_z);
+            out["views_jpeg"] = view_files_dict(x.files);
+            out["k14_s"] = x.k14_s;
+            out["render_s"] = x.render_s;
+            return out;
+          },
+          py::arg("w"), py::arg("h"), py::arg("d"), py::arg("params") = PipelineParams(), py::arg("render") = RenderParams(),
+          py::arg("at") = py::str("mask"), py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0}, py::arg("type") = "u16",
+          py::arg("stored_bits") = 16, py::arg("slope") = 1.f, py::arg("intercept") = 0.f)
+      .def(
           "run_slab",
           // One rank's z-slab (planes [z0, z0 + slab depth) of a `depth`-deep volume) through the
           // distributed 3D pipeline over `comm` (collective; volume_slabs.h). Seeds in volume
@@ -2536,6 +2660,115 @@ PYBIND11_MODULE(_nm03, m) {
   }, py::arg("dilated"), py::arg("raw"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("max_lesions"),
      py::arg("spacing_um") = std::vector<int64_t>{1000, 1000, 1000}, py::arg("connectivity") = 26,
      py::arg("brute_force") = false, py::arg("stream") = 0);
+
+  // The golden views (nm03/volume_views.h) of the samples `raw` and the mask `dilated` ([D, H, W] each).
+  m.def(
+      "golden_volume_views",
+      [](py::array_t<uint16_t, py::array::c_style | py::array::forcecast> raw,
+         py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dilated, const py::object& at, const std::string& type,
+         int stored_bits, bool inverted) {
+        if (raw.ndim() != 3 || dilated.ndim() != 3) throw std::invalid_argument("raw and dilated must be [D, H, W]");
+        for (int a = 0; a < 3; ++a)
+          if (raw.shape(a) != dilated.shape(a)) throw std::invalid_argument("raw and dilated must have one shape");
+        const PixelType pt = parse_type(type);
+        const ViewsAt a = views_at_from(at);
+        return views_dict(golden::volume_views(raw.data(), dilated.data(), (int)raw.shape(2), (int)raw.shape(1), (int)raw.shape(0),
+                                               (uint8_t)pt, stored_bits, inverted, a));
+      },
+      py::arg("raw"), py::arg("dilated"), py::arg("at") = py::str("mask"), py::arg("type") = "u16", py::arg("stored_bits") = 16,
+      py::arg("inverted") = false);
+  // The sidecar text of a views dict (golden_volume_views, k_volume_views, VolumeRunner.export_views).
+  m.def(
+      "volume_views_to_json",
+      [](const py::dict& v, double sx, double sy, double sz) { return views::to_json(views_from(v), (float)sx, (float)sy, sz); },
+      py::arg("views"), py::arg("spacing_x") = 1.0, py::arg("spacing_y") = 1.0, py::arg("spacing_z") = 1.0);
+  // The twelve files of a views dict that holds its planes, by the host renderer and encoder: file name → bytes.
+  m.def(
+      "golden_volume_view_jpegs",
+      [](const py::dict& v, const RenderParams& rp, const std::vector<double>& spacing, const std::string& type, int stored_bits,
+         float slope, float intercept) {
+        if (spacing.size() != 3) throw std::invalid_argument("spacing must be (sx, sy, sz)");
+        if (stored_bits < 1 || stored_bits > 16) throw std::invalid_argument("stored_bits must be 1..16");
+        const VolumeViews vv = views_from(v);
+        for (int i = 0; i < kVolumeViewCount; ++i)
+          if (vv.view[i].raw.size() != (size_t)vv.view[i].w * vv.view[i].h || vv.view[i].mask.size() != vv.view[i].raw.size())
+            throw std::invalid_argument("views: every view needs its raw and mask planes");
+        const PixelType pt = parse_type(type);
+        std::vector<std::vector<uint8_t>> files;
+        {
+          py::gil_scoped_release nogil;
+          files = golden::volume_view_jpegs(vv, (uint8_t)pt, stored_bits, slope, intercept, (float)spacing[0], (float)spacing[1],
+                                            spacing[2], rp);
+        }
+        return view_files_dict(files);
+      },
+      py::arg("views"), py::arg("render") = RenderParams(), py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0},
+      py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f, py::arg("intercept") = 0.f);
+
+  // K14 alone on device tensors: `raw` the 16-bit samples (plane z at raw + z · plane_stride), `dilated` the
+  // bit volume [d][h][ceil(w/64)] (int64 words). Returns the views dict with its planes. Synchronous on `stream`.
+  m.def("k_volume_views", [](uintptr_t raw, uintptr_t dilated, int w, int h, int d, int64_t plane_stride, const py::object& at,
+                             const std::string& type, int stored_bits, bool inverted, uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    if (w <= 0 || h <= 0 || d <= 0) throw std::invalid_argument("empty volume");
+    if (stored_bits < 1 || stored_bits > 16) throw std::invalid_argument("stored_bits must be 1..16");
+    if (plane_stride < (int64_t)w * h) throw std::invalid_argument("plane_stride must be at least w * h");
+    if ((uint64_t)plane_stride * (uint64_t)d > 0xFFFFFFFFull) throw std::invalid_argument("volume too large: plane_stride * d must stay below 2^32");
+    const PixelType pt = parse_type(type);
+    const ViewsAt a = views_at_from(at);
+    const std::string err = views::at_error(a, w, h, d);
+    if (!err.empty()) throw std::invalid_argument(err);
+    {
+      // K14's code object, loaded on the current device before this op's first launch there.
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_volume_views();
+        preloaded.push_back(dev);
+      }
+    }
+    const gpu::VolumeViewsLayout L = gpu::volume_views_layout(w, h, d);
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t o_head = 0, o_samples = up(sizeof(gpu::VolumeViewsHead)), o_bits = o_samples + up(L.samples * 2),
+                 o_proj = o_bits + up(L.bit_words * 8), total = o_proj + up(L.proj * 4);
+    uint8_t* dev = (uint8_t*)scratch().get(total);
+    gpu::launch_volume_views((const uint16_t*)raw, (size_t)plane_stride, (const uint64_t*)dilated, (uint8_t)pt, (uint8_t)stored_bits,
+                             inverted, a, L, (uint16_t*)(dev + o_samples), (uint64_t*)(dev + o_bits), (uint32_t*)(dev + o_proj),
+                             (gpu::VolumeViewsHead*)(dev + o_head), st);
+    gpu::VolumeViewsHead hh;
+    std::vector<uint16_t> hs(L.samples);
+    std::vector<uint64_t> hb(L.border_off);
+    gpu::check_hip(hipMemcpyAsync(&hh, dev + o_head, sizeof(hh), hipMemcpyDeviceToHost, st), "D2H views head");
+    gpu::check_hip(hipMemcpyAsync(hs.data(), dev + o_samples, hs.size() * 2, hipMemcpyDeviceToHost, st), "D2H view samples");
+    gpu::check_hip(hipMemcpyAsync(hb.data(), dev + o_bits, hb.size() * 8, hipMemcpyDeviceToHost, st), "D2H view masks");
+    gpu::check_hip(hipStreamSynchronize(st), "k_volume_views");
+    VolumeViews r;
+    r.w = w, r.h = h, r.d = d;
+    r.at_mode = a.mode;
+    r.inverted = inverted;
+    r.has_box = hh.has_box != 0;
+    for (int k = 0; k < 3; ++k) r.at[k] = hh.at[k];
+    for (int k = 0; k < 6; ++k) r.box[k] = hh.box[k];
+    const uint8_t t = pt == kU8 ? (uint8_t)kU16 : (uint8_t)pt;
+    for (int i = 0; i < kVolumeViewCount; ++i) {
+      VolumeView& q = r.view[i];
+      q.w = L.vw[i];
+      q.h = L.vh[i];
+      q.raw_min = (int32_t)raw_value_from_key((uint16_t)hh.stats[i].key_min, t);
+      q.raw_max = (int32_t)raw_value_from_key((uint16_t)hh.stats[i].key_max, t);
+      q.mask_px = hh.mask_px[i];
+      q.raw.assign(hs.begin() + L.sample_off[i], hs.begin() + L.sample_off[i] + (size_t)q.w * q.h);
+      q.mask.assign((size_t)q.w * q.h, 0);
+      for (int y = 0; y < q.h; ++y)
+        for (int x = 0; x < q.w; ++x) q.mask[(size_t)y * q.w + x] = (hb[L.mask_off[i] + (size_t)y * L.wpr[i] + x / 64] >> (x % 64)) & 1;
+    }
+    return views_dict(r);
+  }, py::arg("raw"), py::arg("dilated"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("plane_stride"),
+     py::arg("at") = py::str("mask"), py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("inverted") = false,
+     py::arg("stream") = 0);
 
   // K11 on a batch of masks of ANY sizes in one launch: planes = the masks' bit planes back to back
   // (mask i: hs[i] × ceil(ws[i] / 64) words); raw = the slices' u16 samples back to back; one pixel type

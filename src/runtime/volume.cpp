@@ -346,12 +346,44 @@ struct ExportBufs {
   }
 };
 
+// K14 (export_views): the six views' sample and bit planes (masks, then their borders), the projection
+// scratch, the head (P, box, stats, popcounts) with its pinned copy, the border operator's scratch for
+// view planes too large for LDS, and the two extra events of the timing. Allocated by the first
+// export_views, kept, rebuilt with the volume.
+struct ViewBufs {
+  VolumeViewsLayout L;
+  DevBuf samples, bits, proj, head, scratch;
+  VolumeViewsHead* h_head = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+  static size_t scratch_words(const VolumeViewsLayout& l) {
+    size_t n = 0;
+    for (int i = 0; i < 3; ++i) n = std::max(n, morph3d_scratch_words(l.vw[i], l.vh[i], 2));
+    return n;
+  }
+  explicit ViewBufs(const VolumeViewsLayout& l)
+      : L(l), samples(l.samples * 2), bits(l.bit_words * 8), proj(l.proj * 4), head(sizeof(VolumeViewsHead)),
+        scratch(8 * scratch_words(l)) {
+    check_hip(hipHostMalloc((void**)&h_head, sizeof(VolumeViewsHead), hipHostMallocDefault), "hipHostMalloc views head");
+    check_hip(hipEventCreate(&e0), "event");
+    check_hip(hipEventCreate(&e1), "event");
+    check_hip(hipEventCreate(&e2), "event");
+  }
+  ~ViewBufs() {
+    if (h_head) (void)hipHostFree(h_head);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (e2) (void)hipEventDestroy(e2);
+  }
+};
+
 // Device buffers, stream and events are cached across runs (allocation and stream creation cost
 // more than the kernels for a 256³ volume); they are rebuilt only when the volume shape changes.
 struct VolumeRunner::Impl {
   int device;
   std::unique_ptr<VolumeDevice> V;
   std::unique_ptr<ExportBufs> X;
+  std::unique_ptr<ViewBufs> W;  // K14's buffers (first export_views)
+  bool views_loaded = false;    // K14's code object (first export_views)
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   bool measure_loaded = false;  // K8's code object (first measuring run)
   bool lesions_loaded = false;  // K10's code object (first run that asks for lesions)
@@ -367,6 +399,7 @@ struct VolumeRunner::Impl {
   }
   ~Impl() {
     (void)hipSetDevice(device);
+    W.reset();
     X.reset();
     V.reset();
     if (e0) (void)hipEventDestroy(e0);
@@ -384,6 +417,7 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
   Impl& I = *impl_;
   check_hip(hipSetDevice(I.device), "hipSetDevice");
   if (!I.V || I.V->w != v.w || I.V->h != v.h || I.V->d != v.d) {
+    I.W.reset();
     I.X.reset();
     I.V.reset();
     I.V = std::make_unique<VolumeDevice>(v);
@@ -674,6 +708,7 @@ VolumeResult VolumeRunner::run_slab(Comm& comm, const VolumeInput& slab, int z0,
   Impl& I = *impl_;
   check_hip(hipSetDevice(I.device), "hipSetDevice");
   if (!I.V || I.V->w != slab.w || I.V->h != slab.h || I.V->d != slab.d) {
+    I.W.reset();
     I.X.reset();
     I.V.reset();
     I.V = std::make_unique<VolumeDevice>(slab);
@@ -834,6 +869,173 @@ std::vector<std::vector<uint8_t>> VolumeRunner::export_jpegs(const VolumeInput& 
   return files;
 }
 
+VolumeViewsExport VolumeRunner::export_views(const VolumeInput& v, const VolumeParams& p, const RenderParams& rp,
+                                             const ViewsAt& at, bool want_planes, VolumeExportStats* st) {
+  Impl& I = *impl_;
+  if (!I.V || I.V->w != v.w || I.V->h != v.h || I.V->d != v.d) throw DeviceError("export_views: run() this volume first");
+  const std::string at_err = views::at_error(at, v.w, v.h, v.d);
+  if (!at_err.empty()) throw std::invalid_argument("--volume-views-at: " + at_err);
+  check_hip(hipSetDevice(I.device), "hipSetDevice");
+  VolumeDevice& V = *I.V;
+  const int cw = rp.out_width, ch = rp.out_height;
+  if (cw % 16 || ch % 16) throw DeviceError("canvas size must be a multiple of 16");
+  if (!I.X || I.X->cw != cw || I.X->ch != ch) {
+    I.X.reset();
+    I.X = std::make_unique<ExportBufs>(cw, ch, V.words * V.d);
+  }
+  ExportBufs& X = *I.X;
+  // First use: K14's code object while the stream is idle (run() and export_jpegs() end with a
+  // synchronisation), then its buffers.
+  if (!I.views_loaded) {
+    preload_volume_views();
+    I.views_loaded = true;
+  }
+  if (!I.W) I.W = std::make_unique<ViewBufs>(volume_views_layout(v.w, v.h, v.d));
+  ViewBufs& W = *I.W;
+  const VolumeViewsLayout& L = W.L;
+  const double t0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  const float slope = p.pipe.apply_rescale ? v.slope : 1.f, intercept = p.pipe.apply_rescale ? v.intercept : 0.f;
+  const bool inverted = slope < 0.f;
+  auto* head = W.head.as<VolumeViewsHead>();
+  uint64_t* bits = W.bits.as<uint64_t>();
+  check_hip(hipEventRecord(W.e0, V.stream), "event");
+  launch_volume_views(V.raw.as<uint16_t>(), V.ps, V.dil.as<uint64_t>(), (uint8_t)v.type, (uint8_t)v.stored_bits, inverted, at, L,
+                      W.samples.as<uint16_t>(), bits, W.proj.as<uint32_t>(), head, V.stream);
+  check_hip(hipEventRecord(W.e1, V.stream), "event");
+  // The renderer border in each view's own image: views of one size are neighbours, a two-plane volume.
+  for (int i = 0; i < 3; ++i)
+    border_volume(bits + L.mask_off[i], bits + L.border_off + L.mask_off[i], L.vw[i], L.vh[i], 2, rp.border_radius, V.stream,
+                  W.scratch.as<uint64_t>());
+  const jpeg::Tables tables = jpeg::make_tables(rp.jpeg_quality);
+  const jpeg::Sampling samp = (jpeg::Sampling)rp.jpeg_sampling;
+  const std::vector<uint8_t> header = jpeg::make_header(cw, ch, tables, samp);
+  const uint8_t fill = opacity_u8(rp.label_opacity), bval = opacity_u8(rp.border_opacity);
+  const size_t canvas_bytes = (size_t)cw * ch;
+  const int nc = 2 * kVolumeViewCount;
+  auto* rd = reinterpret_cast<RenderDesc*>(X.h_tables);
+  auto* jd = reinterpret_cast<JpegDesc*>(X.h_tables + (size_t)X.cap * sizeof(RenderDesc));
+  bool any_canvas = false;
+  for (int k = 0; k < nc; ++k) {
+    const int i = k / 2;
+    float su = 1.f, sv = 1.f;
+    views::view_spacing(i, v.spacing_x, v.spacing_y, v.spacing_z, &su, &sv);
+    const RenderGeom g = make_render_geom(L.vw[i], L.vh[i], su, sv, cw, ch);
+    RenderDesc& r = rd[k];
+    std::memset(&r, 0, sizeof(r));
+    r.kind = (k & 1) ? kRenderLabels : kRenderRawGray;
+    r.filter = (uint8_t)(rp.filter == kFilterNearest ? 1 : 0);
+    r.type = (uint8_t)v.type;
+    r.stored_bits = (uint8_t)v.stored_bits;
+    r.fill = fill;
+    r.border_value = bval;
+    r.slice = (uint32_t)i;  // the view's own key min / max
+    r.src_w = (uint16_t)L.vw[i];
+    r.src_h = (uint16_t)L.vh[i];
+    r.wpr = (uint16_t)L.wpr[i];
+    r.ox = g.ox;
+    r.oy = g.oy;
+    r.invx = g.invx;
+    r.invy = g.invy;
+    r.slope = slope;
+    r.intercept = intercept;
+    r.src_off = (k & 1) ? L.mask_off[i] : L.sample_off[i];
+    r.border_off = L.border_off + L.mask_off[i];
+    r.canvas_off = (uint32_t)(k * canvas_bytes);
+    JpegDesc& j = jd[k];
+    std::memset(&j, 0, sizeof(j));
+    j.canvas_off = (uint32_t)(k * canvas_bytes);
+    j.out_off = (uint64_t)k * kVolOutCap;
+    j.out_cap = kVolOutCap;
+    j.render = render_is_exact_2x(r, cw, ch) && (r.kind == kRenderLabels || !r.filter || jpeg_fuses_nearest(samp)) ? k : -1;
+    any_canvas |= j.render < 0;
+  }
+  auto* d_rd = X.tables.as<uint8_t>();
+  auto* d_jd = d_rd + (size_t)X.cap * sizeof(RenderDesc);
+  check_hip(hipMemcpyAsync(d_rd, X.h_tables, (size_t)X.cap * (sizeof(RenderDesc) + sizeof(JpegDesc)), hipMemcpyHostToDevice,
+                           V.stream),
+            "H2D view tables");
+  const auto* drd = reinterpret_cast<const RenderDesc*>(d_rd);
+  const SliceStats* stats = head->stats;  // device address arithmetic only
+  if (any_canvas)
+    launch_render(W.samples.as<uint16_t>(), nullptr, bits, stats, drd, nc, cw, ch, X.canvas.as<uint8_t>(), V.stream);
+  JpegRenderSrc rs;
+  rs.raw = W.samples.as<uint16_t>();
+  rs.bits = bits;
+  rs.stats = stats;
+  rs.rd = drd;
+  rs.nrd = nc;
+  launch_jpeg(X.canvas.as<uint8_t>(), reinterpret_cast<const JpegDesc*>(d_jd), nc, cw, ch, tables.div_luma, X.jw, X.d_out,
+              X.d_sizes, V.stream, &rs, samp, rp.filter == kFilterNearest && jpeg_fuses_nearest(samp));
+  // P, the box and the per-view integers come back once, with the JPEG sizes.
+  check_hip(hipMemcpyAsync(W.h_head, head, sizeof(VolumeViewsHead), hipMemcpyDeviceToHost, V.stream), "D2H views head");
+  check_hip(hipEventRecord(W.e2, V.stream), "event");
+  check_hip(hipStreamSynchronize(V.stream), "views sync");
+  VolumeViewsExport out;
+  out.files.resize((size_t)nc);
+  bool rendered = any_canvas;
+  for (int k = 0; k < nc; ++k) {
+    std::vector<uint8_t>& f = out.files[(size_t)k];
+    f = header;
+    if (X.h_sizes[k] >= 0) {
+      f.insert(f.end(), X.h_out + (size_t)k * kVolOutCap, X.h_out + (size_t)k * kVolOutCap + X.h_sizes[k]);
+    } else {  // capacity overflow: host encoder on the rendered canvas
+      if (!rendered) {
+        launch_render(W.samples.as<uint16_t>(), nullptr, bits, stats, drd, nc, cw, ch, X.canvas.as<uint8_t>(), V.stream);
+        check_hip(hipStreamSynchronize(V.stream), "fallback render");
+        rendered = true;
+      }
+      std::vector<uint8_t> canvas(canvas_bytes);
+      check_hip(hipMemcpy(canvas.data(), X.canvas.as<uint8_t>() + (size_t)k * canvas_bytes, canvas_bytes, hipMemcpyDeviceToHost),
+                "canvas D2H");
+      const auto scan = jpeg::encode_scan_gray(canvas.data(), cw, ch, cw, tables, samp);
+      f.insert(f.end(), scan.begin(), scan.end());
+      if (st) ++st->jpeg_fallbacks;
+    }
+    f.push_back(0xFF);
+    f.push_back(0xD9);
+  }
+  const VolumeViewsHead& hh = *W.h_head;
+  VolumeViews& r = out.views;
+  r.w = v.w, r.h = v.h, r.d = v.d;
+  r.at_mode = at.mode;
+  r.inverted = inverted;
+  r.has_box = hh.has_box != 0;
+  for (int a = 0; a < 3; ++a) r.at[a] = hh.at[a];
+  for (int a = 0; a < 6; ++a) r.box[a] = hh.box[a];
+  const uint8_t type = v.type == kU8 ? (uint8_t)kU16 : (uint8_t)v.type;
+  for (int i = 0; i < kVolumeViewCount; ++i) {
+    VolumeView& q = r.view[i];
+    q.w = L.vw[i];
+    q.h = L.vh[i];
+    // the smallest and the largest stored sample: keys are in value order
+    q.raw_min = (int32_t)raw_value_from_key((uint16_t)hh.stats[i].key_min, type);
+    q.raw_max = (int32_t)raw_value_from_key((uint16_t)hh.stats[i].key_max, type);
+    q.mask_px = hh.mask_px[i];
+  }
+  if (want_planes) {
+    std::vector<uint16_t> hs(L.samples);
+    std::vector<uint64_t> hb(L.border_off);
+    check_hip(hipMemcpy(hs.data(), W.samples.p, hs.size() * 2, hipMemcpyDeviceToHost), "D2H view samples");
+    check_hip(hipMemcpy(hb.data(), W.bits.p, hb.size() * 8, hipMemcpyDeviceToHost), "D2H view masks");
+    for (int i = 0; i < kVolumeViewCount; ++i) {
+      VolumeView& q = r.view[i];
+      q.raw.assign(hs.begin() + L.sample_off[i], hs.begin() + L.sample_off[i] + (size_t)q.w * q.h);
+      q.mask.assign((size_t)q.w * q.h, 0);
+      for (int y = 0; y < q.h; ++y)
+        for (int x = 0; x < q.w; ++x)
+          q.mask[(size_t)y * q.w + x] = (hb[L.mask_off[i] + (size_t)y * L.wpr[i] + x / 64] >> (x % 64)) & 1;
+    }
+  }
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, W.e0, W.e1);
+  out.k14_s = ms * 1e-3;
+  (void)hipEventElapsedTime(&ms, W.e1, W.e2);
+  out.render_s = ms * 1e-3;
+  if (st)
+    st->export_s += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0;
+  return out;
+}
+
 VolumeResult run_volume(const VolumeInput& v, const VolumeParams& p, int device, bool want_masks) {
   VolumeRunner runner(device);
   return runner.run(v, p, want_masks);
@@ -861,6 +1063,7 @@ struct VolOutcome {
   int64_t exchanged = 0;      // --split-volume: boundary + halo bytes sent
   std::string measure_json;   // --measure-volume: the sidecar text (measure::volume_to_json)
   double measure_s = 0;       // --measure-volume: GPU time of K8
+  int32_t view_files = 0;     // --volume-views: view files written (12, or 0)
 };
 
 std::vector<uint8_t> encode(const std::vector<VolPatient>& pl) {
@@ -961,7 +1164,8 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
                                                       std::vector<VolumeLesion>* lesions = nullptr,
                                                       IntensityStats* intensity = nullptr,
                                                       measure::Glcm* texture = nullptr,
-                                                      std::vector<VolumeLesionDiameters>* diameters = nullptr) {
+                                                      std::vector<VolumeLesionDiameters>* diameters = nullptr,
+                                                      const ViewsAt* views_at = nullptr, VolumeViewsExport* views = nullptr) {
   const GoldenPlanes gp = golden_preprocess(v, vp);
   std::vector<Seed> seeds = vp.seeds;
   if (seeds.empty()) {
@@ -977,6 +1181,15 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
     *diameters = golden::measure_volume_diameters(dil, v.w, v.h, v.d, vp.measure_connectivity, vp.measure_lesions, vp.spacing_um);
   if (measured && intensity && vp.measure_intensity) *intensity = golden::measure_intensity(dil, v);
   if (measured && texture && vp.measure_texture) *texture = golden::measure_texture(dil, v, vp.texture_levels);
+  if (views_at && views) {  // --volume-views: the golden views and their files (nm03/volume_views.h)
+    // The projections are taken on keys; the maximum of the rescaled floats in gp.vals would render the
+    // same pixels, since the rescale is monotone (tests/test_volume_views.py checks both slope signs).
+    const float slope = vp.pipe.apply_rescale ? v.slope : 1.f, intercept = vp.pipe.apply_rescale ? v.intercept : 0.f;
+    views->views = golden::volume_views(v.raw.data(), dil.data(), v.w, v.h, v.d, (uint8_t)v.type, v.stored_bits, slope < 0.f,
+                                        *views_at);
+    views->files = golden::volume_view_jpegs(views->views, (uint8_t)v.type, v.stored_bits, slope, intercept, v.spacing_x,
+                                             v.spacing_y, v.spacing_z, rp);
+  }
   return golden_export(v, gp.vals, dil, rp);
 }
 
@@ -1149,8 +1362,14 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         const std::string ext = measure::volume_diameters_extent_error(v.w, v.h, v.d, vp.spacing_um);
         if (!ext.empty()) throw std::runtime_error("--measure-volume-diameters: " + ext);
       }
+      VolumeViewsExport vx;
+      if (cfg.volume_views) {  // an explicit point outside this patient's volume fails the patient, on both backends
+        const std::string err = views::at_error(cfg.volume_views_at, v.w, v.h, v.d);
+        if (!err.empty()) throw std::runtime_error("--volume-views-at: " + err);
+      }
       if (cfg.cpu) {
-        files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions, &intensity, &texture, &diameters);
+        files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions, &intensity, &texture, &diameters,
+                                    cfg.volume_views ? &cfg.volume_views_at : nullptr, &vx);
       } else {
         VolumeResult r = runner->run(v, vp, false);
         o.sweeps = r.sweeps;
@@ -1163,10 +1382,21 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         texture = std::move(r.texture);
         VolumeExportStats xs;
         files = runner->export_jpegs(v, vp, rp, &xs);
+        if (cfg.volume_views) vx = runner->export_views(v, vp, rp, cfg.volume_views_at, false, &xs);
         o.export_s = xs.export_s;
         o.fallbacks = xs.jpeg_fallbacks;
       }
       write_planes(pp, 0, v.d, files);
+      if (cfg.volume_views) {  // after the planes: a DICOM stem that equals a view's name loses its plane file
+        for (int k = 0; k < 2 * kVolumeViewCount; ++k)
+          write_file(pp.out_dir + "/" + views::file_name(k / 2, k & 1), vx.files[(size_t)k]);
+        const std::string text = views::to_json(vx.views, v.spacing_x, v.spacing_y, v.spacing_z);
+        const std::string path = pp.out_dir + "/" + views::kSidecarName;
+        std::ofstream f(path, std::ios::binary | std::ios::trunc);
+        f.write(text.data(), (std::streamsize)text.size());
+        if (!f) throw std::runtime_error("Cannot write " + path);
+        o.view_files = 2 * kVolumeViewCount;
+      }
       if (vp.measure) {  // the sidecar next to the planes; its text travels to rank 0 for the table
         o.measure_json = vp.measure_texture
                              ? golden::measure_volume_json(measured, vp.measure_intensity ? &intensity : nullptr,
@@ -1211,6 +1441,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
     w.u64((uint64_t)o.exchanged);
     w.str(o.measure_json);
     w.f64(o.measure_s);
+    w.i32(o.view_files);
   }
   auto all = comm.allgather_bytes(w.b);
   double tot = wall_now() - t_start;
@@ -1236,6 +1467,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       o.exchanged = (int64_t)r.u64();
       o.measure_json = r.str();
       o.measure_s = r.f64();
+      o.view_files = r.i32();
       outs.push_back(std::move(o));
     }
   }
@@ -1328,6 +1560,12 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
     for (int r = 0; r < size; ++r) f << (r ? ", " : "") << walls[r];
     f << "], \"patients\": [" << pj.str() << "]";
     if (cfg.measure_volume) f << ", \"measure_volume\": " << volume_totals_json(volume_totals);
+    if (cfg.volume_views) {
+      int64_t vp_n = 0, vf_n = 0;
+      for (const auto& o : outs) vp_n += o.ok && o.view_files > 0, vf_n += o.ok ? o.view_files : 0;
+      f << ", \"volume_views\": {\"patients\": " << vp_n << ", \"files\": " << vf_n << ", \"at_mode\": \""
+        << views::at_mode_name(cfg.volume_views_at.mode) << "\"}";
+    }
     f << "}\n";
   }
   return 0;
