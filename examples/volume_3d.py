@@ -1,7 +1,7 @@
 """One DICOM series as a 3D volume on the MI355X: per-slice preprocessing, 6-connected 3D region
 growing and a 7×7×7 dilation (BASELINE config 5), checked against the golden 3D model.
 
-    python examples/volume_3d.py --series path/to/series_dir [--ball] [--measure] [--views DIR]
+    python examples/volume_3d.py --series path/to/series_dir [--ball] [--measure] [--views DIR] [--mesh DIR]
 """
 import argparse
 import os
@@ -23,9 +23,13 @@ def main(argv=None):
     ap.add_argument("--views", metavar="DIR",
                     help="also write the axial / coronal / sagittal planes through the lesion and the three projections "
                          "(K14): twelve JPEGs and views.json into DIR")
+    ap.add_argument("--mesh", metavar="DIR",
+                    help="also write the surface of the dilated mask as a closed mesh in mm (K15): mesh.ply and mesh.json "
+                         "into DIR")
     a = ap.parse_args(argv)
     vp = nm.VolumePipeline(nm.PipelineConfig(se_shape=int(a.ball)), connectivity=6, dilation=7, measure=a.measure,
-                           measure_lesions=int(a.measure), measure_diameters=a.measure, views=bool(a.views))
+                           measure_lesions=int(a.measure), measure_diameters=a.measure, views=bool(a.views),
+                           mesh=bool(a.mesh))
     res = vp.run_series(a.series)
     band = res["band"]
     region, dil = vp.golden(band, vp.default_seeds(band))
@@ -50,6 +54,15 @@ def main(argv=None):
         with open(os.path.join(a.views, "views.json"), "w") as f:
             f.write(res["views_json"])
         print(f"views through {res['views_at']}: {len(res['views_jpeg'])} files and views.json in {a.views}")
+    if a.mesh:
+        os.makedirs(a.mesh, exist_ok=True)
+        with open(os.path.join(a.mesh, "mesh.ply"), "wb") as f:
+            f.write(res["mesh_file"])
+        with open(os.path.join(a.mesh, "mesh.json"), "w") as f:
+            f.write(res["mesh_json"])
+        m = res["mesh"]
+        print(f"mesh: {len(m['vertices'])} vertices, {len(m['quads'])} quads ({2 * len(m['quads'])} triangles) of "
+              f"{m['voxels']} voxels: mesh.ply and mesh.json in {a.mesh}")
     return 0 if same else 1
 
 

@@ -18,6 +18,7 @@
 
 #include "nm03/comm.h"
 #include "nm03/engine.h"
+#include "nm03/volume_mesh.h"
 #include "nm03/volume_views.h"
 
 namespace nm03::app {
@@ -113,6 +114,13 @@ struct AppConfig {
   // --volume-views-at mask|centre|X,Y,Z (default mask).
   bool volume_views = false;
   ViewsAt volume_views_at;
+  // --volume-mesh (3d): the surface of the dilated mask as <patient>/mesh.ply (or mesh.stl) and mesh.json
+  // (nm03/volume_mesh.h). --volume-mesh-placement corner|nets, --volume-mesh-format ply|stl,
+  // --volume-mesh-max-mb N: a mesh whose 12 · V + 16 · Q bytes exceed the cap fails the patient.
+  bool volume_mesh = false;
+  int volume_mesh_placement = kMeshCorner;
+  int volume_mesh_format = kMeshPly;
+  uint64_t volume_mesh_max_mb = mesh::kDefaultMaxMb;
   // CLOCK_REALTIME when parse_args began (the --json record's "main_unix_s"): with the launcher's
   // own clock it splits a cold run's wall into process start-up (exec → main) and the rest.
   double main_unix_s = 0;

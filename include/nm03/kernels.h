@@ -10,6 +10,7 @@
 #include "nm03/gpu_types.h"
 #include "nm03/measure.h"
 #include "nm03/pixel_math.h"
+#include "nm03/volume_mesh.h"
 #include "nm03/volume_views.h"
 
 namespace nm03::gpu {
@@ -360,6 +361,45 @@ void launch_volume_views(const uint16_t* raw, size_t raw_plane_stride, const uin
 // Loads K14's code object on the current device: only a VolumeRunner's first export_views and the Python
 // op load it.
 void preload_volume_views();
+
+// K15 (k15_volume_mesh.hip): the surface mesh of nm03/volume_mesh.h from the `dilated` bit volume (d planes of
+// h rows of ceil(w / 64) words), a thread per u64 word of the lattice. Two halves around the one host round
+// trip. launch_volume_mesh: classify (mixed and face words with their popcounts, the voxel count), then the
+// exclusive prefix of the four count streams in raster order — block totals, one workgroup over the totals,
+// downsweep, `scan_block` lattice words per block — and the head (four totals, voxel count) copied to the
+// pinned `h_head`. After the stream is synchronised the host sizes the result (mesh::size_error) and
+// launch_volume_mesh_emit writes the positions (3 · V floats) and the quads (4 · Q indices, x then y then z)
+// with plain vector stores. Separate launches; no cooperative launch, grid barrier, flag, look-back or spin.
+// `work`: volume_mesh_work_bytes of device memory, no initialisation needed, kept between the two halves.
+struct VolumeMeshHead {
+  uint64_t total[4];  // vertices, x-quads, y-quads, z-quads
+  uint64_t voxels;
+};
+constexpr int kVolumeMeshScanBlock = mesh::kScanBlock;        // the default
+constexpr int kVolumeMeshMinScanBlock = mesh::kMinScanBlock;  // tests force many blocks on a small volume
+constexpr int kVolumeMeshMaxScanBlock = mesh::kMaxScanBlock;
+struct VolumeMeshLayout {
+  int w = 0, h = 0, d = 0;
+  int lw = 0;           // lattice words per row, ceil((w + 1) / 64)
+  uint32_t words = 0;   // lattice words, lw · (h + 1) · (d + 1) < 2^31
+  uint32_t scan_block = 0, blocks = 0;
+  size_t off_head = 0, off_bits = 0, off_counts = 0, off_blocks = 0;  // byte offsets into `work`
+  size_t bytes = 0;     // 48 bytes per lattice word, 16 per block, the head
+};
+// scan_block 0 = the default. Throws DeviceError for an empty volume, a lattice of 2^31 words or more and a
+// scan block outside kVolumeMeshMinScanBlock .. kVolumeMeshMaxScanBlock.
+VolumeMeshLayout volume_mesh_layout(int w, int h, int d, int scan_block = 0);
+size_t volume_mesh_work_bytes(int w, int h, int d, int scan_block = 0);
+void launch_volume_mesh(const uint64_t* dilated, const VolumeMeshLayout& L, void* work, VolumeMeshHead* h_head,
+                        hipStream_t stream);
+// `totals`: the head launch_volume_mesh left, read after the stream was synchronised; `positions` / `quads`
+// hold at least its 3 · V floats and 4 · Q indices (16-byte aligned). Throws DeviceError before any launch
+// when V or 2 · Q reaches 2^31. An empty mask launches nothing.
+void launch_volume_mesh_emit(const uint64_t* dilated, const VolumeMeshLayout& L, const void* work, const VolumeMeshHead& totals,
+                             int placement, float sx, float sy, float sz, float* positions, uint32_t* quads, hipStream_t stream);
+// Loads K15's code object on the current device: only a VolumeRunner's first export_mesh and the Python op
+// load it.
+void preload_volume_mesh();
 
 // K6: binary threshold lo ≤ x ≤ hi → u8 0/1 (in 16-byte aligned, out 4-byte aligned).
 void launch_threshold(const float* in, uint8_t* out, size_t n, float lo, float hi, hipStream_t stream);

@@ -12,6 +12,7 @@
 #include "nm03/comm.h"
 #include "nm03/engine.h"
 #include "nm03/measure.h"
+#include "nm03/volume_mesh.h"
 #include "nm03/volume_views.h"
 
 namespace nm03 {
@@ -140,6 +141,16 @@ class VolumeRunner {
   // `want_planes`: also copy the sample and mask planes back.
   VolumeViewsExport export_views(const VolumeInput& v, const VolumeParams& p, const RenderParams& rp, const ViewsAt& at,
                                  bool want_planes = false, struct VolumeExportStats* stats = nullptr);
+  // After run() on the same volume (--volume-mesh): the surface mesh of nm03/volume_mesh.h from the dilated
+  // bit planes still on the device (K15), equal to golden::volume_mesh of the dilated mask at the volume's
+  // spacing. The first call loads K15's code object and allocates its work buffer, kept like the others and
+  // rebuilt with the volume shape; the result buffer is kept and regrown. Without a call nothing of K15 is
+  // touched. One host round trip: the totals come back, the sizes are checked (vertices and 2 · quads below
+  // 2^31, 12 · V + 16 · Q ≤ max_bytes; std::runtime_error naming V, Q and the cap, nothing emitted), then
+  // positions and quads are written and copied back with one copy each. A volume left by run_slab is
+  // refused. `scan_block`: lattice words per block of the prefix scan (0 = default).
+  VolumeMesh export_mesh(const VolumeInput& v, const VolumeParams& p, int placement = kMeshCorner,
+                         uint64_t max_bytes = mesh::kDefaultMaxMb << 20, int scan_block = 0);
   // One rank's z-slab of a `depth`-deep volume (volume_slabs.h): `slab` holds planes
   // [z0, z0 + slab.d); seeds (p.seeds, or the reference pattern on plane depth / 2) are in volume
   // coordinates. Preprocesses the slab's planes, runs the global region-growing fixpoint and the

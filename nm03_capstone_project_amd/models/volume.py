@@ -26,7 +26,14 @@ still on the device. `views_at` is "mask" (default: the centre of the dilated ma
 volume's centre when the mask is empty), "centre" or a voxel (x, y, z). The result gains `views` (a dict
 name → {width, height, raw, mask, raw_min, raw_max, mask_px}), `views_at` (x, y, z), `views_json` (the text
 of the CLI's views.json, from the one native writer) and `views_jpeg` (file name → the bytes of the twelve
-JPEGs the CLI writes, rendered at the config's canvas, quality, sampling and filter)."""
+JPEGs the CLI writes, rendered at the config's canvas, quality, sampling and filter).
+
+With `mesh=True` every run also extracts the surface of the dilated mask as a closed, indexed quad mesh in
+millimetres (K15, nm03/volume_mesh.h) from the bit planes still on the device. `mesh_placement` is "corner"
+or "nets", `mesh_format` "ply" or "stl", `mesh_max_mb` the cap on 12 · V + 16 · Q bytes (a larger mesh raises
+RuntimeError). The result gains `mesh` (vertices float32 [V, 3], quads int32 [Q, 4], quads_x / _y / _z,
+voxels), `mesh_file` (the bytes of the CLI's mesh.ply / mesh.stl) and `mesh_json` (the text of mesh.json),
+both from the one native writer."""
 import numpy as np
 
 from .._native import native
@@ -42,7 +49,8 @@ def _meta_args(meta):
 class VolumePipeline:
     def __init__(self, config: PipelineConfig = None, connectivity: int = 6, dilation: int = 7, measure: bool = False,
                  measure_connectivity: int = 26, measure_lesions: int = 0, measure_intensity: bool = False, measure_texture: bool = False,
-                 texture_levels: int = 32, measure_diameters: bool = False, views: bool = False, views_at="mask"):
+                 texture_levels: int = 32, measure_diameters: bool = False, views: bool = False, views_at="mask",
+                 mesh: bool = False, mesh_placement: str = "corner", mesh_format: str = "ply", mesh_max_mb: int = 512):
         self.config = config or PipelineConfig()
         self.connectivity = connectivity
         self.dilation = dilation
@@ -73,6 +81,18 @@ class VolumePipeline:
             raise ValueError(f"views_at must be 'mask', 'centre' or (x, y, z) (got {views_at!r})")
         if self.views and self.config.host_only:
             raise ValueError("views are extracted, rendered and encoded on the GPU: not available with host_only")
+        self.mesh = bool(mesh)
+        self.mesh_placement = str(mesh_placement)
+        self.mesh_format = str(mesh_format)
+        self.mesh_max_mb = int(mesh_max_mb)
+        if self.mesh_placement not in ("corner", "nets"):
+            raise ValueError(f"mesh_placement must be 'corner' or 'nets' (got {mesh_placement!r})")
+        if self.mesh_format not in ("ply", "stl"):
+            raise ValueError(f"mesh_format must be 'ply' or 'stl' (got {mesh_format!r})")
+        if self.mesh_max_mb < 0:
+            raise ValueError(f"mesh_max_mb must not be negative (got {mesh_max_mb})")
+        if self.mesh and self.config.host_only:
+            raise ValueError("the mesh is extracted on the GPU: not available with host_only")
         self._runners = {}  # device -> native VolumeRunner (buffers/stream reused across volumes)
 
     def default_seeds(self, volume):
@@ -112,6 +132,13 @@ class VolumePipeline:
             res["views_at"] = tuple(x["at"])
             res["views_json"] = x["views_json"]
             res["views_jpeg"] = x["views_jpeg"]
+        if self.mesh:  # K15 on the dilated bit planes the run left on the device
+            d, h, w = vol.shape
+            sp = [float(v) for v in spacing]
+            m = runner.export_mesh(w, h, d, self.mesh_placement, sp, self.mesh_max_mb << 20)
+            res["mesh"] = m
+            res["mesh_file"] = native().volume_mesh_file(m, self.mesh_format)
+            res["mesh_json"] = native().volume_mesh_to_json(m, self.mesh_format, len(res["mesh_file"]), sp)
         return res
 
     def run_series(self, series_dir, seeds=None, device=None):
@@ -120,7 +147,7 @@ class VolumePipeline:
         (utils.series_geometry) and the first slice's storage format go with it."""
         from ..utils.dicom import read_series, series_geometry
         vol, slices = read_series(series_dir)
-        if not self.measure and not self.views:
+        if not self.measure and not self.views and not self.mesh:
             return self.run(vol, seeds=seeds, device=device)
         g = series_geometry(series_dir)
         return self.run(vol, seeds=seeds, device=device, spacing=(g["spacing_x"], g["spacing_y"], g["spacing_z"]),

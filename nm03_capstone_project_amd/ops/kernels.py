@@ -588,3 +588,30 @@ def volume_views(raw, dilated, at="mask", pixel_type="u16", stored_bits=16, inve
     dw = pack_bits(dilated.bool()).contiguous()
     return native().k_volume_views(x.data_ptr(), dw.data_ptr(), w, h, d, stride, at, pixel_type, int(stored_bits),
                                    bool(inverted), _stream())
+
+
+def volume_mesh(mask, spacing=(1, 1, 1), placement="corner", scan_block=None, max_bytes=512 << 20):
+    """The surface of a volume mask as a closed, indexed quad mesh (K15 alone, nm03/volume_mesh.h) → dict:
+    vertices (float32 [V, 3], mm), quads (int32 [Q, 4]: the x-quads, then the y-quads, then the z-quads, each in
+    raster order of their lattice position), quads_x, quads_y, quads_z, voxels, placement, width, height, depth.
+
+    `mask` is a bool CUDA tensor [D, H, W]; `spacing` is (sx, sy, sz) in mm; `placement` is "corner" (vertices at
+    the lattice corners, c − ½ in voxel index space) or "nets" (the mean of the midpoints of the window's
+    crossing edges); the quads do not depend on it. `scan_block` (lattice words per block of the prefix scan,
+    native().volume_mesh_scan_blocks() gives default, smallest and largest) does not change the result either.
+    Four launches (classify, block totals, totals scan, downsweep), one host round trip that sizes the result
+    — a mesh above `max_bytes` (12 per vertex, 16 per quad) raises RuntimeError — then vertices and quads."""
+    if mask.dim() != 3:
+        raise ValueError("mask must be [D, H, W]")
+    if not mask.is_cuda:
+        raise ValueError("masks must be CUDA (HIP) tensors")
+    if placement not in ("corner", "nets"):
+        raise ValueError("placement must be 'corner' or 'nets'")
+    d, h, w = (int(v) for v in mask.shape)
+    if d < 1 or h < 1 or w < 1:
+        raise ValueError("empty volume")
+    spacing = [float(v) for v in spacing]
+    if len(spacing) != 3:
+        raise ValueError("spacing must be (sx, sy, sz)")
+    dw = pack_bits(mask.bool()).contiguous()
+    return native().k_volume_mesh(dw.data_ptr(), w, h, d, spacing, placement, int(scan_block or 0), int(max_bytes), _stream())

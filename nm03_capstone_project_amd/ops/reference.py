@@ -697,3 +697,73 @@ def volume_views(raw, dilated, at="mask", pixel_type="u16", stored_bits=16, inve
                        "mask_px": int(k.sum())}
     return {"width": w, "height": h, "depth": d, "at_mode": mode, "at": p, "mask_bbox": box, "inverted": bool(inverted),
             "views": views}
+
+
+def volume_mesh(mask, spacing=(1, 1, 1), placement="corner"):
+    """NumPy reference of ops.volume_mesh / native.golden_volume_mesh (nm03/volume_mesh.h) on a [D, H, W] mask
+    (array or CPU tensor): the same dict of vertices (float32 [V, 3]), quads (int32 [Q, 4]), quads_x / _y / _z
+    and voxels, from whole-array operations on the padded mask rather than loops or word arithmetic."""
+    import numpy as np
+    m = np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask).astype(bool)
+    if m.ndim != 3:
+        raise ValueError("mask must be [D, H, W]")
+    if placement not in ("corner", "nets"):
+        raise ValueError("placement must be 'corner' or 'nets'")
+    d, h, w = m.shape
+    p = np.zeros((d + 2, h + 2, w + 2), dtype=np.int8)  # voxel (x, y, z) at p[z + 1, y + 1, x + 1]
+    p[1:-1, 1:-1, 1:-1] = m
+
+    def win(dx, dy, dz):  # voxel (i - 1 + dx, j - 1 + dy, k - 1 + dz) of every corner, [d + 1, h + 1, w + 1]
+        return p[dz:dz + d + 1, dy:dy + h + 1, dx:dx + w + 1]
+
+    vox = [[[win(dx, dy, dz) for dx in (0, 1)] for dy in (0, 1)] for dz in (0, 1)]  # vox[dz][dy][dx]
+    total = sum(vox[dz][dy][dx].astype(np.int32) for dz in (0, 1) for dy in (0, 1) for dx in (0, 1))
+    mixed = (total > 0) & (total < 8)
+    rank = np.full(mixed.shape, -1, dtype=np.int64)
+    rank[mixed] = np.arange(int(mixed.sum()))
+    kk, jj, ii = np.nonzero(mixed)  # raster order (k, j, i)
+    c = np.stack([ii, jj, kk], axis=1).astype(np.int64)
+    if placement == "corner":
+        n = np.ones(len(c), dtype=np.int64)
+        s = np.zeros((len(c), 3), dtype=np.int64)
+    else:
+        n = np.zeros(mixed.shape, dtype=np.int64)
+        s = np.zeros(mixed.shape + (3,), dtype=np.int64)
+        for a in range(3):  # edges along axis a: the two voxels differ in offset a only
+            for u in (0, 1):
+                for v in (0, 1):
+                    o0, o1 = [0, 0, 0], [0, 0, 0]
+                    b, cc = (a + 1) % 3, (a + 2) % 3
+                    o0[a], o1[a] = 0, 1
+                    o0[b] = o1[b] = u
+                    o0[cc] = o1[cc] = v
+                    cross = vox[o0[2]][o0[1]][o0[0]] != vox[o1[2]][o1[1]][o1[0]]
+                    n += cross
+                    s[..., b] += cross * (2 * u - 1)
+                    s[..., cc] += cross * (2 * v - 1)
+        n = n[mixed]
+        s = s[mixed]
+    num = (2 * c - 1) * n[:, None] + s
+    sp = np.asarray([np.float32(spacing[0]), np.float32(spacing[1]), np.float32(np.float64(spacing[2]))], dtype=np.float32)
+    verts = (num.astype(np.float32) / (2 * n[:, None]).astype(np.float32)).astype(np.float32) * sp[None, :]
+    verts = verts.astype(np.float32).reshape(-1, 3)
+    quads, counts = [], []
+    e = np.eye(3, dtype=np.int64)
+    for a in range(3):
+        b, cc = (a + 1) % 3, (a + 2) % 3
+        sl_lo = [slice(1, -1)] * 3  # numpy axes are (z, y, x): axis a of the mesh is numpy axis 2 - a
+        sl_hi = [slice(1, -1)] * 3
+        sl_lo[2 - a] = slice(0, -1)
+        sl_hi[2 - a] = slice(1, None)
+        lower, upper = p[tuple(sl_lo)], p[tuple(sl_hi)]  # voxel p - e_a and voxel p for p_a in [0, dim_a]
+        pz, py, px = np.nonzero(lower != upper)
+        pos = np.stack([px, py, pz], axis=1).astype(np.int64)
+        low_set = lower[pz, py, px] == 1
+        cs = [pos, pos + e[b], pos + e[b] + e[cc], pos + e[cc]]
+        idx = [rank[q[:, 2], q[:, 1], q[:, 0]] for q in cs]
+        q = np.stack([idx[0], np.where(low_set, idx[1], idx[3]), idx[2], np.where(low_set, idx[3], idx[1])], axis=1)
+        quads.append(q)
+        counts.append(len(q))
+    quads = np.concatenate(quads, axis=0).astype(np.int32).reshape(-1, 4)
+    return {"width": w, "height": h, "depth": d, "placement": placement, "vertices": verts, "quads": quads,
+            "quads_x": counts[0], "quads_y": counts[1], "quads_z": counts[2], "voxels": int(m.sum())}

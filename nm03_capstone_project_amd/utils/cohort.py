@@ -193,3 +193,40 @@ def read_volume_views(out_dir):
             with open(os.path.join(out_dir, name), "rb") as f:
                 rec["files"][name] = f.read()
     return rec
+
+
+def read_volume_mesh(path):
+    """The mesh.ply the 3D CLI writes with --volume-mesh (binary little-endian PLY; `path` is the file or the
+    patient directory that holds it) → dict: vertices (float32 [V, 3], mm), triangles (int32 [T, 3]), quads
+    (int32 [T / 2, 4]: the writer stores every quad (q0, q1, q2, q3) as the triangles (q0, q1, q2) and
+    (q0, q2, q3)) and comments (the header's comment lines)."""
+    import os
+
+    import numpy as np
+    if os.path.isdir(path):
+        path = os.path.join(path, "mesh.ply")
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    lines = data[:end].decode("ascii").split("\n")
+    if "format binary_little_endian 1.0" not in lines:
+        raise ValueError(f"{path}: only binary_little_endian 1.0 is read")
+    counts = {}
+    for ln in lines:
+        parts = ln.split()
+        if len(parts) == 3 and parts[0] == "element":
+            counts[parts[1]] = int(parts[2])
+    nv, nf = counts.get("vertex", 0), counts.get("face", 0)
+    body = end + len(b"end_header\n")
+    if len(data) != body + 12 * nv + 13 * nf:
+        raise ValueError(f"{path}: {len(data)} bytes, expected {body + 12 * nv + 13 * nf}")
+    verts = np.frombuffer(data, dtype="<f4", count=3 * nv, offset=body).reshape(nv, 3).copy()
+    faces = np.frombuffer(data, dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]), count=nf, offset=body + 12 * nv)
+    if nf and not (faces["n"] == 3).all():
+        raise ValueError(f"{path}: a face is not a triangle")
+    tri = faces["v"].astype(np.int32).reshape(nf, 3)
+    quads = np.concatenate([tri[0::2], tri[1::2, 2:3]], axis=1) if nf else np.zeros((0, 4), dtype=np.int32)
+    return {"vertices": verts, "triangles": tri, "quads": quads.astype(np.int32),
+            "comments": [ln[len("comment "):] for ln in lines if ln.startswith("comment ")]}

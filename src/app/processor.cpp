@@ -90,6 +90,12 @@ void usage(const std::string& which) {
             << "                         <patient>/views.json (needs --mode 3d; not with --split-volume)\n"
             << "  --volume-views-at mask|centre|X,Y,Z  the point of --volume-views: the centre of the dilated mask's box\n"
             << "                         (default; the volume's centre when the mask is empty), the volume's centre, or a voxel\n"
+            << "  --volume-mesh          3d: also write the surface of the dilated mask as a closed, indexed mesh in mm:\n"
+            << "                         <patient>/mesh.ply and <patient>/mesh.json (needs --mode 3d; not with --split-volume)\n"
+            << "  --volume-mesh-placement corner|nets  vertices at the lattice corners (default) or at the mean of the\n"
+            << "                         crossing edges' midpoints (naive surface nets); the faces are the same\n"
+            << "  --volume-mesh-format ply|stl  binary PLY (default) or binary STL (mesh.stl)\n"
+            << "  --volume-mesh-max-mb N a mesh above N MiB (12 bytes per vertex, 16 per quad; default 512) fails the patient\n"
             << "  --mode 2d|3d           3d: whole series as a volume (SRG 6-conn + cube dilation)\n"
             << "  --split-volume         3d: each volume split into z-slabs over all ranks (halo exchange)\n"
             << "  --input FILE           test_pipeline: slice to process\n"
@@ -174,6 +180,7 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
   bool measure_texture = false;    // --measure-texture
   bool texture_levels_given = false;
   bool volume_views_at_given = false;
+  const char* volume_mesh_sub = nullptr;  // the first --volume-mesh-* sub-flag given
   c.main_unix_s = main_unix;
   c.data_root = cohort::default_data_root();
   c.out_dir = which == "test_pipeline" ? "../out-test" : which == "img_processing_sequential" ? "../out-sequential" : "../out-parallel";
@@ -323,6 +330,34 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
       }
       volume_views_at_given = true;
     }
+    else if (a == "--volume-mesh") c.volume_mesh = true;
+    else if (a == "--volume-mesh-placement") {
+      const std::string v = val();
+      if (!mesh::parse_placement(v, &c.volume_mesh_placement)) {
+        std::cerr << "--volume-mesh-placement must be corner or nets (got " << v << ")" << std::endl;
+        std::exit(2);
+      }
+      if (!volume_mesh_sub) volume_mesh_sub = "--volume-mesh-placement";
+    }
+    else if (a == "--volume-mesh-format") {
+      const std::string v = val();
+      if (!mesh::parse_format(v, &c.volume_mesh_format)) {
+        std::cerr << "--volume-mesh-format must be ply or stl (got " << v << ")" << std::endl;
+        std::exit(2);
+      }
+      if (!volume_mesh_sub) volume_mesh_sub = "--volume-mesh-format";
+    }
+    else if (a == "--volume-mesh-max-mb") {
+      const std::string v = val();
+      char* end = nullptr;
+      const unsigned long long mb = std::strtoull(v.c_str(), &end, 10);
+      if (v.empty() || v[0] < '0' || v[0] > '9' || *end != '\0' || mb > (1ull << 20)) {
+        std::cerr << "--volume-mesh-max-mb must be an integer in [0, 1048576] (got " << v << ")" << std::endl;
+        std::exit(2);
+      }
+      c.volume_mesh_max_mb = mb;
+      if (!volume_mesh_sub) volume_mesh_sub = "--volume-mesh-max-mb";
+    }
     else if (a == "--measure-connectivity") {
       const std::string v = val();
       if (v != "4" && v != "8") {
@@ -429,6 +464,20 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
   if (c.volume_views && c.split_volume) {
     std::cerr << "--volume-views is not available with --split-volume: a view crosses the slabs (drop --split-volume to "
                  "get the views, or --volume-views to split the volume)"
+              << std::endl;
+    std::exit(2);
+  }
+  if (volume_mesh_sub && !c.volume_mesh) {
+    std::cerr << volume_mesh_sub << " needs --volume-mesh" << std::endl;
+    std::exit(2);
+  }
+  if (c.volume_mesh && c.mode != "3d") {
+    std::cerr << "--volume-mesh needs --mode 3d" << std::endl;
+    std::exit(2);
+  }
+  if (c.volume_mesh && c.split_volume) {
+    std::cerr << "--volume-mesh is not available with --split-volume: a mesh crosses the slabs (drop --split-volume to "
+                 "get the mesh, or --volume-mesh to split the volume)"
               << std::endl;
     std::exit(2);
   }

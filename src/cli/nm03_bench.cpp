@@ -48,6 +48,9 @@ int main(int argc, char** argv) {
   int texture_levels = 32;
   bool measure_intensity = false;  // cohort with --measure / volume with --measure-volume: also K11 (percentiles, sum of squares)
   bool volume_views = false;       // volume: also K14 and the render + encode of the twelve view files per run
+  bool volume_mesh = false;        // volume: also K15 (the surface mesh of the dilated volume) per run
+  int mesh_placement = nm03::kMeshCorner;
+  uint64_t mesh_max_mb = nm03::mesh::kDefaultMaxMb;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto v = [&] { return std::string(argv[++i]); };
@@ -89,6 +92,14 @@ int main(int argc, char** argv) {
     else if (a == "--measure-volume-diameters") measure_volume_diameters = true;
     else if (a == "--volume-diameters-brute-force") diameters_brute_force = true;
     else if (a == "--volume-views") volume_views = true;
+    else if (a == "--volume-mesh") volume_mesh = true;
+    else if (a == "--volume-mesh-placement") {
+      if (!nm03::mesh::parse_placement(v(), &mesh_placement)) {
+        std::cerr << "--volume-mesh-placement must be corner or nets" << std::endl;
+        return 2;
+      }
+    }
+    else if (a == "--volume-mesh-max-mb") mesh_max_mb = std::stoull(v());
     else if (a == "--se-shape") ec.pipe.se_shape = v() == "disc" ? nm03::kSeDisc : nm03::kSeSquare;
     else if (a == "--render-filter") ec.render.filter = v() == "nearest" ? nm03::kFilterNearest : nm03::kFilterBilinear;
     else {
@@ -103,6 +114,10 @@ int main(int argc, char** argv) {
   if (diameters_brute_force) measure_volume_diameters = true;
   if (volume_views && (config != "volume" || ec.host_only)) {
     std::cerr << "--volume-views needs --config volume and the GPU (not --host-only)" << std::endl;
+    return 2;
+  }
+  if (volume_mesh && (config != "volume" || ec.host_only)) {
+    std::cerr << "--volume-mesh needs --config volume and the GPU (not --host-only)" << std::endl;
     return 2;
   }
   // --measure-intensity implies the measurement it extends: --measure (cohort) or --measure-volume (volume).
@@ -254,6 +269,21 @@ int main(int argc, char** argv) {
         }
         views_ms = (now_s() - t2) * 1e3;
       }
+      // + the surface mesh (K15) of the dilated volume the last run left on the device, as the 3D CLI does with
+      // --volume-mesh: mesh_ms_per_volume from device events, outside kernels_s
+      double mesh_ms = 0, mesh_wall_ms = 0;
+      size_t mesh_v = 0, mesh_q = 0;
+      if (volume_mesh) {
+        for (int w = 0; w < warmup + 1; ++w) runner.export_mesh(v, vp, mesh_placement, mesh_max_mb << 20);
+        const double t3 = now_s();
+        for (int k = 0; k < steps; ++k) {
+          const auto m = runner.export_mesh(v, vp, mesh_placement, mesh_max_mb << 20);
+          mesh_ms += m.k15_s * 1e3;
+          mesh_v = m.vertices();
+          mesh_q = m.quad_count();
+        }
+        mesh_wall_ms = (now_s() - t3) * 1e3;
+      }
       std::cout << "{\"config\": \"volume\", \"dims\": [" << v.w << ", " << v.h << ", " << v.d << "], \"steps\": " << steps
                 << ", \"ms_per_volume\": " << dt * 1e3 / steps << ", \"gpu_ms_per_volume\": " << ks * 1e3 / steps
                 << ", \"sweeps\": " << sweeps << ", \"ms_per_volume_with_export\": " << dt2 * 1e3 / steps
@@ -270,6 +300,10 @@ int main(int argc, char** argv) {
       if (volume_views)
         std::cout << ", \"views_ms_per_volume\": " << views_ms / steps << ", \"views_k14_ms\": " << k14_ms / steps
                   << ", \"views_render_encode_ms\": " << views_render_ms / steps << ", \"views_jpeg_bytes\": " << view_bytes;
+      if (volume_mesh)
+        std::cout << ", \"mesh_ms_per_volume\": " << mesh_ms / steps << ", \"mesh_wall_ms_per_volume\": " << mesh_wall_ms / steps
+                  << ", \"mesh_placement\": \"" << nm03::mesh::placement_name(mesh_placement) << "\", \"mesh_vertices\": " << mesh_v
+                  << ", \"mesh_quads\": " << mesh_q;
       if (measure_intensity) std::cout << ", \"intensity\": true, \"raw_p50\": " << vi.pct[2];
       if (measure_texture)
         std::cout << ", \"texture\": true, \"texture_levels\": " << texture_levels << ", \"glcm_pairs\": " << glcm_pairs;

@@ -634,6 +634,61 @@ py::dict view_files_dict(const std::vector<std::vector<uint8_t>>& files) {
   return d;
 }
 
+// --volume-mesh-placement / -format from Python.
+int mesh_placement_from(const std::string& s) {
+  int p = kMeshCorner;
+  if (!mesh::parse_placement(s, &p)) throw std::invalid_argument("placement must be 'corner' or 'nets'");
+  return p;
+}
+int mesh_format_from(const std::string& s) {
+  int f = kMeshPly;
+  if (!mesh::parse_format(s, &f)) throw std::invalid_argument("format must be 'ply' or 'stl'");
+  return f;
+}
+
+// A VolumeMesh as Python sees it: width, height, depth, placement, vertices (float32 [V, 3], mm), quads
+// (int32 [Q, 4]), quads_x / _y / _z, voxels, k15_s.
+py::dict mesh_dict(const VolumeMesh& m) {
+  py::dict d;
+  d["width"] = m.w;
+  d["height"] = m.h;
+  d["depth"] = m.d;
+  d["placement"] = std::string(mesh::placement_name(m.placement));
+  d["vertices"] = to_np<float>(m.positions, {(py::ssize_t)m.vertices(), 3});
+  py::array_t<int32_t> q({(py::ssize_t)m.quad_count(), (py::ssize_t)4});
+  if (!m.quads.empty()) std::memcpy(q.mutable_data(), m.quads.data(), m.quads.size() * 4);
+  d["quads"] = q;
+  d["quads_x"] = m.quads_x;
+  d["quads_y"] = m.quads_y;
+  d["quads_z"] = m.quads_z;
+  d["voxels"] = m.voxels;
+  d["k15_s"] = m.k15_s;
+  return d;
+}
+
+VolumeMesh mesh_from(const py::dict& d) {
+  VolumeMesh m;
+  m.w = d["width"].cast<int>();
+  m.h = d["height"].cast<int>();
+  m.d = d["depth"].cast<int>();
+  m.placement = mesh_placement_from(d["placement"].cast<std::string>());
+  const auto v = d["vertices"].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+  const auto q = d["quads"].cast<py::array_t<int32_t, py::array::c_style | py::array::forcecast>>();
+  if (v.ndim() != 2 || v.shape(1) != 3 || q.ndim() != 2 || q.shape(1) != 4)
+    throw std::invalid_argument("mesh: vertices must be [V, 3] and quads [Q, 4]");
+  m.positions.assign(v.data(), v.data() + v.size());
+  m.quads.resize((size_t)q.size());
+  for (py::ssize_t i = 0; i < q.size(); ++i) {
+    if (q.data()[i] < 0 || (size_t)q.data()[i] >= m.vertices()) throw std::invalid_argument("mesh: a quad index is not a vertex");
+    m.quads[(size_t)i] = (uint32_t)q.data()[i];
+  }
+  m.quads_x = d["quads_x"].cast<uint64_t>();
+  m.quads_y = d["quads_y"].cast<uint64_t>();
+  m.quads_z = d["quads_z"].cast<uint64_t>();
+  m.voxels = d["voxels"].cast<uint64_t>();
+  return m;
+}
+
 }  // namespace
 
 template <class Fn>
@@ -1903,6 +1958,28 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("at") = py::str("mask"), py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0}, py::arg("type") = "u16",
           py::arg("stored_bits") = 16, py::arg("slope") = 1.f, py::arg("intercept") = 0.f)
       .def(
+          "export_mesh",
+          // After run() on a volume of this shape: the surface mesh of nm03/volume_mesh.h from the dilated bit
+          // planes still on the device (K15). Returns the mesh dict; a mesh above max_bytes raises RuntimeError.
+          [](VolumeRunner& self, int w, int h, int d, const std::string& placement, const std::vector<double>& spacing,
+             uint64_t max_bytes, int scan_block) {
+            VolumeMeta mt;
+            mt.spacing = spacing;
+            VolumeInput v;
+            v.w = w, v.h = h, v.d = d;
+            apply_meta(mt, v);
+            const int pl = mesh_placement_from(placement);
+            VolumeMesh m;
+            {
+              py::gil_scoped_release nogil;
+              m = self.export_mesh(v, VolumeParams(), pl, max_bytes, scan_block);
+            }
+            return mesh_dict(m);
+          },
+          py::arg("w"), py::arg("h"), py::arg("d"), py::arg("placement") = "corner",
+          py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0}, py::arg("max_bytes") = mesh::kDefaultMaxMb << 20,
+          py::arg("scan_block") = 0)
+      .def(
           "run_slab",
           // One rank's z-slab (planes [z0, z0 + slab depth) of a `depth`-deep volume) through the
           // distributed 3D pipeline over `comm` (collective; volume_slabs.h). Seeds in volume
@@ -2768,6 +2845,129 @@ PYBIND11_MODULE(_nm03, m) {
     return views_dict(r);
   }, py::arg("raw"), py::arg("dilated"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("plane_stride"),
      py::arg("at") = py::str("mask"), py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("inverted") = false,
+     py::arg("stream") = 0);
+
+  // The golden surface mesh (nm03/volume_mesh.h) of the mask `dilated` ([D, H, W], non-zero = set).
+  m.def(
+      "golden_volume_mesh",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dilated, const std::vector<double>& spacing,
+         const std::string& placement) {
+        if (dilated.ndim() != 3) throw std::invalid_argument("dilated must be [D, H, W]");
+        if (spacing.size() != 3) throw std::invalid_argument("spacing must be (sx, sy, sz)");
+        const int pl = mesh_placement_from(placement);
+        VolumeMesh r;
+        {
+          py::gil_scoped_release nogil;
+          r = golden::volume_mesh(dilated.data(), (int)dilated.shape(2), (int)dilated.shape(1), (int)dilated.shape(0),
+                                  (float)spacing[0], (float)spacing[1], spacing[2], pl);
+        }
+        return mesh_dict(r);
+      },
+      py::arg("dilated"), py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0}, py::arg("placement") = "corner");
+  // The same mesh from the K15 kernels' per-word functions and blocked scan, run on the host
+  // (measure::volume_mesh_words): what the kernels compute, without a GPU.
+  m.def(
+      "volume_mesh_words",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> dilated, const std::vector<double>& spacing,
+         const std::string& placement, int scan_block) {
+        if (dilated.ndim() != 3) throw std::invalid_argument("dilated must be [D, H, W]");
+        if (spacing.size() != 3) throw std::invalid_argument("spacing must be (sx, sy, sz)");
+        const int pl = mesh_placement_from(placement);
+        const std::vector<uint64_t> dw = pack_volume(dilated);
+        VolumeMesh r;
+        {
+          py::gil_scoped_release nogil;
+          r = measure::volume_mesh_words(dw.data(), (int)dilated.shape(2), (int)dilated.shape(1), (int)dilated.shape(0),
+                                         (float)spacing[0], (float)spacing[1], spacing[2], pl, scan_block);
+        }
+        return mesh_dict(r);
+      },
+      py::arg("dilated"), py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0}, py::arg("placement") = "corner",
+      py::arg("scan_block") = 0);
+  // (default, smallest, largest) scan block of K15 in lattice words, and the lattice words of a volume.
+  m.def("volume_mesh_scan_blocks", [] { return py::make_tuple(mesh::kScanBlock, mesh::kMinScanBlock, mesh::kMaxScanBlock); });
+  // Empty, or why a mesh of V vertices and Q quads is refused under a cap of max_bytes.
+  m.def("volume_mesh_size_error", [](uint64_t V, uint64_t Q, uint64_t max_bytes) { return mesh::size_error(V, Q, max_bytes); });
+  // The bytes of mesh.ply / mesh.stl of a mesh dict, by the one writer.
+  m.def(
+      "volume_mesh_file",
+      [](const py::dict& md, const std::string& format) {
+        const VolumeMesh vm = mesh_from(md);
+        const std::vector<uint8_t> b = mesh::file_bytes(vm, mesh_format_from(format));
+        return py::bytes((const char*)b.data(), b.size());
+      },
+      py::arg("mesh"), py::arg("format") = "ply");
+  // The text of mesh.json for a mesh dict whose file has `bytes` bytes.
+  m.def(
+      "volume_mesh_to_json",
+      [](const py::dict& md, const std::string& format, uint64_t bytes, const std::vector<double>& spacing) {
+        if (spacing.size() != 3) throw std::invalid_argument("spacing must be (sx, sy, sz)");
+        return mesh::to_json(mesh_from(md), mesh_format_from(format), bytes, (float)spacing[0], (float)spacing[1], spacing[2]);
+      },
+      py::arg("mesh"), py::arg("format") = "ply", py::arg("bytes") = 0, py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0});
+
+  // K15 alone on a device bit volume [d][h][ceil(w/64)] (int64 words). Returns the mesh dict. One host round
+  // trip between the scan and the emission; synchronous on `stream`.
+  m.def("k_volume_mesh", [](uintptr_t dilated, int w, int h, int d, const std::vector<double>& spacing, const std::string& placement,
+                            int scan_block, uint64_t max_bytes, uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    if (w <= 0 || h <= 0 || d <= 0) throw std::invalid_argument("empty volume");
+    if (spacing.size() != 3) throw std::invalid_argument("spacing must be (sx, sy, sz)");
+    const int pl = mesh_placement_from(placement);
+    if (scan_block != 0 && (scan_block < mesh::kMinScanBlock || scan_block > mesh::kMaxScanBlock))
+      throw std::invalid_argument("scan_block must be 0 (default) or " + std::to_string(mesh::kMinScanBlock) + " .. " +
+                                  std::to_string(mesh::kMaxScanBlock));
+    {
+      // K15's code object, loaded on the current device before this op's first launch there.
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_volume_mesh();
+        preloaded.push_back(dev);
+      }
+    }
+    const gpu::VolumeMeshLayout L = gpu::volume_mesh_layout(w, h, d, scan_block);
+    struct DevMem {  // this op's own buffers: the shared scratch may be regrown between the two halves
+      void* p = nullptr;
+      ~DevMem() {
+        if (p) (void)hipFree(p);
+      }
+    } work, out;
+    gpu::check_hip(hipMalloc(&work.p, L.bytes), "hipMalloc mesh work");
+    gpu::VolumeMeshHead* h_head = nullptr;
+    gpu::check_hip(hipHostMalloc((void**)&h_head, sizeof(gpu::VolumeMeshHead), hipHostMallocDefault), "hipHostMalloc mesh head");
+    struct Pinned {
+      void* p;
+      ~Pinned() { (void)hipHostFree(p); }
+    } pinned{h_head};
+    gpu::launch_volume_mesh((const uint64_t*)dilated, L, work.p, h_head, st);
+    gpu::check_hip(hipStreamSynchronize(st), "k_volume_mesh totals");
+    const gpu::VolumeMeshHead hh = *h_head;
+    const uint64_t nv = hh.total[0], nq = hh.total[1] + hh.total[2] + hh.total[3];
+    const std::string err = mesh::size_error(nv, nq, max_bytes);
+    if (!err.empty()) throw std::runtime_error(err);
+    VolumeMesh r;
+    r.w = w, r.h = h, r.d = d;
+    r.placement = pl;
+    r.quads_x = hh.total[1], r.quads_y = hh.total[2], r.quads_z = hh.total[3];
+    r.voxels = hh.voxels;
+    r.positions.resize(3 * (size_t)nv);
+    r.quads.resize(4 * (size_t)nq);
+    const size_t pos_bytes = (12 * (size_t)nv + 255) / 256 * 256;
+    gpu::check_hip(hipMalloc(&out.p, std::max<size_t>(pos_bytes + 16 * (size_t)nq, 256)), "hipMalloc mesh result");
+    float* d_pos = (float*)out.p;
+    uint32_t* d_quads = (uint32_t*)((uint8_t*)out.p + pos_bytes);
+    gpu::launch_volume_mesh_emit((const uint64_t*)dilated, L, work.p, hh, pl, (float)spacing[0], (float)spacing[1], (float)spacing[2],
+                                 d_pos, d_quads, st);
+    if (nv) gpu::check_hip(hipMemcpyAsync(r.positions.data(), d_pos, 12 * (size_t)nv, hipMemcpyDeviceToHost, st), "D2H mesh positions");
+    if (nq) gpu::check_hip(hipMemcpyAsync(r.quads.data(), d_quads, 16 * (size_t)nq, hipMemcpyDeviceToHost, st), "D2H mesh quads");
+    gpu::check_hip(hipStreamSynchronize(st), "k_volume_mesh");
+    return mesh_dict(r);
+  }, py::arg("dilated"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0},
+     py::arg("placement") = "corner", py::arg("scan_block") = 0, py::arg("max_bytes") = mesh::kDefaultMaxMb << 20,
      py::arg("stream") = 0);
 
   // K11 on a batch of masks of ANY sizes in one launch: planes = the masks' bit planes back to back

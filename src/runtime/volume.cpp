@@ -376,6 +376,27 @@ struct ViewBufs {
   }
 };
 
+// K15 (export_mesh): the work buffer of the lattice words (bit words, counts / prefixes, block totals, head),
+// the pinned head, the result buffer (positions, then quads; regrown when a mesh needs more) and the events of
+// the timing. Allocated by the first export_mesh, kept, rebuilt with the volume or the scan block.
+struct MeshBufs {
+  VolumeMeshLayout L;
+  DevBuf work;
+  std::unique_ptr<DevBuf> out;
+  size_t out_bytes = 0;
+  VolumeMeshHead* h_head = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
+  explicit MeshBufs(const VolumeMeshLayout& l) : L(l), work(l.bytes) {
+    check_hip(hipHostMalloc((void**)&h_head, sizeof(VolumeMeshHead), hipHostMallocDefault), "hipHostMalloc mesh head");
+    for (hipEvent_t* e : {&e0, &e1, &e2, &e3}) check_hip(hipEventCreate(e), "event");
+  }
+  ~MeshBufs() {
+    if (h_head) (void)hipHostFree(h_head);
+    for (hipEvent_t e : {e0, e1, e2, e3})
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 // Device buffers, stream and events are cached across runs (allocation and stream creation cost
 // more than the kernels for a 256³ volume); they are rebuilt only when the volume shape changes.
 struct VolumeRunner::Impl {
@@ -384,6 +405,9 @@ struct VolumeRunner::Impl {
   std::unique_ptr<ExportBufs> X;
   std::unique_ptr<ViewBufs> W;  // K14's buffers (first export_views)
   bool views_loaded = false;    // K14's code object (first export_views)
+  std::unique_ptr<MeshBufs> M;  // K15's buffers (first export_mesh)
+  bool mesh_loaded = false;     // K15's code object (first export_mesh)
+  bool slab_volume = false;     // the volume on the device was left by run_slab
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   bool measure_loaded = false;  // K8's code object (first measuring run)
   bool lesions_loaded = false;  // K10's code object (first run that asks for lesions)
@@ -399,6 +423,7 @@ struct VolumeRunner::Impl {
   }
   ~Impl() {
     (void)hipSetDevice(device);
+    M.reset();
     W.reset();
     X.reset();
     V.reset();
@@ -417,11 +442,13 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
   Impl& I = *impl_;
   check_hip(hipSetDevice(I.device), "hipSetDevice");
   if (!I.V || I.V->w != v.w || I.V->h != v.h || I.V->d != v.d) {
+    I.M.reset();
     I.W.reset();
     I.X.reset();
     I.V.reset();
     I.V = std::make_unique<VolumeDevice>(v);
   }
+  I.slab_volume = false;
   VolumeDevice& V = *I.V;
   if (p.measure_lesions != 0 && !p.measure)
     throw std::invalid_argument("3D lesion measurements need measure");
@@ -707,7 +734,9 @@ VolumeResult VolumeRunner::run_slab(Comm& comm, const VolumeInput& slab, int z0,
   check_volume_params(p.connectivity, p.dilation_size);
   Impl& I = *impl_;
   check_hip(hipSetDevice(I.device), "hipSetDevice");
+  I.slab_volume = true;
   if (!I.V || I.V->w != slab.w || I.V->h != slab.h || I.V->d != slab.d) {
+    I.M.reset();
     I.W.reset();
     I.X.reset();
     I.V.reset();
@@ -1036,6 +1065,63 @@ VolumeViewsExport VolumeRunner::export_views(const VolumeInput& v, const VolumeP
   return out;
 }
 
+VolumeMesh VolumeRunner::export_mesh(const VolumeInput& v, const VolumeParams& p, int placement, uint64_t max_bytes,
+                                     int scan_block) {
+  (void)p;
+  Impl& I = *impl_;
+  if (!I.V || I.V->w != v.w || I.V->h != v.h || I.V->d != v.d) throw DeviceError("export_mesh: run() this volume first");
+  if (I.slab_volume) throw DeviceError("export_mesh: the volume on the device is a z-slab: a mesh crosses the slabs");
+  if (placement != kMeshCorner && placement != kMeshNets) throw std::invalid_argument("export_mesh: placement must be corner or nets");
+  check_hip(hipSetDevice(I.device), "hipSetDevice");
+  VolumeDevice& V = *I.V;
+  const VolumeMeshLayout L = volume_mesh_layout(v.w, v.h, v.d, scan_block);
+  // First use: K15's code object while the stream is idle (run() ends with a synchronisation), then its buffers.
+  if (!I.mesh_loaded) {
+    preload_volume_mesh();
+    I.mesh_loaded = true;
+  }
+  if (!I.M || I.M->L.scan_block != L.scan_block) {
+    I.M.reset();
+    I.M = std::make_unique<MeshBufs>(L);
+  }
+  MeshBufs& M = *I.M;
+  const uint64_t* dil = V.dil.as<uint64_t>();
+  check_hip(hipEventRecord(M.e0, V.stream), "event");
+  launch_volume_mesh(dil, L, M.work.p, M.h_head, V.stream);
+  check_hip(hipEventRecord(M.e1, V.stream), "event");
+  check_hip(hipStreamSynchronize(V.stream), "mesh totals sync");
+  const VolumeMeshHead hh = *M.h_head;
+  const uint64_t nv = hh.total[0], nq = hh.total[1] + hh.total[2] + hh.total[3];
+  const std::string err = mesh::size_error(nv, nq, max_bytes);
+  if (!err.empty()) throw std::runtime_error("--volume-mesh: " + err);
+  VolumeMesh m;
+  m.w = v.w, m.h = v.h, m.d = v.d;
+  m.placement = placement;
+  m.quads_x = hh.total[1], m.quads_y = hh.total[2], m.quads_z = hh.total[3];
+  m.voxels = hh.voxels;
+  m.positions.resize(3 * (size_t)nv);
+  m.quads.resize(4 * (size_t)nq);
+  const size_t pos_bytes = (12 * (size_t)nv + 255) / 256 * 256, need = pos_bytes + 16 * (size_t)nq;
+  if (!M.out || M.out_bytes < need) {
+    M.out.reset();
+    M.out = std::make_unique<DevBuf>(need);
+    M.out_bytes = need;
+  }
+  float* d_pos = M.out->as<float>();
+  uint32_t* d_quads = reinterpret_cast<uint32_t*>(M.out->as<uint8_t>() + pos_bytes);
+  check_hip(hipEventRecord(M.e2, V.stream), "event");
+  launch_volume_mesh_emit(dil, L, M.work.p, hh, placement, v.spacing_x, v.spacing_y, (float)v.spacing_z, d_pos, d_quads, V.stream);
+  check_hip(hipEventRecord(M.e3, V.stream), "event");
+  if (nv) check_hip(hipMemcpyAsync(m.positions.data(), d_pos, 12 * (size_t)nv, hipMemcpyDeviceToHost, V.stream), "D2H mesh positions");
+  if (nq) check_hip(hipMemcpyAsync(m.quads.data(), d_quads, 16 * (size_t)nq, hipMemcpyDeviceToHost, V.stream), "D2H mesh quads");
+  check_hip(hipStreamSynchronize(V.stream), "mesh sync");
+  float a = 0, b = 0;
+  (void)hipEventElapsedTime(&a, M.e0, M.e1);
+  (void)hipEventElapsedTime(&b, M.e2, M.e3);
+  m.k15_s = (double)(a + b) * 1e-3;
+  return m;
+}
+
 VolumeResult run_volume(const VolumeInput& v, const VolumeParams& p, int device, bool want_masks) {
   VolumeRunner runner(device);
   return runner.run(v, p, want_masks);
@@ -1064,6 +1150,8 @@ struct VolOutcome {
   std::string measure_json;   // --measure-volume: the sidecar text (measure::volume_to_json)
   double measure_s = 0;       // --measure-volume: GPU time of K8
   int32_t view_files = 0;     // --volume-views: view files written (12, or 0)
+  int32_t mesh_files = 0;     // --volume-mesh: files written (the mesh and mesh.json: 2, or 0)
+  int64_t mesh_vertices = 0, mesh_quads = 0;
 };
 
 std::vector<uint8_t> encode(const std::vector<VolPatient>& pl) {
@@ -1101,6 +1189,13 @@ std::vector<VolPatient> decode(const std::vector<uint8_t>& b) {
 void write_file(const std::string& path, const std::vector<uint8_t>& jpg) {
   // complete JPEG file (header + scan + EOI): write_jpeg_file appends the EOI itself
   jpeg::write_jpeg_file(path, {}, jpg.data(), jpg.size() - 2);
+}
+
+// Any other file, as it is.
+void write_bytes(const std::string& path, const void* data, size_t n) {
+  std::ofstream f(path, std::ios::binary | std::ios::trunc);
+  f.write(static_cast<const char*>(data), (std::streamsize)n);
+  if (!f) throw std::runtime_error("Cannot write " + path);
 }
 
 // Golden 3D path (--cpu): per-plane preprocessing on a thread pool, 3D SRG + cube dilation, host
@@ -1165,7 +1260,8 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
                                                       IntensityStats* intensity = nullptr,
                                                       measure::Glcm* texture = nullptr,
                                                       std::vector<VolumeLesionDiameters>* diameters = nullptr,
-                                                      const ViewsAt* views_at = nullptr, VolumeViewsExport* views = nullptr) {
+                                                      const ViewsAt* views_at = nullptr, VolumeViewsExport* views = nullptr,
+                                                      VolumeMesh* mesh_out = nullptr, int mesh_placement = kMeshCorner) {
   const GoldenPlanes gp = golden_preprocess(v, vp);
   std::vector<Seed> seeds = vp.seeds;
   if (seeds.empty()) {
@@ -1190,6 +1286,8 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
     views->files = golden::volume_view_jpegs(views->views, (uint8_t)v.type, v.stored_bits, slope, intercept, v.spacing_x,
                                              v.spacing_y, v.spacing_z, rp);
   }
+  if (mesh_out)  // --volume-mesh: the golden mesh of the dilated mask (nm03/volume_mesh.h)
+    *mesh_out = golden::volume_mesh(dil.data(), v.w, v.h, v.d, v.spacing_x, v.spacing_y, v.spacing_z, mesh_placement);
   return golden_export(v, gp.vals, dil, rp);
 }
 
@@ -1362,6 +1460,8 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         const std::string ext = measure::volume_diameters_extent_error(v.w, v.h, v.d, vp.spacing_um);
         if (!ext.empty()) throw std::runtime_error("--measure-volume-diameters: " + ext);
       }
+      VolumeMesh vmesh;
+      const uint64_t mesh_cap = cfg.volume_mesh_max_mb << 20;
       VolumeViewsExport vx;
       if (cfg.volume_views) {  // an explicit point outside this patient's volume fails the patient, on both backends
         const std::string err = views::at_error(cfg.volume_views_at, v.w, v.h, v.d);
@@ -1369,7 +1469,12 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       }
       if (cfg.cpu) {
         files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions, &intensity, &texture, &diameters,
-                                    cfg.volume_views ? &cfg.volume_views_at : nullptr, &vx);
+                                    cfg.volume_views ? &cfg.volume_views_at : nullptr, &vx, cfg.volume_mesh ? &vmesh : nullptr,
+                                    cfg.volume_mesh_placement);
+        if (cfg.volume_mesh) {  // the check export_mesh makes between its two halves
+          const std::string err = mesh::size_error(vmesh.vertices(), vmesh.quad_count(), mesh_cap);
+          if (!err.empty()) throw std::runtime_error("--volume-mesh: " + err);
+        }
       } else {
         VolumeResult r = runner->run(v, vp, false);
         o.sweeps = r.sweeps;
@@ -1383,6 +1488,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         VolumeExportStats xs;
         files = runner->export_jpegs(v, vp, rp, &xs);
         if (cfg.volume_views) vx = runner->export_views(v, vp, rp, cfg.volume_views_at, false, &xs);
+        if (cfg.volume_mesh) vmesh = runner->export_mesh(v, vp, cfg.volume_mesh_placement, mesh_cap);
         o.export_s = xs.export_s;
         o.fallbacks = xs.jpeg_fallbacks;
       }
@@ -1396,6 +1502,15 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         f.write(text.data(), (std::streamsize)text.size());
         if (!f) throw std::runtime_error("Cannot write " + path);
         o.view_files = 2 * kVolumeViewCount;
+      }
+      if (cfg.volume_mesh) {  // the mesh file and its sidecar, one writer for both backends
+        const std::vector<uint8_t> bytes = mesh::file_bytes(vmesh, cfg.volume_mesh_format);
+        write_bytes(pp.out_dir + "/" + mesh::file_name(cfg.volume_mesh_format), bytes.data(), bytes.size());
+        const std::string text = mesh::to_json(vmesh, cfg.volume_mesh_format, bytes.size(), v.spacing_x, v.spacing_y, v.spacing_z);
+        write_bytes(pp.out_dir + "/" + mesh::kSidecarName, text.data(), text.size());
+        o.mesh_files = 2;
+        o.mesh_vertices = (int64_t)vmesh.vertices();
+        o.mesh_quads = (int64_t)vmesh.quad_count();
       }
       if (vp.measure) {  // the sidecar next to the planes; its text travels to rank 0 for the table
         o.measure_json = vp.measure_texture
@@ -1442,6 +1557,9 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
     w.str(o.measure_json);
     w.f64(o.measure_s);
     w.i32(o.view_files);
+    w.i32(o.mesh_files);
+    w.u64((uint64_t)o.mesh_vertices);
+    w.u64((uint64_t)o.mesh_quads);
   }
   auto all = comm.allgather_bytes(w.b);
   double tot = wall_now() - t_start;
@@ -1468,6 +1586,9 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       o.measure_json = r.str();
       o.measure_s = r.f64();
       o.view_files = r.i32();
+      o.mesh_files = r.i32();
+      o.mesh_vertices = (int64_t)r.u64();
+      o.mesh_quads = (int64_t)r.u64();
       outs.push_back(std::move(o));
     }
   }
@@ -1565,6 +1686,14 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       for (const auto& o : outs) vp_n += o.ok && o.view_files > 0, vf_n += o.ok ? o.view_files : 0;
       f << ", \"volume_views\": {\"patients\": " << vp_n << ", \"files\": " << vf_n << ", \"at_mode\": \""
         << views::at_mode_name(cfg.volume_views_at.mode) << "\"}";
+    }
+    if (cfg.volume_mesh) {
+      int64_t mp_n = 0, mv_n = 0, mq_n = 0;
+      for (const auto& o : outs)
+        if (o.ok && o.mesh_files > 0) ++mp_n, mv_n += o.mesh_vertices, mq_n += o.mesh_quads;
+      f << ", \"volume_mesh\": {\"patients\": " << mp_n << ", \"vertices\": " << mv_n << ", \"quads\": " << mq_n
+        << ", \"placement\": \"" << mesh::placement_name(cfg.volume_mesh_placement) << "\", \"format\": \""
+        << mesh::format_name(cfg.volume_mesh_format) << "\"}";
     }
     f << "}\n";
   }
