@@ -1,7 +1,7 @@
 """One DICOM series as a 3D volume on the MI355X: per-slice preprocessing, 6-connected 3D region
 growing and a 7×7×7 dilation (BASELINE config 5), checked against the golden 3D model.
 
-    python examples/volume_3d.py --series path/to/series_dir [--ball] [--measure] [--views DIR] [--mesh DIR]
+    python examples/volume_3d.py --series path/to/series_dir [--ball] [--measure] [--views DIR] [--mesh DIR] [--dilate-mm R]
 """
 import argparse
 import os
@@ -26,16 +26,31 @@ def main(argv=None):
     ap.add_argument("--mesh", metavar="DIR",
                     help="also write the surface of the dilated mask as a closed mesh in mm (K15): mesh.ply and mesh.json "
                          "into DIR")
+    ap.add_argument("--dilate-mm", type=float, metavar="R",
+                    help="dilate by a Euclidean margin of R mm in physical space (K16) instead of the 7x7x7 cube, and print "
+                         "the voxel counts of both and the thickness of the dilated volume")
     a = ap.parse_args(argv)
-    vp = nm.VolumePipeline(nm.PipelineConfig(se_shape=int(a.ball)), connectivity=6, dilation=7, measure=a.measure,
+    margin = a.dilate_mm is not None
+    vp = nm.VolumePipeline(nm.PipelineConfig(se_shape=int(a.ball)), connectivity=6, dilation=7, measure=a.measure or margin,
                            measure_lesions=int(a.measure), measure_diameters=a.measure, views=bool(a.views),
-                           mesh=bool(a.mesh))
+                           mesh=bool(a.mesh), dilate_mm=a.dilate_mm, measure_thickness=margin)
     res = vp.run_series(a.series)
     band = res["band"]
-    region, dil = vp.golden(band, vp.default_seeds(band))
+    g = nm.utils.series_geometry(a.series)
+    region, dil = vp.golden(band, vp.default_seeds(band), spacing=(g["spacing_x"], g["spacing_y"], g["spacing_z"]))
     same = np.array_equal(res["region"], region) and np.array_equal(res["dilated"], dil)
     print(f"volume {tuple(band.shape)}: region {int(res['region'].sum())} voxels, dilated "
           f"{int(res['dilated'].sum())} voxels, GPU == golden: {same}")
+    if margin:
+        cube = nm.native().golden_dilate3d(region, 7, False)
+        t = res["thickness"]
+        print(f"margin of {a.dilate_mm} mm at {g['spacing_x']} x {g['spacing_y']} x {g['spacing_z']} mm: "
+              f"{int(res['dilated'].sum())} voxels; the 7x7x7 cube: {int(cube.sum())} voxels")
+        if t["found"]:
+            print(f"thickness {t['thickness_mm']:.3f} mm (inscribed radius {t['inscribed_radius_mm']:.3f} mm at "
+                  f"{tuple(t['inscribed_at'])})")
+        else:
+            print("thickness: none (empty mask, or no background in the frame)")
     if a.measure:
         import json
         m = json.loads(res["measure_json"])

@@ -117,6 +117,13 @@ struct AppConfig {
   // --volume-mesh (3d): the surface of the dilated mask as <patient>/mesh.ply (or mesh.stl) and mesh.json
   // (nm03/volume_mesh.h). --volume-mesh-placement corner|nets, --volume-mesh-format ply|stl,
   // --volume-mesh-max-mb N: a mesh whose 12 · V + 16 · Q bytes exceed the cap fails the patient.
+  // --dilate-mm R (3d): the dilation is the Euclidean margin of R millimetres around the region in physical
+  // space (nm03/volume_distance.h) instead of the cube / ball of --dilation-size index steps; dilate_um =
+  // llround(R · 1000), −1 = off. --measure-volume-thickness (3d, implies --measure-volume): the radius of the
+  // largest inscribed ball of the dilated volume in the sidecar and volumes.csv.
+  int64_t dilate_um = -1;
+  double dilate_mm = 0;
+  bool measure_volume_thickness = false;
   bool volume_mesh = false;
   int volume_mesh_placement = kMeshCorner;
   int volume_mesh_format = kMeshPly;
@@ -208,12 +215,16 @@ struct VolumeTotals {
   int texture_levels = 0;  // --measure-texture: the table has the texture columns (0: not asked for)
   bool diameters = false;  // --measure-volume-diameters: lesions.csv has the diameter columns
   double diameter_3d_mm_max = 0;  // the largest diameter_3d_mm over the job's lesions
+  bool thickness = false;       // --measure-volume-thickness: the table has the thickness columns
+  double thickness_mm_max = 0;  // the largest thickness_mm over the job's patients
 };
 // `intensity` (--measure-intensity): the 13 intensity keys' columns after `mean`; a sidecar without them
 // (written earlier without the flag) leaves them empty.
 // `texture_levels` (--measure-texture; 0 = off): the 23 texture keys' columns after those, alike.
+// `thickness` (--measure-volume-thickness): inscribed_um2, inscribed_x / _y / _z, inscribed_radius_mm and
+// thickness_mm after all existing columns, alike.
 VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows,
-                               bool intensity = false, int texture_levels = 0);
+                               bool intensity = false, int texture_levels = 0, bool thickness = false);
 // --measure-volume-lesions: <out_root>/lesions.csv from the same sidecar texts, in plan order: a header,
 // then one row per reported lesion (patient, lesion = its 0-based rank, then the lesion object's fields
 // with first and bbox flattened); a failed patient has one row with its status name in `lesion` and

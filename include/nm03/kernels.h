@@ -10,6 +10,7 @@
 #include "nm03/gpu_types.h"
 #include "nm03/measure.h"
 #include "nm03/pixel_math.h"
+#include "nm03/volume_distance.h"
 #include "nm03/volume_mesh.h"
 #include "nm03/volume_views.h"
 
@@ -400,6 +401,41 @@ void launch_volume_mesh_emit(const uint64_t* dilated, const VolumeMeshLayout& L,
 // Loads K15's code object on the current device: only a VolumeRunner's first export_mesh and the Python op
 // load it.
 void preload_volume_mesh();
+
+// K16 (k16_volume_distance.hip): the exact Euclidean distance map of nm03/volume_distance.h from a bit volume
+// (d planes of h rows of ceil(w / 64) words), a wave per u64 word, lane = voxel. Three separable passes as
+// separate launches on `stream` — rows (u16 index distances), cols and planes (the outward search of
+// nm03/volume_distance_core.h on i64 values) — and the last pass ends in one of three ways:
+//   launch_volume_distance   stores the i64 map (w · h · d values, raster z, y, x; device memory); cap_um < 0 =
+//                            no cap, `to_background` measures to the zero voxels of the frame
+//   launch_volume_margin     stores the bits of { D_region ≤ radius_um² } into `dilated` (the layout of `region`,
+//                            every word written, bits past the width zero); no map is materialised
+//   launch_volume_thickness  keeps the best (value, smallest position) over the mask voxels in a slot per
+//                            workgroup, then ONE workgroup writes the 32-byte record to `out` (device, pinned or
+//                            host-mapped memory) with plain vector stores
+// No cooperative launch, grid barrier, flag, look-back, spin, atomic, host round trip or allocation. `work`:
+// volume_distance_work_bytes of device memory (2 + 8 bytes per voxel and 16 KiB of slots), no initialisation
+// needed. Each throws DeviceError before any launch for a null buffer, a spacing below 1, a negative radius and
+// the extent rule (measure::volume_distance_extent_error, naming the sum).
+constexpr int kVolumeDistanceWordsPerBlock = 4;
+struct VolumeDistanceLayout {
+  int w = 0, h = 0, d = 0, wpr = 0;
+  uint32_t words = 0, blocks = 0;                     // wpr · h · d < 2^31; workgroups of every launch
+  size_t off_rows = 0, off_cols = 0, off_slots = 0;  // byte offsets into `work`
+  size_t bytes = 0;
+};
+// Throws DeviceError for an empty volume, a width above 65535 and a volume of 2^31 words or more.
+VolumeDistanceLayout volume_distance_layout(int w, int h, int d);
+size_t volume_distance_work_bytes(int w, int h, int d);
+void launch_volume_distance(const uint64_t* bits, const VolumeDistanceLayout& L, const uint32_t um[3], bool to_background,
+                            int64_t cap_um, void* work, int64_t* out, hipStream_t stream);
+void launch_volume_margin(const uint64_t* region, const VolumeDistanceLayout& L, const uint32_t um[3], int64_t radius_um, void* work,
+                          uint64_t* dilated, hipStream_t stream);
+void launch_volume_thickness(const uint64_t* mask, const VolumeDistanceLayout& L, const uint32_t um[3], void* work,
+                             VolumeThickness* out, hipStream_t stream);
+// Loads K16's code object on the current device: only a VolumeRunner's first run that asks for a margin in
+// millimetres or the thickness, and the Python ops, load it.
+void preload_volume_distance();
 
 // K6: binary threshold lo ≤ x ≤ hi → u8 0/1 (in 16-byte aligned, out 4-byte aligned).
 void launch_threshold(const float* in, uint8_t* out, size_t n, float lo, float hi, hipStream_t stream);

@@ -12,6 +12,7 @@
 #include "nm03/comm.h"
 #include "nm03/engine.h"
 #include "nm03/measure.h"
+#include "nm03/volume_distance.h"
 #include "nm03/volume_mesh.h"
 #include "nm03/volume_views.h"
 
@@ -70,6 +71,8 @@ struct VolumeResult {
   IntensityStats intensity = {};
   // VolumeParams::measure_texture: the K12 record of the samples under the dilated volume.
   measure::Glcm texture;
+  // VolumeParams::measure_thickness: the K16 record of the dilated volume.
+  VolumeThickness thickness = {};
 };
 
 struct VolumeExportStats {
@@ -110,6 +113,13 @@ struct VolumeParams {
   // the thirteen forward directions (K12, nm03/measure.h TextureGlcm).
   bool measure_texture = false;
   int texture_levels = 32;
+  // ≥ 0: the dilation is the margin of `dilate_um` micrometres around the region (K16, nm03/volume_distance.h:
+  // { p : D_region(p) ≤ dilate_um² } at `spacing_um`) instead of the cube / ball of dilation_size index steps,
+  // inside kernels_s where the dilation is. −1 = off: nothing of K16 is touched.
+  int64_t dilate_um = -1;
+  // With measure: also the thickness of the dilated volume (K16, VolumeThickness) at `spacing_um`, after K12's
+  // launches, inside measure_s.
+  bool measure_thickness = false;
 };
 
 // Runs the 3D pipeline on `device`; copies masks back when `want_masks`. A VolumeRunner keeps
@@ -126,6 +136,9 @@ class VolumeRunner {
   // same holds for p.measure_lesions and K10, for p.measure_intensity and K11 (after K8's last launch)
   // and for p.measure_texture and K12 (after K11's), and for p.measure_diameters and K13 (directly after
   // K10's launches; its work buffer is sized by the N asked for and regrown when a later run asks for more).
+  // p.dilate_um ≥ 0 and p.measure_thickness share K16: its code object and its scratch (2 + 8 bytes per
+  // voxel) come with the first run that asks for either and are kept and rebuilt with the volume shape. All
+  // argument checks, the extent rule of nm03/volume_distance.h included, run before the run's first launch.
   VolumeResult run(const VolumeInput& v, const VolumeParams& p, bool want_masks);
   // After run() on the same volume: the 2·d exported JPEG files of the 3D cohort mode, in plane
   // order (original, processed), rendered and encoded on the GPU (K3/K4) from the volume still on
@@ -157,7 +170,8 @@ class VolumeRunner {
   // halo cube dilation with the other ranks of `comm` (collective), leaving the slab on the device:
   // export_jpegs(slab, ...) then exports its planes. Masks (when requested) are the slab's.
   // p.measure, p.measure_lesions, p.measure_diameters, p.measure_intensity or p.measure_texture throws std::invalid_argument: components that cross slabs would
-  // need a collective.
+  // need a collective. p.dilate_um ≥ 0 and p.measure_thickness throw it too: a margin across slabs needs a
+  // halo of its reach.
   VolumeResult run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p, bool want_masks,
                         struct SlabStats* stats = nullptr);
 

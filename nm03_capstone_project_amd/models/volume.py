@@ -33,7 +33,14 @@ millimetres (K15, nm03/volume_mesh.h) from the bit planes still on the device. `
 or "nets", `mesh_format` "ply" or "stl", `mesh_max_mb` the cap on 12 · V + 16 · Q bytes (a larger mesh raises
 RuntimeError). The result gains `mesh` (vertices float32 [V, 3], quads int32 [Q, 4], quads_x / _y / _z,
 voxels), `mesh_file` (the bytes of the CLI's mesh.ply / mesh.stl) and `mesh_json` (the text of mesh.json),
-both from the one native writer."""
+both from the one native writer.
+
+With `dilate_mm=R` (0 … 1000) the dilation is the Euclidean margin of R millimetres around the region in
+physical space (K16, nm03/volume_distance.h: { p : D_region(p) ≤ r² }, r = llround(R · 1000) µm, at the spacing
+quantised to integer micrometres) instead of the cube / ball of `dilation` index steps; everything downstream
+reads that mask. With `measure_thickness=True` (needs `measure`) K16 also reports the largest ball inscribed in
+the dilated volume: the result gains `thickness` (inscribed_um2, inscribed_at, found, inscribed_radius_mm,
+thickness_mm) and `measure_json` carries the thickness keys after the texture keys."""
 import numpy as np
 
 from .._native import native
@@ -50,7 +57,8 @@ class VolumePipeline:
     def __init__(self, config: PipelineConfig = None, connectivity: int = 6, dilation: int = 7, measure: bool = False,
                  measure_connectivity: int = 26, measure_lesions: int = 0, measure_intensity: bool = False, measure_texture: bool = False,
                  texture_levels: int = 32, measure_diameters: bool = False, views: bool = False, views_at="mask",
-                 mesh: bool = False, mesh_placement: str = "corner", mesh_format: str = "ply", mesh_max_mb: int = 512):
+                 mesh: bool = False, mesh_placement: str = "corner", mesh_format: str = "ply", mesh_max_mb: int = 512,
+                 dilate_mm=None, measure_thickness: bool = False):
         self.config = config or PipelineConfig()
         self.connectivity = connectivity
         self.dilation = dilation
@@ -93,6 +101,14 @@ class VolumePipeline:
             raise ValueError(f"mesh_max_mb must not be negative (got {mesh_max_mb})")
         if self.mesh and self.config.host_only:
             raise ValueError("the mesh is extracted on the GPU: not available with host_only")
+        self.dilate_mm = None if dilate_mm is None else float(dilate_mm)
+        if self.dilate_mm is not None and not 0.0 <= self.dilate_mm <= 1000.0:  # NaN fails both comparisons
+            raise ValueError(f"dilate_mm must be a finite number in [0, 1000] (got {dilate_mm})")
+        self.measure_thickness = bool(measure_thickness)
+        if self.measure_thickness and not self.measure:
+            raise ValueError("measure_thickness needs measure=True")
+        if (self.dilate_mm is not None or self.measure_thickness) and self.config.host_only:
+            raise ValueError("the distance map is computed on the GPU: not available with host_only")
         self._runners = {}  # device -> native VolumeRunner (buffers/stream reused across volumes)
 
     def default_seeds(self, volume):
@@ -114,8 +130,16 @@ class VolumePipeline:
             x, y, z = self.views_at
             if not (0 <= x < w and 0 <= y < h and 0 <= z < d):
                 raise ValueError(f"views_at: the point ({x}, {y}, {z}) lies outside the volume of {w} x {h} x {d}")
-        if not self.measure and meta is None:
+        if not self.measure and meta is None and self.dilate_mm is None:
             res = runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s)
+        elif self.dilate_mm is not None or self.measure_thickness:
+            res = runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s, measure=self.measure,
+                             measure_connectivity=self.measure_connectivity, spacing=[float(v) for v in spacing],
+                             spacing_z_source=str(spacing_z_source), measure_lesions=self.measure_lesions,
+                             measure_intensity=self.measure_intensity, measure_texture=self.measure_texture,
+                             texture_levels=self.texture_levels, measure_diameters=self.measure_diameters,
+                             dilate_um=-1 if self.dilate_mm is None else native().dilate_mm_to_um(self.dilate_mm),
+                             measure_thickness=self.measure_thickness, **_meta_args(meta))
         else:
             res = runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s, measure=self.measure,
                              measure_connectivity=self.measure_connectivity, spacing=[float(v) for v in spacing],
@@ -147,7 +171,7 @@ class VolumePipeline:
         (utils.series_geometry) and the first slice's storage format go with it."""
         from ..utils.dicom import read_series, series_geometry
         vol, slices = read_series(series_dir)
-        if not self.measure and not self.views and not self.mesh:
+        if not self.measure and not self.views and not self.mesh and self.dilate_mm is None:
             return self.run(vol, seeds=seeds, device=device)
         g = series_geometry(series_dir)
         return self.run(vol, seeds=seeds, device=device, spacing=(g["spacing_x"], g["spacing_y"], g["spacing_z"]),
@@ -168,9 +192,13 @@ class VolumePipeline:
                                 dilation=self.dilation, seeds=seeds, band=band, backend=backend, gather=gather,
                                 device=dev, runner=runner)
 
-    def golden(self, band, seeds):
+    def golden(self, band, seeds, spacing=(1.0, 1.0, 1.0)):
+        """`spacing` only enters with dilate_mm: the margin is taken at the spacing quantised to micrometres."""
         n = native()
         region = n.golden_region_grow3d(band, list(seeds), self.connectivity)
+        if self.dilate_mm is not None:
+            um = n.volume_spacing_um(float(np.float32(spacing[0])), float(np.float32(spacing[1])), float(spacing[2]))
+            return region, n.golden_dilate3d_mm(region, list(um), n.dilate_mm_to_um(self.dilate_mm))
         return region, n.golden_dilate3d(region, self.dilation, self.config.se_shape == 1)
 
     def golden_measure(self, dilated, region, raw, spacing=(1.0, 1.0, 1.0), spacing_z_source="default", meta=None):
@@ -181,7 +209,18 @@ class VolumePipeline:
         measure_intensity the text carries the intensity keys and the tuple's last member is the intensity
         dict (`run`'s `intensity`). With measure_texture the text carries the texture keys too and the
         texture dict (`run`'s `texture`) comes last of all. With measure_diameters the text carries the diameter
-        keys as well and the list of diameter dicts (`run`'s `diameters`) is a further last member."""
+        keys as well and the list of diameter dicts (`run`'s `diameters`) is a further last member. With
+        measure_thickness the text carries the thickness keys and the thickness dict (`run`'s `thickness`) is a
+        further last member after all of those."""
+        out = self._golden_measure_diameters(dilated, region, raw, spacing, spacing_z_source, meta)
+        if not self.measure_thickness:
+            return out
+        n = native()
+        um = n.volume_spacing_um(float(np.float32(spacing[0])), float(np.float32(spacing[1])), float(spacing[2]))
+        th = n.golden_volume_thickness(np.ascontiguousarray(dilated, dtype=np.uint8), list(um))
+        return (out[0], n.volume_insert_thickness_keys(out[1], th, list(um))) + tuple(out[2:]) + (th,)
+
+    def _golden_measure_diameters(self, dilated, region, raw, spacing, spacing_z_source, meta):
         out = self._golden_measure(dilated, region, raw, spacing, spacing_z_source, meta)
         if not self.measure_diameters:
             return out

@@ -615,3 +615,67 @@ def volume_mesh(mask, spacing=(1, 1, 1), placement="corner", scan_block=None, ma
         raise ValueError("spacing must be (sx, sy, sz)")
     dw = pack_bits(mask.bool()).contiguous()
     return native().k_volume_mesh(dw.data_ptr(), w, h, d, spacing, placement, int(scan_block or 0), int(max_bytes), _stream())
+
+
+def _distance_args(mask, spacing_um, name="mask"):
+    if not hasattr(mask, "is_cuda") or not mask.is_cuda:
+        raise ValueError(f"{name} must be a CUDA (HIP) tensor")
+    if mask.dim() != 3:
+        raise ValueError(f"{name} must be [D, H, W]")
+    d, h, w = (int(v) for v in mask.shape)
+    if d < 1 or h < 1 or w < 1:
+        raise ValueError("empty volume")
+    if w > 65535:
+        raise ValueError("a row holds at most 65535 voxels")
+    um = [int(v) for v in spacing_um]
+    if len(um) != 3 or min(um) < 1 or max(um) > 2 ** 32 - 1:
+        raise ValueError("spacing_um must be three integers of at least 1")
+    err = native().volume_distance_extent_error(w, h, d, um)
+    if err:
+        raise ValueError(err)
+    return d, h, w, um
+
+
+def volume_distance(mask, spacing_um=(1000, 1000, 1000), to="foreground", cap_um=None):
+    """The exact squared Euclidean distance map of a volume mask in physical space (K16, nm03/volume_distance.h)
+    → int64 CUDA tensor [D, H, W]: at every voxel the smallest ((dx·ux)² + (dy·uy)² + (dz·uz)²) to a voxel of S,
+    centre to centre, in squared micrometres. S is the set voxels of `mask` (`to="foreground"`) or its zero
+    voxels inside the frame (`to="background"`); outside the frame is neither. The map is 0 exactly on S and
+    native().NO_DISTANCE (2⁶³ − 1) everywhere when S is empty; with `cap_um` every value above cap_um² is
+    NO_DISTANCE too.
+
+    `mask` is a bool CUDA tensor [D, H, W]; `spacing_um` is (ux, uy, uz) in integer micrometres. Three launches
+    (rows, columns, planes). A volume with ((w − 1)·ux)² + ((h − 1)·uy)² + ((d − 1)·uz)² ≥ 2⁶² raises."""
+    if to not in ("foreground", "background"):
+        raise ValueError("to must be 'foreground' or 'background'")
+    d, h, w, um = _distance_args(mask, spacing_um)
+    if cap_um is not None and int(cap_um) < 0:
+        raise ValueError("cap_um must not be negative")
+    bits = pack_bits(mask.bool()).contiguous()
+    out = torch.empty((d, h, w), dtype=torch.int64, device=bits.device)
+    native().k_volume_distance(bits.data_ptr(), w, h, d, um, "map", to == "background", -1 if cap_um is None else int(cap_um),
+                               out.data_ptr(), _stream())
+    return out
+
+
+def dilate_volume_mm(mask, spacing_um=(1000, 1000, 1000), radius_um=0):
+    """The margin of `radius_um` micrometres around a volume mask (K16): { p : D_mask(p) ≤ radius_um² } → bool
+    CUDA tensor [D, H, W]. The ball is Euclidean in physical space; radius 0 gives the mask itself. The last
+    pass stores the bits by wave ballot: no distance map is materialised."""
+    d, h, w, um = _distance_args(mask, spacing_um)
+    if int(radius_um) < 0:
+        raise ValueError("radius_um must not be negative")
+    bits = pack_bits(mask.bool()).contiguous()
+    out = torch.empty_like(bits)
+    native().k_volume_distance(bits.data_ptr(), w, h, d, um, "margin", False, int(radius_um), out.data_ptr(), _stream())
+    return unpack_bits(out, w)
+
+
+def volume_thickness(mask, spacing_um=(1000, 1000, 1000)):
+    """The thickness of a volume mask (K16) → dict: inscribed_um2 (the largest squared distance of a mask voxel to
+    the background of the frame), inscribed_at [x, y, z] (the voxel that attains it, the smallest raster
+    (z, y, x) on a tie), found, inscribed_radius_mm = √inscribed_um2 / 1000 and thickness_mm = 2 · radius. An
+    empty mask or a frame without a background voxel gives 0, [−1, −1, −1], found False and None."""
+    d, h, w, um = _distance_args(mask, spacing_um)
+    bits = pack_bits(mask.bool()).contiguous()
+    return native().k_volume_distance(bits.data_ptr(), w, h, d, um, "thickness", True, -1, 0, _stream())

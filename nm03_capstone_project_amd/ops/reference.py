@@ -767,3 +767,82 @@ def volume_mesh(mask, spacing=(1, 1, 1), placement="corner"):
     quads = np.concatenate(quads, axis=0).astype(np.int32).reshape(-1, 4)
     return {"width": w, "height": h, "depth": d, "placement": placement, "vertices": verts, "quads": quads,
             "quads_x": counts[0], "quads_y": counts[1], "quads_z": counts[2], "voxels": int(m.sum())}
+
+
+NO_DISTANCE = 2 ** 63 - 1
+
+
+def _distance_set(mask, to):
+    import numpy as np
+    m = np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask).astype(bool)
+    if m.ndim != 3:
+        raise ValueError("mask must be [D, H, W]")
+    if to not in ("foreground", "background"):
+        raise ValueError("to must be 'foreground' or 'background'")
+    return m if to == "foreground" else ~m
+
+
+def _apply_cap(dist, cap_um):
+    if cap_um is not None:
+        if int(cap_um) < 0:
+            raise ValueError("cap_um must not be negative")
+        dist[dist > int(cap_um) ** 2] = NO_DISTANCE
+    return dist
+
+
+def volume_distance(mask, spacing_um=(1000, 1000, 1000), to="foreground", cap_um=None):
+    """Reference of ops.volume_distance / native.golden_volume_distance (nm03/volume_distance.h) on a [D, H, W]
+    mask (array or CPU tensor) → int64 array [D, H, W]. SciPy's distance_transform_edt names a nearest voxel of S
+    for every voxel (return_indices, sampling = (uz, uy, ux)); the squared distance is then RECOMPUTED IN INT64
+    from those indices, so no float of SciPy's is ever compared. Outside the frame is neither S nor its
+    complement, which is SciPy's own convention."""
+    import numpy as np
+    from scipy import ndimage
+    s = _distance_set(mask, to)
+    ux, uy, uz = (int(v) for v in spacing_um)
+    if not s.any():
+        return np.full(s.shape, NO_DISTANCE, dtype=np.int64)
+    idx = ndimage.distance_transform_edt(~s, sampling=(float(uz), float(uy), float(ux)), return_distances=False,
+                                         return_indices=True)
+    zz, yy, xx = np.indices(s.shape)
+    dz = (zz - idx[0]).astype(np.int64) * uz
+    dy = (yy - idx[1]).astype(np.int64) * uy
+    dx = (xx - idx[2]).astype(np.int64) * ux
+    return _apply_cap(dx * dx + dy * dy + dz * dz, cap_um)
+
+
+def volume_distance_brute(mask, spacing_um=(1000, 1000, 1000), to="foreground", cap_um=None):
+    """The same map by all pairs in int64 (NumPy broadcasting): for the tiny cases."""
+    import numpy as np
+    s = _distance_set(mask, to)
+    ux, uy, uz = (int(v) for v in spacing_um)
+    if not s.any():
+        return np.full(s.shape, NO_DISTANCE, dtype=np.int64)
+    qz, qy, qx = (a.astype(np.int64) for a in np.nonzero(s))
+    zz, yy, xx = (a.reshape(-1, 1).astype(np.int64) for a in np.indices(s.shape))
+    d2 = ((xx - qx) * ux) ** 2 + ((yy - qy) * uy) ** 2 + ((zz - qz) * uz) ** 2
+    return _apply_cap(d2.min(axis=1).reshape(s.shape), cap_um)
+
+
+def dilate_volume_mm(mask, spacing_um=(1000, 1000, 1000), radius_um=0):
+    """Reference of ops.dilate_volume_mm: the threshold D_mask ≤ radius_um² of the reference map → bool array."""
+    if int(radius_um) < 0:
+        raise ValueError("radius_um must not be negative")
+    return volume_distance(mask, spacing_um, "foreground") <= int(radius_um) ** 2
+
+
+def volume_thickness(mask, spacing_um=(1000, 1000, 1000)):
+    """Reference of ops.volume_thickness: the largest background distance over the mask voxels, the first voxel
+    in raster (z, y, x) order that attains it, and the two derived lengths."""
+    import numpy as np
+    m = _distance_set(mask, "foreground")
+    dist = volume_distance(m, spacing_um, "background")
+    cand = m & (dist != NO_DISTANCE)
+    if not cand.any():
+        return {"inscribed_um2": 0, "inscribed_at": [-1, -1, -1], "found": False, "inscribed_radius_mm": None,
+                "thickness_mm": None}
+    v = np.where(cand, dist, -1)
+    best = int(v.max())
+    z, y, x = (int(a) for a in np.unravel_index(int(np.argmax(v)), v.shape))  # argmax: the first in raster order
+    r = math.sqrt(float(best)) / 1000.0
+    return {"inscribed_um2": best, "inscribed_at": [x, y, z], "found": True, "inscribed_radius_mm": r, "thickness_mm": 2.0 * r}

@@ -129,13 +129,14 @@ def read_measurements(out_dir):
 def read_volume_measurements(out_dir):
     """Rows of <out_dir>/volumes.csv (written by the 3D CLI with --measure-volume) as dicts keyed by
     the header: one per patient in plan order (`status` "ok", or "failed" and then empty fields). With
-    --measure-intensity the rows also have the 13 intensity columns, with --measure-texture the 23 glcm_ ones.
+    --measure-intensity the rows also have the 13 intensity columns, with --measure-texture the 23 glcm_ ones, with
+    --measure-volume-thickness inscribed_um2, inscribed_x / _y / _z (int), inscribed_radius_mm and thickness_mm (float).
     Integer columns come back as int, spacings and the derived ones as float, empty fields as None."""
     import csv
     import os
     floats = {"spacing_x", "spacing_y", "spacing_z", "volume_mm3", "volume_ml", "surface_mm2", "centroid_x",
               "centroid_y", "centroid_z", "centroid_x_mm", "centroid_y_mm", "centroid_z_mm", "mean", "std", "p10", "p25",
-              "median", "p75", "p90", "iqr"} | _GLCM_FLOATS
+              "median", "p75", "p90", "iqr", "inscribed_radius_mm", "thickness_mm"} | _GLCM_FLOATS
     text = {"patient", "status", "spacing_z_source"}
     rows = []
     with open(os.path.join(out_dir, "volumes.csv"), newline="") as f:

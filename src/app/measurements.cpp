@@ -147,6 +147,23 @@ std::string without_texture(const std::string& text, std::vector<std::string>* t
   return text.substr(0, at) + "}\n";
 }
 
+// --measure-volume-thickness: the columns after all of those. The sidecar's thickness keys (the last global
+// keys) hold nine values: thickness_spacing_um's three, which have no column, then these six.
+const char* const kThicknessColumns[] = {"inscribed_um2", "inscribed_x", "inscribed_y", "inscribed_z", "inscribed_radius_mm",
+                                         "thickness_mm"};
+constexpr size_t kNumThicknessColumns = sizeof(kThicknessColumns) / sizeof(kThicknessColumns[0]);
+constexpr size_t kNumThicknessValues = kNumThicknessColumns + 3;
+const char* const kThicknessKey = ",\"thickness_spacing_um\":";
+
+// Likewise the thickness keys: the last keys of a sidecar whose lesion keys the caller has cut.
+std::string without_thickness(const std::string& text, std::vector<std::string>* thickness) {
+  const size_t at = text.find(kThicknessKey);
+  if (at == std::string::npos) return text;
+  std::vector<std::string> v;
+  if (thickness && parse_sidecar("{" + text.substr(at + 1), v, kNumThicknessValues)) *thickness = v;
+  return text.substr(0, at) + "}\n";
+}
+
 // The texture columns of one row: the values, or empty fields.
 void put_texture(std::ostringstream& o, bool have, const std::vector<std::string>& tv) {
   for (size_t c = 0; c < kNumTextureColumns; ++c) o << "," << (have && tv.size() == kNumTextureColumns ? tv[c] : std::string());
@@ -160,10 +177,11 @@ void put_texture_totals(std::string& s, int levels) {
 }  // namespace
 
 VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<VolumePatientRow>& rows, bool intensity,
-                               int texture_levels) {
+                               int texture_levels, bool thickness) {
   VolumeTotals tot;
   tot.intensity = intensity;
   tot.texture_levels = texture_levels;
+  tot.thickness = thickness;
   std::ostringstream o;
   o << "patient,status";
   for (const char* c : kVolumeColumns) o << "," << c;
@@ -171,11 +189,14 @@ VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<Vo
     for (const char* c : kIntensityColumns) o << "," << c;
   if (texture_levels)
     for (const char* c : kTextureColumns) o << "," << c;
+  if (thickness)
+    for (const char* c : kThicknessColumns) o << "," << c;
   o << "\n";
   for (const auto& r : rows) {
-    std::vector<std::string> v, iv, tv;
+    std::vector<std::string> v, iv, tv, hv;
     const bool have =
-        r.ok && parse_sidecar(without_intensity(without_texture(without_lesions(r.sidecar), &tv), &iv), v, kNumVolumeColumns);
+        r.ok && parse_sidecar(without_intensity(without_texture(without_thickness(without_lesions(r.sidecar), &hv), &tv), &iv), v,
+                              kNumVolumeColumns);
     o << r.id << "," << (r.ok ? (have ? "ok" : "no_sidecar") : "failed");
     for (size_t c = 0; c < kNumVolumeColumns; ++c) {
       std::string x = have ? v[c] : std::string();
@@ -185,6 +206,11 @@ VolumeTotals write_volumes_csv(const std::string& out_root, const std::vector<Vo
     if (intensity)
       for (size_t c = 0; c < kNumIntensityColumns; ++c) o << "," << (have && iv.size() == kNumIntensityColumns ? iv[c] : std::string());
     if (texture_levels) put_texture(o, have, tv);
+    if (thickness) {
+      const bool hh = have && hv.size() == kNumThicknessValues;
+      for (size_t c = 0; c < kNumThicknessColumns; ++c) o << "," << (hh ? hv[3 + c] : std::string());
+      if (hh) tot.thickness_mm_max = std::max(tot.thickness_mm_max, std::strtod(hv[3 + 5].c_str(), nullptr));
+    }
     o << "\n";
     if (!have) continue;
     ++tot.volumes;
@@ -210,6 +236,10 @@ std::string volume_totals_json(const VolumeTotals& t) {
   std::string s = buf;
   if (t.intensity) s.insert(s.size() - 1, ", \"intensity\": true");
   put_texture_totals(s, t.texture_levels);
+  if (t.thickness) {
+    std::snprintf(buf, sizeof buf, ", \"thickness\": true, \"thickness_mm_max\": %.9g", t.thickness_mm_max);
+    s.insert(s.size() - 1, buf);
+  }
   if (t.diameters) {
     std::snprintf(buf, sizeof buf, ", \"diameters\": true, \"diameter_3d_mm_max\": %.9g", t.diameter_3d_mm_max);
     s.insert(s.size() - 1, buf);

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -96,6 +97,12 @@ void usage(const std::string& which) {
             << "                         crossing edges' midpoints (naive surface nets); the faces are the same\n"
             << "  --volume-mesh-format ply|stl  binary PLY (default) or binary STL (mesh.stl)\n"
             << "  --volume-mesh-max-mb N a mesh above N MiB (12 bytes per vertex, 16 per quad; default 512) fails the patient\n"
+            << "  --dilate-mm R          3d: dilate by a Euclidean margin of R millimetres in physical space (0..1000; the\n"
+            << "                         voxel spacing is consulted) instead of the cube / ball of --dilation-size index\n"
+            << "                         steps (needs --mode 3d; not with --split-volume or --dilation-size)\n"
+            << "  --measure-volume-thickness  3d: --measure-volume plus the radius of the largest ball inscribed in the\n"
+            << "                         dilated volume and the thickness, twice that: keys in the sidecar, columns in\n"
+            << "                         <out>/volumes.csv (not with --split-volume)\n"
             << "  --mode 2d|3d           3d: whole series as a volume (SRG 6-conn + cube dilation)\n"
             << "  --split-volume         3d: each volume split into z-slabs over all ranks (halo exchange)\n"
             << "  --input FILE           test_pipeline: slice to process\n"
@@ -330,6 +337,18 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
       }
       volume_views_at_given = true;
     }
+    else if (a == "--dilate-mm") {
+      const std::string v = val();
+      char* end = nullptr;
+      const double mm = std::strtod(v.c_str(), &end);
+      if (v.empty() || end != v.c_str() + v.size() || !std::isfinite(mm) || mm < 0.0 || mm > kMaxDilateMm) {
+        std::cerr << "--dilate-mm needs a finite number of millimetres in [0, 1000] (got '" << v << "')" << std::endl;
+        std::exit(2);
+      }
+      c.dilate_mm = mm;
+      c.dilate_um = measure::dilate_mm_to_um(mm);
+    }
+    else if (a == "--measure-volume-thickness") c.measure_volume_thickness = true;
     else if (a == "--volume-mesh") c.volume_mesh = true;
     else if (a == "--volume-mesh-placement") {
       const std::string v = val();
@@ -425,6 +444,29 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
     std::cerr << "--measure is not available with --mode 3d (use --measure-volume)" << std::endl;
     std::exit(2);
   }
+  if (c.dilate_um >= 0 && c.mode != "3d") {
+    std::cerr << "--dilate-mm needs --mode 3d (the 2D dilation is --dilation-size, in index steps)" << std::endl;
+    std::exit(2);
+  }
+  if (c.dilate_um >= 0 && c.split_volume) {
+    std::cerr << "--dilate-mm is not available with --split-volume: a margin across the slabs needs a halo of its reach "
+                 "(drop --split-volume to get the margin, or --dilate-mm to split the volume)"
+              << std::endl;
+    std::exit(2);
+  }
+  if (c.dilate_um >= 0 && c.dilation_set) {
+    std::cerr << "--dilate-mm and --dilation-size both set the dilation: give one of them" << std::endl;
+    std::exit(2);
+  }
+  if (c.measure_volume_thickness && c.mode != "3d") {
+    std::cerr << "--measure-volume-thickness needs --mode 3d" << std::endl;
+    std::exit(2);
+  }
+  if (c.measure_volume_thickness && c.split_volume) {
+    std::cerr << "--measure-volume-thickness is not available with --split-volume" << std::endl;
+    std::exit(2);
+  }
+  if (c.measure_volume_thickness) c.measure_volume = true;  // implies --measure-volume
   if (c.measure_volume_diameters && c.mode != "3d") {
     std::cerr << "--measure-volume-diameters needs --mode 3d (per-slice diameters: --measure-diameters)" << std::endl;
     std::exit(2);

@@ -49,6 +49,9 @@ int main(int argc, char** argv) {
   bool measure_intensity = false;  // cohort with --measure / volume with --measure-volume: also K11 (percentiles, sum of squares)
   bool volume_views = false;       // volume: also K14 and the render + encode of the twelve view files per run
   bool volume_mesh = false;        // volume: also K15 (the surface mesh of the dilated volume) per run
+  int64_t dilate_um = -1;          // volume: the margin of --dilate-mm R (K16) in place of the cube / ball, inside kernels_s
+  double dilate_mm = 0;
+  bool measure_volume_thickness = false;  // volume with --measure-volume: also K16's thickness, inside measure_s
   int mesh_placement = nm03::kMeshCorner;
   uint64_t mesh_max_mb = nm03::mesh::kDefaultMaxMb;
   for (int i = 1; i < argc; ++i) {
@@ -91,6 +94,15 @@ int main(int argc, char** argv) {
     }
     else if (a == "--measure-volume-diameters") measure_volume_diameters = true;
     else if (a == "--volume-diameters-brute-force") diameters_brute_force = true;
+    else if (a == "--dilate-mm") {
+      dilate_mm = std::atof(v().c_str());
+      if (!(dilate_mm >= 0.0 && dilate_mm <= nm03::kMaxDilateMm)) {
+        std::cerr << "--dilate-mm must be in [0, 1000]" << std::endl;
+        return 2;
+      }
+      dilate_um = nm03::measure::dilate_mm_to_um(dilate_mm);
+    }
+    else if (a == "--measure-volume-thickness") measure_volume_thickness = true;
     else if (a == "--volume-views") volume_views = true;
     else if (a == "--volume-mesh") volume_mesh = true;
     else if (a == "--volume-mesh-placement") {
@@ -112,6 +124,11 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (diameters_brute_force) measure_volume_diameters = true;
+  if ((dilate_um >= 0 || measure_volume_thickness) && (config != "volume" || ec.host_only)) {
+    std::cerr << "--dilate-mm and --measure-volume-thickness need --config volume and the GPU (not --host-only)" << std::endl;
+    return 2;
+  }
+  if (measure_volume_thickness) measure_volume = true;
   if (volume_views && (config != "volume" || ec.host_only)) {
     std::cerr << "--volume-views needs --config volume and the GPU (not --host-only)" << std::endl;
     return 2;
@@ -221,6 +238,10 @@ int main(int argc, char** argv) {
       vp.measure_intensity = measure_intensity;
       vp.measure_texture = measure_texture;
       vp.texture_levels = texture_levels;
+      vp.dilate_um = dilate_um;
+      vp.measure_thickness = measure_volume_thickness;
+      if (dilate_um >= 0 || measure_volume_thickness)
+        nm03::measure::volume_spacing_um((double)v.spacing_x, (double)v.spacing_y, v.spacing_z, vp.spacing_um);
       nm03::VolumeRunner runner(ec.device);
       for (int w = 0; w < warmup; ++w) runner.run(v, vp, false);
       double ks = 0, ms = 0;
@@ -230,6 +251,7 @@ int main(int argc, char** argv) {
       uint64_t lesion0_vox = 0, lesion0_major_um2 = 0;
       nm03::IntensityStats vi = {};
       uint64_t glcm_pairs = 0;
+      nm03::VolumeThickness vt = {};
       const double t0 = now_s();
       for (int k = 0; k < steps; ++k) {
         auto r = runner.run(v, vp, false);
@@ -239,6 +261,7 @@ int main(int argc, char** argv) {
         vm = r.measure;
         vi = r.intensity;
         glcm_pairs = r.texture.head.pairs;
+        vt = r.thickness;
         lesions = r.lesions.size();
         lesion0_vox = lesions ? r.lesions[0].voxels : 0;
         lesion0_major_um2 = r.diameters.empty() ? 0 : r.diameters[0].major_um2;
@@ -307,6 +330,10 @@ int main(int argc, char** argv) {
       if (measure_intensity) std::cout << ", \"intensity\": true, \"raw_p50\": " << vi.pct[2];
       if (measure_texture)
         std::cout << ", \"texture\": true, \"texture_levels\": " << texture_levels << ", \"glcm_pairs\": " << glcm_pairs;
+      if (dilate_um >= 0) std::cout << ", \"dilate_mm\": " << dilate_mm << ", \"dilate_um\": " << dilate_um;
+      if (measure_volume_thickness)
+        std::cout << ", \"thickness\": true, \"inscribed_um2\": " << vt.inscribed_um2
+                  << ", \"thickness_mm\": " << 2.0 * nm03::measure::inscribed_radius_mm(vt);
       std::cout << "}" << std::endl;
     } else if (config == "volume-cpu") {
       if (pids.empty()) throw std::runtime_error("no patients");

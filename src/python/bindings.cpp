@@ -497,6 +497,41 @@ void spacing_um_from(const std::vector<int64_t>& v, uint32_t um[3]) {
   }
 }
 
+py::dict volume_thickness_dict(const VolumeThickness& t) {
+  py::dict d;
+  d["inscribed_um2"] = t.inscribed_um2;
+  py::list at;
+  for (int k = 0; k < 3; ++k) at.append(t.at[k]);
+  d["inscribed_at"] = at;
+  d["found"] = t.found != 0;
+  if (t.found) {
+    const double r = measure::inscribed_radius_mm(t);
+    d["inscribed_radius_mm"] = r;
+    d["thickness_mm"] = 2.0 * r;
+  } else {
+    d["inscribed_radius_mm"] = py::none();
+    d["thickness_mm"] = py::none();
+  }
+  return d;
+}
+
+VolumeThickness volume_thickness_from(const py::dict& d) {
+  VolumeThickness t{};
+  t.inscribed_um2 = d["inscribed_um2"].cast<uint64_t>();
+  const std::vector<int> at = d["inscribed_at"].cast<std::vector<int>>();
+  if (at.size() != 3) throw std::invalid_argument("inscribed_at must be [x, y, z]");
+  for (int k = 0; k < 3; ++k) t.at[k] = at[(size_t)k];
+  t.found = d["found"].cast<bool>() ? 1 : 0;
+  return t;
+}
+
+// (ux, uy, uz), the mask's shape and the cap of the distance bindings, checked as the ops check them.
+void distance_args(const py::array& mask, const std::vector<int64_t>& spacing_um, uint32_t um[3]) {
+  if (mask.ndim() != 3) throw std::invalid_argument("mask must be [D, H, W]");
+  if (mask.shape(0) < 1 || mask.shape(1) < 1 || mask.shape(2) < 1) throw std::invalid_argument("empty volume");
+  spacing_um_from(spacing_um, um);
+}
+
 void check_max_lesions(int n) {
   if (n < 1 || n > kMaxVolumeLesions)
     throw std::invalid_argument("max_lesions must be 1.." + std::to_string(kMaxVolumeLesions));
@@ -528,6 +563,8 @@ struct VolumeMeta {
   bool measure_intensity = false;
   bool measure_texture = false;
   int texture_levels = 32;
+  int64_t dilate_um = -1;  // ≥ 0: the margin in micrometres in place of the cube / ball
+  bool measure_thickness = false;
 };
 
 void apply_meta(const VolumeMeta& mt, VolumeInput& v) {
@@ -717,6 +754,10 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
     vp.measure_intensity = meta->measure_intensity;
     vp.measure_texture = meta->measure_texture;
     vp.texture_levels = meta->texture_levels;
+    vp.dilate_um = meta->dilate_um;
+    vp.measure_thickness = meta->measure_thickness;
+    if (vp.dilate_um >= 0 || vp.measure_thickness)
+      measure::volume_spacing_um((double)v.spacing_x, (double)v.spacing_y, v.spacing_z, vp.spacing_um);
   }
   VolumeResult r;
   {
@@ -747,6 +788,10 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
       d["measure_json"] = golden::measure_volume_json(r.measure, vp.measure_intensity ? &r.intensity : nullptr,
                                                       vp.measure_lesions ? &r.lesions : nullptr, vp.measure_lesions, r.texture, v,
                                                       vp.pipe.apply_rescale, vp.measure_connectivity);
+    }
+    if (vp.measure_thickness) {
+      d["thickness"] = volume_thickness_dict(r.thickness);
+      d["measure_json"] = measure::insert_thickness_keys(d["measure_json"].cast<std::string>(), r.thickness, vp.spacing_um);
     }
     if (vp.measure_diameters) {
       d["diameters"] = volume_diameters_list(r.diameters.data(), r.diameters.size());
@@ -1395,10 +1440,21 @@ PYBIND11_MODULE(_nm03, m) {
       "volume_measure_to_json",
       [](const py::dict& rec, int w, int h, int d, double sx, double sy, double sz, const std::string& source, float slope,
          float intercept, bool apply_rescale, int connectivity, const py::object& lesions, int lesions_max,
-         const py::object& intensity, const py::object& texture, const py::object& diameters, const py::object& spacing_um) {
+         const py::object& intensity, const py::object& texture, const py::object& diameters, const py::object& spacing_um,
+         const py::object& thickness) {
+        // `thickness` (a thickness dict): the thickness keys after the global keys, at `spacing_um` or the
+        // quantised spacings.
+        auto with_thickness = [&](std::string text) {
+          if (thickness.is_none()) return text;
+          uint32_t um[3];
+          if (spacing_um.is_none()) measure::volume_spacing_um((double)(float)sx, (double)(float)sy, sz, um);
+          else spacing_um_from(spacing_um.cast<std::vector<int64_t>>(), um);
+          return measure::insert_thickness_keys(std::move(text), volume_thickness_from(thickness.cast<py::dict>()), um);
+        };
         // `diameters` (a list of diameter dicts, one per lesion): the text below with the diameter keys, at
         // `spacing_um` (ux, uy, uz) or, when that is None, the quantised spacings.
         auto with_diameters = [&](std::string text) {
+          text = with_thickness(std::move(text));
           if (diameters.is_none()) return text;
           if (lesions.is_none()) throw std::invalid_argument("diameters need lesions");
           std::vector<VolumeLesionDiameters> ds;
@@ -1449,7 +1505,8 @@ PYBIND11_MODULE(_nm03, m) {
       py::arg("spacing_z") = 1.0, py::arg("spacing_z_source") = "default", py::arg("slope") = 1.f,
       py::arg("intercept") = 0.f, py::arg("apply_rescale") = true, py::arg("connectivity") = 26,
       py::arg("lesions") = py::none(), py::arg("lesions_max") = 0, py::arg("intensity") = py::none(),
-      py::arg("texture") = py::none(), py::arg("diameters") = py::none(), py::arg("spacing_um") = py::none());
+      py::arg("texture") = py::none(), py::arg("diameters") = py::none(), py::arg("spacing_um") = py::none(),
+      py::arg("thickness") = py::none());
   // The N largest components of a volume mask (nm03/measure.h VolumeLesion) by the golden model (flood
   // fill per component) → list of dicts of the records' integers, largest first.
   m.def(
@@ -1898,9 +1955,11 @@ PYBIND11_MODULE(_nm03, m) {
              const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_connectivity,
              const std::vector<double>& spacing, const std::string& spacing_z_source, const std::string& type,
              int stored_bits, float slope, float intercept, int measure_lesions, bool measure_intensity, bool measure_texture,
-             int texture_levels, bool measure_diameters) {
+             int texture_levels, bool measure_diameters, int64_t dilate_um, bool measure_thickness) {
             VolumeMeta mt;
             mt.measure_diameters = measure_diameters;
+            mt.dilate_um = dilate_um;
+            mt.measure_thickness = measure_thickness;
             mt.measure_lesions = measure_lesions;
             mt.measure_intensity = measure_intensity;
             mt.measure_texture = measure_texture;
@@ -1922,7 +1981,8 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0}, py::arg("spacing_z_source") = "default",
           py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f, py::arg("intercept") = 0.f,
           py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false, py::arg("measure_texture") = false,
-          py::arg("texture_levels") = 32, py::arg("measure_diameters") = false)
+          py::arg("texture_levels") = 32, py::arg("measure_diameters") = false, py::arg("dilate_um") = -1,
+          py::arg("measure_thickness") = false)
       .def(
           "export_views",
           // After run() on a volume of this shape: the views of nm03/volume_views.h from the volume still on
@@ -1987,10 +2047,12 @@ PYBIND11_MODULE(_nm03, m) {
           [](VolumeRunner& self, Comm& comm, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> slab,
              int z0, int depth, const PipelineParams& p, int connectivity, int dilation,
              const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_lesions, bool measure_intensity,
-             bool measure_texture, bool measure_diameters) {
+             bool measure_texture, bool measure_diameters, int64_t dilate_um, bool measure_thickness) {
             SlabStats st;
             VolumeMeta mt;
             mt.measure_diameters = measure_diameters;
+            mt.dilate_um = dilate_um;  // refused by run_slab, as the measurements are
+            mt.measure_thickness = measure_thickness;
             mt.measure = measure;  // refused by run_slab (std::invalid_argument) before anything is launched
             mt.measure_lesions = measure_lesions;  // alike
             mt.measure_intensity = measure_intensity;
@@ -2007,7 +2069,7 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("connectivity") = 6, py::arg("dilation") = 7,
           py::arg("seeds") = std::vector<std::tuple<int, int, int>>{}, py::arg("measure") = false,
           py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false, py::arg("measure_texture") = false,
-          py::arg("measure_diameters") = false);
+          py::arg("measure_diameters") = false, py::arg("dilate_um") = -1, py::arg("measure_thickness") = false);
 
   // One-process rehearsal of the z-slab decomposition: `nranks` threads, each with its own
   // VolumeRunner (stream) on `device`, talking over loopback comms — the device-resident exchange
@@ -2969,6 +3031,170 @@ PYBIND11_MODULE(_nm03, m) {
   }, py::arg("dilated"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing") = std::vector<double>{1.0, 1.0, 1.0},
      py::arg("placement") = "corner", py::arg("scan_block") = 0, py::arg("max_bytes") = mesh::kDefaultMaxMb << 20,
      py::arg("stream") = 0);
+
+  // ---- K16: the distance map of nm03/volume_distance.h -------------------------------------------------
+  // The golden map (whole-line minima) of `mask` ([D, H, W], non-zero = set) → int64 [D, H, W].
+  m.def(
+      "golden_volume_distance",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> mask, const std::vector<int64_t>& spacing_um,
+         bool to_background, const py::object& cap_um) {
+        uint32_t um[3];
+        distance_args(mask, spacing_um, um);
+        const int64_t cap = cap_um.is_none() ? -1 : cap_um.cast<int64_t>();
+        if (!cap_um.is_none() && cap < 0) throw std::invalid_argument("cap_um must not be negative");
+        const int d = (int)mask.shape(0), h = (int)mask.shape(1), w = (int)mask.shape(2);
+        const std::vector<uint8_t> mk = from_np<uint8_t>(mask);
+        std::vector<int64_t> r;
+        {
+          py::gil_scoped_release nogil;
+          r = golden::volume_distance(mk, w, h, d, um, to_background, cap);
+        }
+        return to_np<int64_t>(r, {d, h, w});
+      },
+      py::arg("mask"), py::arg("spacing_um") = std::vector<int64_t>{1000, 1000, 1000}, py::arg("to_background") = false,
+      py::arg("cap_um") = py::none());
+  // The golden margin by the direct definition → uint8 [D, H, W].
+  m.def(
+      "golden_dilate3d_mm",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> region, const std::vector<int64_t>& spacing_um,
+         int64_t radius_um) {
+        uint32_t um[3];
+        distance_args(region, spacing_um, um);
+        const int d = (int)region.shape(0), h = (int)region.shape(1), w = (int)region.shape(2);
+        const std::vector<uint8_t> mk = from_np<uint8_t>(region);
+        std::vector<uint8_t> r;
+        {
+          py::gil_scoped_release nogil;
+          r = golden::dilate3d_mm(mk, w, h, d, um, radius_um);
+        }
+        return to_np<uint8_t>(r, {d, h, w});
+      },
+      py::arg("region"), py::arg("spacing_um") = std::vector<int64_t>{1000, 1000, 1000}, py::arg("radius_um") = 0);
+  // The golden thickness → the thickness dict (inscribed_um2, inscribed_at, found, inscribed_radius_mm, thickness_mm).
+  m.def(
+      "golden_volume_thickness",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> mask, const std::vector<int64_t>& spacing_um) {
+        uint32_t um[3];
+        distance_args(mask, spacing_um, um);
+        const int d = (int)mask.shape(0), h = (int)mask.shape(1), w = (int)mask.shape(2);
+        const std::vector<uint8_t> mk = from_np<uint8_t>(mask);
+        VolumeThickness t;
+        {
+          py::gil_scoped_release nogil;
+          t = golden::volume_thickness(mk, w, h, d, um);
+        }
+        return volume_thickness_dict(t);
+      },
+      py::arg("mask"), py::arg("spacing_um") = std::vector<int64_t>{1000, 1000, 1000});
+  // The map and the thickness from the K16 kernels' per-line functions run on the host
+  // (measure::volume_distance_words): what the kernels compute, without a GPU. `junk`: the storage bits past
+  // the width are set, as a kernel may find them.
+  m.def(
+      "volume_distance_words",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> mask, const std::vector<int64_t>& spacing_um,
+         bool to_background, const py::object& cap_um, bool junk) {
+        uint32_t um[3];
+        distance_args(mask, spacing_um, um);
+        const int64_t cap = cap_um.is_none() ? -1 : cap_um.cast<int64_t>();
+        if (!cap_um.is_none() && cap < 0) throw std::invalid_argument("cap_um must not be negative");
+        const int d = (int)mask.shape(0), h = (int)mask.shape(1), w = (int)mask.shape(2), wpr = (w + 63) / 64;
+        std::vector<uint64_t> words = pack_volume(mask);
+        if (junk)
+          for (size_t r = 0; r < (size_t)d * h; ++r) words[r * wpr + wpr - 1] |= ~row_word_mask(wpr - 1, w);
+        std::vector<int64_t> out((size_t)w * h * d);
+        {
+          py::gil_scoped_release nogil;
+          measure::volume_distance_words(words.data(), w, h, d, wpr, um, to_background, cap, out.data());
+        }
+        return to_np<int64_t>(out, {d, h, w});
+      },
+      py::arg("mask"), py::arg("spacing_um") = std::vector<int64_t>{1000, 1000, 1000}, py::arg("to_background") = false,
+      py::arg("cap_um") = py::none(), py::arg("junk") = false);
+  m.def(
+      "volume_thickness_words",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> mask, const std::vector<int64_t>& spacing_um) {
+        uint32_t um[3];
+        distance_args(mask, spacing_um, um);
+        const int d = (int)mask.shape(0), h = (int)mask.shape(1), w = (int)mask.shape(2), wpr = (w + 63) / 64;
+        const std::vector<uint64_t> words = pack_volume(mask);
+        VolumeThickness t;
+        {
+          py::gil_scoped_release nogil;
+          t = measure::volume_thickness_words(words.data(), w, h, d, wpr, um);
+        }
+        return volume_thickness_dict(t);
+      },
+      py::arg("mask"), py::arg("spacing_um") = std::vector<int64_t>{1000, 1000, 1000});
+  // Empty, or why a w × h × d volume at (ux, uy, uz) is refused by the extent rule.
+  m.def("volume_distance_extent_error", [](int w, int h, int d, const std::vector<int64_t>& spacing_um) {
+    uint32_t um[3];
+    spacing_um_from(spacing_um, um);
+    return measure::volume_distance_extent_error(w, h, d, um);
+  });
+  // `text` (a volume sidecar) with the thickness keys of a thickness dict at (ux, uy, uz).
+  m.def("volume_insert_thickness_keys", [](const std::string& text, const py::dict& thickness, const std::vector<int64_t>& spacing_um) {
+    uint32_t um[3];
+    spacing_um_from(spacing_um, um);
+    return measure::insert_thickness_keys(text, volume_thickness_from(thickness), um);
+  });
+  // llround(R · 1000): the margin of --dilate-mm in micrometres.
+  m.def("dilate_mm_to_um", [](double mm) { return measure::dilate_mm_to_um(mm); });
+  m.attr("NO_DISTANCE") = py::int_(kNoDistance);
+
+  // K16 alone on a device bit volume [d][h][ceil(w/64)] (int64 words). mode "map": `out` is int64 [d][h][w];
+  // "margin": `out` is a bit volume like `bits`, `cap_um` the radius; "thickness": returns the dict. The work
+  // buffer is this op's own; synchronous on `stream`.
+  m.def("k_volume_distance", [](uintptr_t bits, int w, int h, int d, const std::vector<int64_t>& spacing_um, const std::string& mode,
+                                bool to_background, int64_t cap_um, uintptr_t out, uintptr_t stream) -> py::object {
+    hipStream_t st = as_stream(stream);
+    if (w <= 0 || h <= 0 || d <= 0) throw std::invalid_argument("empty volume");
+    uint32_t um[3];
+    spacing_um_from(spacing_um, um);
+    const std::string ext = measure::volume_distance_extent_error(w, h, d, um);
+    if (!ext.empty()) throw std::invalid_argument(ext);
+    if (mode != "map" && mode != "margin" && mode != "thickness") throw std::invalid_argument("mode must be map, margin or thickness");
+    if (mode == "margin" && cap_um < 0) throw std::invalid_argument("the radius must not be negative");
+    {
+      // K16's code object, loaded on the current device before this op's first launch there.
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_volume_distance();
+        preloaded.push_back(dev);
+      }
+    }
+    const gpu::VolumeDistanceLayout L = gpu::volume_distance_layout(w, h, d);
+    struct DevMem {
+      void* p = nullptr;
+      ~DevMem() {
+        if (p) (void)hipFree(p);
+      }
+    } work;
+    gpu::check_hip(hipMalloc(&work.p, L.bytes), "hipMalloc distance work");
+    if (mode == "map") {
+      gpu::launch_volume_distance((const uint64_t*)bits, L, um, to_background, cap_um, work.p, (int64_t*)out, st);
+      gpu::check_hip(hipStreamSynchronize(st), "k_volume_distance");
+      return py::none();
+    }
+    if (mode == "margin") {
+      gpu::launch_volume_margin((const uint64_t*)bits, L, um, cap_um, work.p, (uint64_t*)out, st);
+      gpu::check_hip(hipStreamSynchronize(st), "k_volume_distance margin");
+      return py::none();
+    }
+    VolumeThickness* h_rec = nullptr;
+    gpu::check_hip(hipHostMalloc((void**)&h_rec, sizeof(VolumeThickness), hipHostMallocDefault), "hipHostMalloc thickness");
+    struct Pinned {
+      void* p;
+      ~Pinned() { (void)hipHostFree(p); }
+    } pinned{h_rec};
+    gpu::launch_volume_thickness((const uint64_t*)bits, L, um, work.p, h_rec, st);
+    gpu::check_hip(hipStreamSynchronize(st), "k_volume_distance thickness");
+    return volume_thickness_dict(*h_rec);
+  }, py::arg("bits"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_um"), py::arg("mode") = "map",
+     py::arg("to_background") = false, py::arg("cap_um") = -1, py::arg("out") = 0, py::arg("stream") = 0);
 
   // K11 on a batch of masks of ANY sizes in one launch: planes = the masks' bit planes back to back
   // (mask i: hs[i] × ceil(ws[i] / 64) words); raw = the slices' u16 samples back to back; one pixel type

@@ -177,6 +177,11 @@ struct VolumeDevice {
   // level count fits), allocated by the first run that asks for them and kept.
   std::unique_ptr<DevBuf> vt_acc;
   void* h_texture = nullptr;
+  // K16 (VolumeParams::dilate_um / measure_thickness): the layout, the scratch of the three passes and the
+  // pinned thickness record, allocated by the first run that asks for either and kept.
+  VolumeDistanceLayout dist_layout;
+  std::unique_ptr<DevBuf> dist_work;
+  VolumeThickness* h_thickness = nullptr;
   VolumeDevice(const VolumeInput& v)
       : w(v.w), h(v.h), d(v.d), wpr((v.w + 63) / 64), words((size_t)v.h * ((v.w + 63) / 64)),
         ps(((size_t)v.w * v.h + 7) / 8 * 8),
@@ -201,6 +206,7 @@ struct VolumeDevice {
     if (h_diameters) (void)hipHostFree(h_diameters);
     if (h_intensity) (void)hipHostFree(h_intensity);
     if (h_texture) (void)hipHostFree(h_texture);
+    if (h_thickness) (void)hipHostFree(h_thickness);
     if (h_measure) (void)hipHostFree(h_measure);
     if (h_tables) (void)hipHostFree(h_tables);
     if (h_flag) (void)hipHostFree(h_flag);
@@ -283,8 +289,12 @@ static void volume_segment(VolumeDevice& V, const VolumeInput& v, const VolumePa
   srg_volume(V.band.as<uint64_t>(), V.region.as<uint64_t>(), v.w, v.h, v.d, V.seeds.as<int32_t>(),
              (int)(sx.size() / 3), p.connectivity, V.flag.as<uint32_t>(), V.h_flag,
              V.srg_scratch.as<uint64_t>(), V.stream);
-  dilate_volume(V.region.as<uint64_t>(), V.dil.as<uint64_t>(), V.tmp.as<uint64_t>(), v.w, v.h, v.d, p.dilation_size,
-                V.stream, V.morph_scratch.as<uint64_t>(), p.pipe.se_shape == kSeDisc);
+  if (p.dilate_um >= 0)  // K16's margin in place of the cube / ball: three launches, region → dil
+    launch_volume_margin(V.region.as<uint64_t>(), V.dist_layout, p.spacing_um, p.dilate_um, V.dist_work->p, V.dil.as<uint64_t>(),
+                         V.stream);
+  else
+    dilate_volume(V.region.as<uint64_t>(), V.dil.as<uint64_t>(), V.tmp.as<uint64_t>(), v.w, v.h, v.d, p.dilation_size,
+                  V.stream, V.morph_scratch.as<uint64_t>(), p.pipe.se_shape == kSeDisc);
 }
 
 static void unpack_volume(const DevBuf& b, const VolumeDevice& V, std::vector<uint8_t>& out) {
@@ -414,6 +424,7 @@ struct VolumeRunner::Impl {
   bool diameters_loaded = false;  // K13's code object (first run that asks for diameters)
   bool intensity_loaded = false;  // K11's code object (first run that asks for the intensity statistics)
   bool texture_loaded = false;    // K12's code object (first run that asks for the texture)
+  bool distance_loaded = false;   // K16's code object (first run that asks for a margin in mm or the thickness)
   explicit Impl(int dev) : device(dev) {
     check_hip(hipSetDevice(device), "hipSetDevice");
     preload_kernels();  // every code object, before the first launch (kernels.h)
@@ -467,6 +478,18 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
   if (p.measure_texture && !p.measure) throw std::invalid_argument("3D texture needs measure");
   if (p.measure_texture && (p.texture_levels < 2 || p.texture_levels > 64))
     throw std::invalid_argument("3D texture levels must be 2..64 (got " + std::to_string(p.texture_levels) + ")");
+  if (p.measure_thickness && !p.measure) throw std::invalid_argument("3D thickness needs measure");
+  if (p.dilate_um >= 0 || p.measure_thickness) {
+    const char* who = p.dilate_um >= 0 ? "3D margin in millimetres: " : "3D thickness: ";
+    if (p.dilate_um > kMaxDilateUm)
+      throw std::invalid_argument("3D margin in millimetres: the radius must be at most " + std::to_string(kMaxDilateUm) +
+                                  " um (got " + std::to_string(p.dilate_um) + ")");
+    for (int a = 0; a < 3; ++a)
+      if (p.spacing_um[a] < 1u) throw std::invalid_argument(std::string(who) + "a spacing must be at least 1 um");
+    if (v.w > 65535) throw std::invalid_argument(std::string(who) + "a row holds at most 65535 voxels");
+    const std::string ext = measure::volume_distance_extent_error(v.w, v.h, v.d, p.spacing_um);
+    if (!ext.empty()) throw std::invalid_argument(who + ext);
+  }
   if (p.measure) {
     if (p.measure_connectivity != 6 && p.measure_connectivity != 26)
       throw std::invalid_argument("3D measurement connectivity must be 6 or 26 (got " +
@@ -532,6 +555,18 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
       }
     }
   }
+  if (p.dilate_um >= 0 || p.measure_thickness) {  // K16 alike, after every check of this run
+    if (!I.distance_loaded) {
+      preload_volume_distance();
+      I.distance_loaded = true;
+    }
+    if (!V.dist_work) {
+      V.dist_layout = volume_distance_layout(v.w, v.h, v.d);
+      V.dist_work = std::make_unique<DevBuf>(V.dist_layout.bytes);
+    }
+    if (p.measure_thickness && !V.h_thickness)
+      check_hip(hipHostMalloc((void**)&V.h_thickness, sizeof(VolumeThickness), hipHostMallocDefault), "hipHostMalloc thickness");
+  }
   const PipeConsts pc = make_consts(p.pipe, 2);
   check_hip(hipEventRecord(I.e0, V.stream), "event");
   VolumeResult r;
@@ -566,10 +601,13 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
     if (p.measure_texture)  // K12's four launches after K11's
       launch_volume_texture(V.dil.as<uint64_t>(), V.raw.as<uint16_t>(), V.ps, v.w, v.h, v.d, (uint8_t)v.type,
                             (uint8_t)v.stored_bits, p.texture_levels, V.vt_acc->p, V.h_texture, V.stream);
+    if (p.measure_thickness)  // K16's four launches after K12's; its scratch is its own
+      launch_volume_thickness(V.dil.as<uint64_t>(), V.dist_layout, p.spacing_um, V.dist_work->p, V.h_thickness, V.stream);
     check_hip(hipEventRecord(I.e2, V.stream), "event");
     check_hip(hipEventSynchronize(I.e2), "sync");
     r.measure = *V.h_measure;
     if (p.measure_intensity) r.intensity = *V.h_intensity;
+    if (p.measure_thickness) r.thickness = *V.h_thickness;
     if (p.measure_texture) {
       r.texture = measure::glcm_from_record(V.h_texture);
       measure::check_glcm_exact(r.texture.head.samples);  // a cell may have wrapped: no result, as on the CPU
@@ -728,6 +766,9 @@ static SlabStats slab_grow_dilate_gpu(Comm& comm, VolumeDevice& V, int nseeds, i
 VolumeResult VolumeRunner::run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p,
                                     bool want_masks, SlabStats* stats) {
   if (slab.d < 1 || slab.w < 1 || slab.h < 1) throw SliceError("empty slab");
+  if (p.dilate_um >= 0 || p.measure_thickness)
+    throw std::invalid_argument("run_slab: a margin in millimetres and the thickness are not supported on a volume split "
+                                "into slabs (a margin across slabs needs a halo of its reach)");
   if (p.measure || p.measure_lesions || p.measure_diameters || p.measure_intensity || p.measure_texture)
     throw std::invalid_argument("run_slab: measuring a volume split into slabs is not supported "
                                 "(components that cross slabs need a collective)");
@@ -1261,7 +1302,8 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
                                                       measure::Glcm* texture = nullptr,
                                                       std::vector<VolumeLesionDiameters>* diameters = nullptr,
                                                       const ViewsAt* views_at = nullptr, VolumeViewsExport* views = nullptr,
-                                                      VolumeMesh* mesh_out = nullptr, int mesh_placement = kMeshCorner) {
+                                                      VolumeMesh* mesh_out = nullptr, int mesh_placement = kMeshCorner,
+                                                      VolumeThickness* thickness = nullptr) {
   const GoldenPlanes gp = golden_preprocess(v, vp);
   std::vector<Seed> seeds = vp.seeds;
   if (seeds.empty()) {
@@ -1269,7 +1311,9 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
     for (auto& sd : seeds) sd.z = v.d / 2;
   }
   const auto region = golden::region_grow3d(gp.band, v.w, v.h, v.d, seeds, vp.connectivity);
-  const auto dil = golden::dilate3d(region, v.w, v.h, v.d, vp.dilation_size, vp.pipe.se_shape == kSeDisc);
+  const auto dil = vp.dilate_um >= 0 ? golden::dilate3d_mm(region, v.w, v.h, v.d, vp.spacing_um, vp.dilate_um)
+                                      : golden::dilate3d(region, v.w, v.h, v.d, vp.dilation_size, vp.pipe.se_shape == kSeDisc);
+  if (measured && thickness && vp.measure_thickness) *thickness = golden::volume_thickness(dil, v.w, v.h, v.d, vp.spacing_um);
   if (measured) *measured = golden::measure_volume(dil, region, v, vp.measure_connectivity);
   if (measured && lesions && vp.measure_lesions)
     *lesions = golden::measure_volume_lesions(dil, v, vp.measure_connectivity, vp.measure_lesions);
@@ -1319,6 +1363,8 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
   vp.measure_intensity = cfg.measure_volume_intensity;
   vp.measure_texture = cfg.measure_volume_texture;
   vp.texture_levels = cfg.engine.pipe.texture_levels;
+  vp.dilate_um = cfg.dilate_um;
+  vp.measure_thickness = cfg.measure_volume_thickness;
   const RenderParams& rp = cfg.engine.render;
   const double t_start = wall_now();
   // ---- plan on rank 0 -----------------------------------------------------------------------
@@ -1460,6 +1506,14 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         const std::string ext = measure::volume_diameters_extent_error(v.w, v.h, v.d, vp.spacing_um);
         if (!ext.empty()) throw std::runtime_error("--measure-volume-diameters: " + ext);
       }
+      VolumeThickness thickness = {};
+      if (vp.dilate_um >= 0 || vp.measure_thickness) {  // the spacing the distances are taken in, and the extent rule
+        measure::volume_spacing_um((double)v.spacing_x, (double)v.spacing_y, v.spacing_z, vp.spacing_um);
+        const std::string ext = v.w > 65535 ? std::string("a row holds at most 65535 voxels")
+                                            : measure::volume_distance_extent_error(v.w, v.h, v.d, vp.spacing_um);
+        if (!ext.empty())
+          throw std::runtime_error(std::string(vp.dilate_um >= 0 ? "--dilate-mm: " : "--measure-volume-thickness: ") + ext);
+      }
       VolumeMesh vmesh;
       const uint64_t mesh_cap = cfg.volume_mesh_max_mb << 20;
       VolumeViewsExport vx;
@@ -1470,7 +1524,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       if (cfg.cpu) {
         files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions, &intensity, &texture, &diameters,
                                     cfg.volume_views ? &cfg.volume_views_at : nullptr, &vx, cfg.volume_mesh ? &vmesh : nullptr,
-                                    cfg.volume_mesh_placement);
+                                    cfg.volume_mesh_placement, &thickness);
         if (cfg.volume_mesh) {  // the check export_mesh makes between its two halves
           const std::string err = mesh::size_error(vmesh.vertices(), vmesh.quad_count(), mesh_cap);
           if (!err.empty()) throw std::runtime_error("--volume-mesh: " + err);
@@ -1485,6 +1539,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         diameters = std::move(r.diameters);
         intensity = r.intensity;
         texture = std::move(r.texture);
+        thickness = r.thickness;
         VolumeExportStats xs;
         files = runner->export_jpegs(v, vp, rp, &xs);
         if (cfg.volume_views) vx = runner->export_views(v, vp, rp, cfg.volume_views_at, false, &xs);
@@ -1524,6 +1579,8 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
                              ? golden::measure_volume_json(measured, lesions, vp.measure_lesions, v, vp.pipe.apply_rescale,
                                                            vp.measure_connectivity)
                              : golden::measure_volume_json(measured, v, vp.pipe.apply_rescale, vp.measure_connectivity);
+        if (vp.measure_thickness)  // after the global keys, before diameters_spacing_um / lesions_max
+          o.measure_json = measure::insert_thickness_keys(std::move(o.measure_json), thickness, vp.spacing_um);
         if (vp.measure_diameters)  // last, so that diameters_spacing_um stands directly before lesions_max
           o.measure_json = measure::insert_diameter_keys(std::move(o.measure_json), diameters.data(), (int)diameters.size(),
                                                          vp.spacing_um);
@@ -1659,7 +1716,8 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
     for (size_t i = 0; i < plan.size(); ++i) rows.push_back({plan[i].id, outs[i].ok != 0, outs[i].measure_json});
     try {
       volume_totals = write_volumes_csv(cfg.out_dir, rows, cfg.measure_volume_intensity,
-                                        cfg.measure_volume_texture ? cfg.engine.pipe.texture_levels : 0);
+                                        cfg.measure_volume_texture ? cfg.engine.pipe.texture_levels : 0,
+                                        cfg.measure_volume_thickness);
     } catch (const std::exception& e) {
       std::cerr << "Error writing volumes.csv: " << e.what() << std::endl;
     }
@@ -1674,8 +1732,9 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
   if (!cfg.json.empty()) {
     std::ofstream f(cfg.json, std::ios::trunc);
     f << "{\"mode\": \"3d\", \"backend\": \"" << (cfg.cpu ? "cpu" : "gpu") << "\", \"gpus\": " << size
-      << ", \"comm\": \"" << comm.backend() << "\", \"dilation_size\": " << vp.dilation_size
-      << ", \"connectivity\": " << vp.connectivity << ", \"split_volume\": " << (cfg.split_volume ? "true" : "false")
+      << ", \"comm\": \"" << comm.backend() << "\", \"dilation_size\": " << vp.dilation_size;
+    if (cfg.dilate_um >= 0) f << ", \"dilate_mm\": " << cfg.dilate_mm << ", \"dilate_um\": " << cfg.dilate_um;
+    f << ", \"connectivity\": " << vp.connectivity << ", \"split_volume\": " << (cfg.split_volume ? "true" : "false")
       << ", \"wall_s\": " << tot << ", \"slices\": " << slices
       << ", \"jpeg_fallbacks\": " << fallbacks << ", \"per_rank_wall_s\": [";
     for (int r = 0; r < size; ++r) f << (r ? ", " : "") << walls[r];

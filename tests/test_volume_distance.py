@@ -1,0 +1,282 @@
+"""The distance map in physical space (nm03/volume_distance.h, K16), its margin and the thickness without a GPU,
+everything compared with == on integers, bits and text:
+  golden == the SciPy-index reference on every case, both polarities, every cap, == the all-pairs brute force on the
+  cases of at most 4096 voxels (the SciPy comparisons alone need SciPy); the kernels' per-line functions on the host
+  == golden; the direct margin == the threshold of the map; the isotropic relation to the digital ball; monotone in R;
+  0 exactly on S; the 319- and 123-voxel examples; slab, ball and hollow shell by hand; the sidecar text with and
+  without the keys; the extent rule's message."""
+import json
+
+import numpy as np
+import pytest
+
+import volume_distance_cases as dc
+
+CASES = dc.all_cases()
+NO = dc.NO_DISTANCE
+
+
+@pytest.fixture(scope="module")
+def goldens(native):
+    """The uncapped golden map of every case and polarity, computed once and shared (read-only)."""
+    out = {}
+    for c in CASES:
+        for to in dc.POLARITIES:
+            g = native.golden_volume_distance(c["mask"], list(c["um"]), to == "background", None)
+            g.setflags(write=False)
+            out[(c["name"], to)] = g
+    return out
+
+
+def capped(g, cap):
+    if cap is None:
+        return g
+    out = g.copy()
+    out[out > cap * cap] = NO
+    return out
+
+
+@pytest.mark.parametrize("c", CASES, ids=dc.ids(CASES))
+def test_golden_equals_scipy_index_reference(native, goldens, c):
+    pytest.importorskip("scipy.ndimage")  # the reference asks SciPy for the nearest voxel's indices
+    from nm03_capstone_project_amd.ops import reference
+    assert native.NO_DISTANCE == NO == reference.NO_DISTANCE
+    for to in dc.POLARITIES:
+        g = goldens[(c["name"], to)]
+        assert g.dtype == np.int64 and g.shape == c["mask"].shape
+        assert np.array_equal(g, reference.volume_distance(c["mask"], c["um"], to))
+        for cap in c["caps"]:
+            got = native.golden_volume_distance(c["mask"], list(c["um"]), to == "background", cap)
+            assert np.array_equal(got, capped(g, cap)), (to, cap)
+            assert np.array_equal(got, reference.volume_distance(c["mask"], c["um"], to, cap)), (to, cap)
+
+
+SMALL = [c for c in CASES if dc.voxels(c) <= 4096]
+
+
+@pytest.mark.parametrize("c", SMALL, ids=dc.ids(SMALL))
+def test_golden_equals_all_pairs_brute_force(native, goldens, c):
+    from nm03_capstone_project_amd.ops import reference
+    for to in dc.POLARITIES:
+        g = goldens[(c["name"], to)]
+        assert np.array_equal(g, reference.volume_distance_brute(c["mask"], c["um"], to))
+        for cap in c["caps"]:
+            got = native.golden_volume_distance(c["mask"], list(c["um"]), to == "background", cap)
+            assert np.array_equal(got, capped(g, cap)), (to, cap)
+            assert np.array_equal(got, reference.volume_distance_brute(c["mask"], c["um"], to, cap)), (to, cap)
+
+
+@pytest.mark.parametrize("c", CASES, ids=dc.ids(CASES))
+def test_host_core_equals_golden(native, goldens, c):
+    for to in dc.POLARITIES:
+        for cap in c["caps"]:
+            want = capped(goldens[(c["name"], to)], cap)
+            for junk in (False, True):  # the storage bits past the width set, as a kernel may find them
+                got = native.volume_distance_words(c["mask"], list(c["um"]), to == "background", cap, junk)
+                assert np.array_equal(got, want), (to, cap, junk)
+    assert native.volume_thickness_words(c["mask"], list(c["um"])) == native.golden_volume_thickness(c["mask"], list(c["um"]))
+
+
+@pytest.mark.parametrize("c", CASES, ids=dc.ids(CASES))
+def test_zero_exactly_on_the_set_and_none_when_empty(goldens, c):
+    for to in dc.POLARITIES:
+        s = c["mask"].astype(bool) if to == "foreground" else ~c["mask"].astype(bool)
+        g = goldens[(c["name"], to)]
+        if s.any():
+            assert np.array_equal(g == 0, s) and int(g.max()) < 2 ** 62
+        else:
+            assert (g == NO).all()
+
+
+def test_caps_hit_their_boundaries(goldens):
+    """Cap 0 keeps S alone; a cap exactly on an attained distance keeps it (<=, not <); a cap between two attained
+    distances drops the upper one."""
+    c = dc.case("worked_example")
+    g = goldens[(c["name"], "foreground")]
+    attained = set(np.unique(g).tolist())
+    assert {500 ** 2, 5000 ** 2, 2 * 500 ** 2} <= attained and 700 ** 2 not in attained
+    assert 500 ** 2 < 700 ** 2 < 2 * 500 ** 2  # 700 um lies between two attained distances
+    assert int((capped(g, 0) != NO).sum()) == 1
+    assert int((capped(g, 500) != NO).sum()) == 5  # the voxel and its four in-plane neighbours
+    assert int((capped(g, 700) != NO).sum()) == 5
+    assert int((capped(g, 5000) != NO).sum()) == 319 and int((capped(g, 5001) != NO).sum()) == 319
+    for other in CASES:  # every case's caps separate something unless its set is empty or everything
+        gg = goldens[(other["name"], "foreground")]
+        if other["mask"].any() and not other["mask"].all():
+            ux = other["um"][0]
+            assert int((gg <= 0).sum()) <= int((gg <= ux * ux).sum()) <= int((gg <= (ux + ux // 2) ** 2).sum())
+
+
+def test_anisotropic_nearest(goldens):
+    g = goldens[("anisotropic_nearest", "foreground")]
+    assert g[1, 1, 4] == 16_000_000  # via dx = 4 to (8, 1, 1), not 25 000 000 via dz = 1 to (4, 1, 2)
+
+
+@pytest.mark.parametrize("c", CASES, ids=dc.ids(CASES))
+def test_direct_margin_equals_threshold(native, goldens, c):
+    g = goldens[(c["name"], "foreground")]
+    ux, uy, uz = c["um"]
+    prev = None
+    for r in (0, ux - 1, ux, uy, uz, 2 * max(c["um"]) + 1, 3 * max(c["um"])):
+        got = native.golden_dilate3d_mm(c["mask"], list(c["um"]), r)
+        assert np.array_equal(got.astype(bool), g <= r * r), r
+        if r == 0:
+            assert np.array_equal(got, c["mask"])
+    for r in sorted((0, ux - 1, ux, uy, uz, 2 * max(c["um"]) + 1, 3 * max(c["um"]))):  # monotone in R
+        cur = native.golden_dilate3d_mm(c["mask"], list(c["um"]), r).astype(bool)
+        assert prev is None or not (prev & ~cur).any()
+        prev = cur
+
+
+@pytest.mark.parametrize("s_um", [1000, 700])
+def test_isotropic_margin_is_the_digital_ball(native, s_um):
+    rng = np.random.RandomState(7)
+    region = (rng.random_sample((11, 13, 70)) < 0.01).astype(np.uint8)
+    region[5, 6, 64] = 1
+    for k in range(5):
+        want = native.golden_dilate3d(region, 2 * k + 1, True)
+        assert np.array_equal(native.golden_dilate3d_mm(region, [s_um] * 3, k * s_um), want), k
+
+
+def test_worked_counts(native):
+    c = dc.case("worked_example")
+    assert native.dilate_mm_to_um(5) == 5000 and native.dilate_mm_to_um(2.5) == 2500 and native.dilate_mm_to_um(0.0004) == 0
+    got = native.golden_dilate3d_mm(c["mask"], list(c["um"]), 5000)
+    assert int(got.sum()) == 319 and int(got[2].sum()) == 317 and got[1, 10, 10] == got[3, 10, 10] == 1
+    assert int(got[1].sum()) == int(got[3].sum()) == 1 and int(got[0].sum()) == int(got[4].sum()) == 0
+    assert int(native.golden_dilate3d(c["mask"], 7, False).sum()) == 5 * 7 * 7  # the cube, clipped by the 5 planes
+    one = np.zeros((9, 9, 9), np.uint8)
+    one[4, 4, 4] = 1
+    assert int(native.golden_dilate3d_mm(one, [1000] * 3, 3000).sum()) == 123
+    assert int(native.golden_dilate3d(one, 7, False).sum()) == 343
+
+
+# ---- thickness ---------------------------------------------------------------------------------------
+def test_thickness_slab_ball_and_shell_by_hand(native):
+    for n in (1, 2, 3, 4, 7):  # a slab n voxels thick along x: the radius is (floor((n - 1) / 2) + 1) * ux
+        m = np.zeros((3, 4, n + 4), np.uint8)
+        m[:, :, 2:2 + n] = 1
+        t = native.golden_volume_thickness(m, [800, 1000, 1000])
+        r_um = ((n - 1) // 2 + 1) * 800
+        assert t["inscribed_um2"] == r_um ** 2 and t["inscribed_at"] == [2 + (n - 1) // 2, 0, 0] and t["found"]
+        assert t["inscribed_radius_mm"] == r_um / 1000.0 and t["thickness_mm"] == 2 * r_um / 1000.0
+    # the digital ball of radius 3 at 1 mm: the nearest voxel outside d^2 <= 9 from the centre is (1, 3, 0), d^2 = 10
+    t = native.golden_volume_thickness(dc.ball(3), [1000] * 3)
+    assert t["inscribed_um2"] == 10_000_000 and t["inscribed_at"] == [4, 4, 4]
+    assert t["inscribed_radius_mm"] == np.sqrt(10.0) and t["thickness_mm"] == 2 * np.sqrt(10.0)
+    # a hollow shell 4 < d^2 <= 25: its voxel (0, -2, -3) (d^2 = 13) has the outside voxel (1, -3, -4) (d^2 = 26) at
+    # squared distance 3 and nothing of the cavity or the outside nearer; no shell voxel is further from both
+    zz, yy, xx = np.indices((13, 13, 13)) - 6
+    r2 = xx * xx + yy * yy + zz * zz
+    shell = ((r2 <= 25) & (r2 > 4)).astype(np.uint8)
+    t = native.golden_volume_thickness(shell, [1000] * 3)
+    assert t["inscribed_um2"] == 3_000_000 and t["inscribed_at"] == [6, 4, 3]
+    assert t["inscribed_um2"] < native.golden_volume_thickness((r2 <= 25).astype(np.uint8), [1000] * 3)["inscribed_um2"]
+
+
+@pytest.mark.parametrize("c", CASES, ids=dc.ids(CASES))
+def test_thickness_equals_the_map_and_the_reference(native, goldens, c):
+    t = native.golden_volume_thickness(c["mask"], list(c["um"]))
+    g = goldens[(c["name"], "background")]
+    m = c["mask"].astype(bool)
+    if m.any() and not m.all():
+        x, y, z = t["inscribed_at"]
+        assert t["found"] and m[z, y, x] and g[z, y, x] == t["inscribed_um2"] == int(g[m].max())
+        zs, ys, xs = np.nonzero(m & (g == t["inscribed_um2"]))
+        assert (int(zs[0]), int(ys[0]), int(xs[0])) == (z, y, x)  # the smallest raster (z, y, x) on a tie
+    else:
+        assert t == {"inscribed_um2": 0, "inscribed_at": [-1, -1, -1], "found": False, "inscribed_radius_mm": None,
+                     "thickness_mm": None}
+    if c["name"] == "two_cubes_tie":
+        assert int((m & (g == t["inscribed_um2"])).sum()) > 1 and t["inscribed_at"] == [2, 2, 0]
+    pytest.importorskip("scipy.ndimage")
+    from nm03_capstone_project_amd.ops import reference
+    assert t == reference.volume_thickness(c["mask"], c["um"])
+
+
+# ---- sidecar text ------------------------------------------------------------------------------------
+def strip_thickness(text):
+    a = text.index(',"thickness_spacing_um":')
+    b = text.index(',"thickness_mm":')
+    e = b + len(',"thickness_mm":')
+    while text[e] not in ",}":
+        e += 1
+    return text[:a] + text[e:]
+
+
+def test_sidecar_text_with_and_without_the_keys(native):
+    import volume_lesion_cases as vlc
+    mask = vlc.word_straddle(130)
+    region, raw = vlc.inputs(mask)
+    rec = native.golden_measure_volume(mask, region, raw, "u16", 16, 26)
+    les = native.golden_measure_volume_lesions(mask, raw, 5, "u16", 16, 26)
+    inten = native.golden_measure_volume_intensity(mask, raw, "u16", 16)
+    tex = native.golden_measure_volume_texture(mask, raw, 8, "u16", 16)
+    args = (130, 9, 6, 0.977, 1.02, 3.3, "position", 2.0, -5.0, True, 26)
+    um = native.volume_spacing_um(float(np.float32(0.977)), float(np.float32(1.02)), 3.3)
+    th = native.golden_volume_thickness(mask, list(um))
+    dia = native.golden_measure_volume_diameters(mask, 5, um, 26)
+    assert th["found"]
+    for kw, before, after in ((dict(), "mean", None), (dict(intensity=inten), "iqr", None),
+                              (dict(intensity=inten, texture=tex), "glcm_diff_entropy", None),
+                              (dict(lesions=les, lesions_max=5), "mean", "lesions_max"),
+                              (dict(lesions=les, lesions_max=5, intensity=inten, texture=tex, diameters=dia), "glcm_diff_entropy",
+                               "diameters_spacing_um")):
+        plain = native.volume_measure_to_json(rec, *args, **kw)
+        text = native.volume_measure_to_json(rec, *args, thickness=th, **kw)
+        assert text != plain and strip_thickness(text) == plain and text.count("\n") == 1
+        assert native.volume_insert_thickness_keys(plain, th, list(um)) == text
+        d = json.loads(text)
+        keys = list(d)
+        i = keys.index("thickness_spacing_um")
+        assert keys[i:i + 5] == ["thickness_spacing_um", "inscribed_um2", "inscribed_at", "inscribed_radius_mm", "thickness_mm"]
+        assert keys[i - 1] == before and (keys[i + 5] if after else len(keys)) == (after or i + 5)
+        assert d["thickness_spacing_um"] == list(um) and d["inscribed_um2"] == th["inscribed_um2"]
+        assert d["inscribed_at"] == th["inscribed_at"]
+        assert d["inscribed_radius_mm"] == float("%.9g" % th["inscribed_radius_mm"])
+        assert d["thickness_mm"] == float("%.9g" % th["thickness_mm"])
+    empty = native.golden_volume_thickness(np.zeros((2, 3, 4), np.uint8), [1000] * 3)
+    text = native.volume_measure_to_json(rec, *args, thickness=empty)
+    assert ',"inscribed_um2":0,"inscribed_at":[-1,-1,-1],"inscribed_radius_mm":null,"thickness_mm":null}' in text
+
+
+def test_pipeline_golden_measure_with_thickness(native):
+    import nm03_capstone_project_amd as nm
+    import volume_lesion_cases as vlc
+    mask = vlc.equal_boxes()
+    region, raw = vlc.inputs(mask)
+    sp = (0.5, 0.5, 5.0)
+    kw = dict(measure=True, measure_lesions=4, measure_diameters=True)
+    plain = nm.VolumePipeline(**kw).golden_measure(mask, region, raw, spacing=sp)
+    out = nm.VolumePipeline(measure_thickness=True, **kw).golden_measure(mask, region, raw, spacing=sp)
+    th = native.golden_volume_thickness(mask, [500, 500, 5000])
+    assert out[-1] == th and out[:1] + out[2:-1] == plain[:1] + plain[2:] and strip_thickness(out[1]) == plain[1]
+    for bad in (dict(measure_thickness=True), dict(dilate_mm=-1), dict(dilate_mm=1000.5), dict(dilate_mm=float("nan"))):
+        with pytest.raises(ValueError):
+            nm.VolumePipeline(**bad)
+    # the golden dilation of the pipeline follows dilate_mm
+    band = np.zeros((5, 21, 21), np.uint8)
+    band[2, 10, 10] = 1
+    region, dil = nm.VolumePipeline(dilate_mm=5).golden(band, [(10, 10, 2)], spacing=sp)
+    assert int(region.sum()) == 1 and int(dil.sum()) == 319
+
+
+# ---- the extent rule ---------------------------------------------------------------------------------
+def test_extent_rule(native):
+    assert native.volume_distance_extent_error(65535, 65535, 65535, [1000, 1000, 1000]) == ""
+    # (2^15 * 2^16)^2 = 2^62 on one axis: refused; one micrometre less: accepted
+    assert native.volume_distance_extent_error(2 ** 15 + 1, 1, 1, [2 ** 16, 1, 1]) == (
+        "the volume is too long for a distance map in micrometres: ((w - 1) * ux)^2 + ((h - 1) * uy)^2 + ((d - 1) * uz)^2 = "
+        "4611686018427387904 must stay below 2^62")
+    assert native.volume_distance_extent_error(2 ** 15 + 1, 1, 1, [2 ** 16 - 1, 1, 1]) == ""
+    msg = native.volume_distance_extent_error(3, 3, 3, [2 ** 31, 2 ** 31, 2 ** 31])
+    assert str(3 * (2 * 2 ** 31) ** 2) in msg
+    m = np.zeros((3, 3, 3), np.uint8)
+    for fn in (lambda: native.golden_volume_distance(m, [2 ** 31] * 3), lambda: native.golden_dilate3d_mm(m, [2 ** 31] * 3, 1),
+               lambda: native.golden_volume_thickness(m, [2 ** 31] * 3), lambda: native.volume_distance_words(m, [2 ** 31] * 3)):
+        with pytest.raises(ValueError, match="must stay below 2\\^62"):
+            fn()
+    for fn in (lambda: native.golden_volume_distance(m[0], [1000] * 3), lambda: native.golden_volume_distance(m, [0, 1, 1]),
+               lambda: native.golden_volume_distance(m, [1000] * 3, False, -1), lambda: native.golden_dilate3d_mm(m, [1000] * 3, -1)):
+        with pytest.raises(ValueError):
+            fn()
