@@ -1,5 +1,6 @@
 """K16 (--dilate-mm, --measure-volume-thickness) on the GPU against the golden model, everything compared with ==:
-  test_ops_equal_golden                 the three ops on every case of volume_distance_cases, both polarities, every cap
+  test_ops_equal_golden                 the three ops on every case of volume_distance_cases, both polarities, every cap;
+                                        near_extent's inverse mask too: a thickness of 4.32e18, just below 2^62
   test_margin_op_equals_map_threshold   ops.dilate_volume_mm == (ops.volume_distance <= r^2)
   test_op_refusals                      every ValueError of the ops
   test_pipeline_equals_golden           VolumePipeline(dilate_mm=R, ...) for R in {0, 1.2, 5}: the dilated mask, the
@@ -50,6 +51,10 @@ def test_ops_equal_golden(native, c):
         assert got.dtype == torch.bool
         assert np.array_equal(got.cpu().numpy(), native.golden_dilate3d_mm(c["mask"], um, r).astype(bool)), r
     assert nm.ops.volume_thickness(mask, um) == native.golden_volume_thickness(c["mask"], um)
+    if c["name"] == "near_extent":  # the inverse mask: 4.32e18 in the high half of the reduction's 64-bit shuffles
+        got = nm.ops.volume_thickness(~mask, um)
+        assert {k: got[k] for k in dc.NEAR_EXTENT_INVERSE_THICKNESS} == dc.NEAR_EXTENT_INVERSE_THICKNESS
+        assert got == native.golden_volume_thickness((1 - c["mask"]).astype(np.uint8), um)
     torch.cuda.synchronize()
 
 

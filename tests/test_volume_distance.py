@@ -189,9 +189,18 @@ def test_thickness_equals_the_map_and_the_reference(native, goldens, c):
                      "thickness_mm": None}
     if c["name"] == "two_cubes_tie":
         assert int((m & (g == t["inscribed_um2"])).sum()) > 1 and t["inscribed_at"] == [2, 2, 0]
+    inverse = None
+    if c["name"] == "near_extent":  # the inverse mask: 4.32e18, just below 2^62, at the last voxel of the raster
+        inverse = (1 - c["mask"]).astype(np.uint8)
+        ti = native.golden_volume_thickness(inverse, list(c["um"]))
+        assert {k: ti[k] for k in dc.NEAR_EXTENT_INVERSE_THICKNESS} == dc.NEAR_EXTENT_INVERSE_THICKNESS
+        assert ti["inscribed_um2"] == int(goldens[(c["name"], "foreground")].max()) > 2 ** 61
+        assert native.volume_thickness_words(inverse, list(c["um"])) == ti
     pytest.importorskip("scipy.ndimage")
     from nm03_capstone_project_amd.ops import reference
     assert t == reference.volume_thickness(c["mask"], c["um"])
+    if inverse is not None:
+        assert ti == reference.volume_thickness(inverse, c["um"])
 
 
 # ---- sidecar text ------------------------------------------------------------------------------------

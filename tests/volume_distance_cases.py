@@ -7,6 +7,10 @@ NO_DISTANCE = 2 ** 63 - 1
 POLARITIES = ("foreground", "background")
 ISO = (1000, 1000, 1000)
 COPRIME = (391, 703, 6500)
+NEAR_EXTENT_UM = (300_000_000, 600_000_000, 600_000_000)
+# the thickness of the INVERSE of near_extent's mask: the far corner (4, 2, 2), whose only background voxel is the
+# origin; 4.32e18 fills the high half of the 64-bit shuffles of the reduction
+NEAR_EXTENT_INVERSE_THICKNESS = {"inscribed_um2": 4_320_000_000_000_000_000, "inscribed_at": [4, 2, 2], "found": True}
 
 
 def _noise(shape, density, seed):
@@ -42,6 +46,8 @@ def all_cases():
     plane[3] = 1
     long_col = np.zeros((1, 300, 2), np.uint8)
     long_col[0, 0, 1] = 1
+    long_line = np.zeros((300, 1, 2), np.uint8)
+    long_line[299, 0, 1] = 1
     return [
         _case("worked_example", _points((5, 21, 21), [(10, 10, 2)]), (500, 500, 5000), (None, 0, 500, 5000, 5001, 700)),
         _case("width_70", _noise((3, 9, 70), 0.3, 1), ISO),
@@ -65,6 +71,11 @@ def all_cases():
         # more than 64 words per row: the rows pass looks at the row's words 64 at a time, and here the nearest set
         # word lies in the same group of 64 (row 0), in the group before (row 1) and in the group after (row 2)
         _case("row_of_66_words", _points((1, 3, 4200), [(5, 0, 0), (4100, 0, 0), (5, 1, 0), (4190, 2, 0)]), (300, 90000, 1000)),
+        # just below the extent limit: every axis spans 1.2e9 um < 2^31, the far corner lies at 4.32e18 < 2^62. The cap
+        # 2e9 drops that corner alone; 2^31 - 1 is the last cap that is squared, 2^31 the first that becomes 2^62
+        _case("near_extent", _points((3, 3, 5), [(0, 0, 0)]), NEAR_EXTENT_UM, (None, 0, 300_000_000, 2_000_000_000, 2 ** 31 - 1, 2 ** 31)),
+        # the planes pass searches 299 steps along z: the maximum, (299 * 800)^2 + 1000^2 = 57 217 640 000, at (0, 0, 0)
+        _case("long_plane_line", long_line, (1000, 1000, 800)),
     ]
 
 
