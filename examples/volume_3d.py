@@ -1,7 +1,7 @@
 """One DICOM series as a 3D volume on the MI355X: per-slice preprocessing, 6-connected 3D region
 growing and a 7×7×7 dilation (BASELINE config 5), checked against the golden 3D model.
 
-    python examples/volume_3d.py --series path/to/series_dir [--ball] [--measure] [--views DIR] [--mesh DIR] [--dilate-mm R]
+    python examples/volume_3d.py --series path/to/series_dir [--ball] [--measure] [--views DIR] [--mesh DIR] [--dilate-mm R [--compare-to-cube]]
 """
 import argparse
 import os
@@ -29,11 +29,20 @@ def main(argv=None):
     ap.add_argument("--dilate-mm", type=float, metavar="R",
                     help="dilate by a Euclidean margin of R mm in physical space (K16) instead of the 7x7x7 cube, and print "
                          "the voxel counts of both and the thickness of the dilated volume")
+    ap.add_argument("--compare-to-cube", action="store_true",
+                    help="with --dilate-mm: also score the margin's mask against the default 7x7x7 cube's (K17) and print "
+                         "Dice and the surface distances")
     a = ap.parse_args(argv)
     margin = a.dilate_mm is not None
+    if a.compare_to_cube and not margin:
+        ap.error("--compare-to-cube needs --dilate-mm R")
+    cube_mask = None
+    if a.compare_to_cube:  # the reference: a run with the default cube; `run` returns `dilated`, so it could be saved as well
+        cube_mask = nm.VolumePipeline(nm.PipelineConfig(se_shape=int(a.ball)), connectivity=6, dilation=7).run_series(a.series)["dilated"]
     vp = nm.VolumePipeline(nm.PipelineConfig(se_shape=int(a.ball)), connectivity=6, dilation=7, measure=a.measure or margin,
                            measure_lesions=int(a.measure), measure_diameters=a.measure, views=bool(a.views),
-                           mesh=bool(a.mesh), dilate_mm=a.dilate_mm, measure_thickness=margin)
+                           mesh=bool(a.mesh), dilate_mm=a.dilate_mm, measure_thickness=margin, compare_to=cube_mask,
+                           compare_reference="cube")
     res = vp.run_series(a.series)
     band = res["band"]
     g = nm.utils.series_geometry(a.series)
@@ -51,6 +60,14 @@ def main(argv=None):
                   f"{tuple(t['inscribed_at'])})")
         else:
             print("thickness: none (empty mask, or no background in the frame)")
+    if a.compare_to_cube:
+        import json
+        c = json.loads(res["compare_json"])
+        if c["found_ab"]:
+            print(f"margin against the cube: Dice {c['dice']:.4f}, Jaccard {c['jaccard']:.4f}, Hausdorff {c['hausdorff_mm']:.3f} mm, "
+                  f"HD95 {c['hd95_mm']:.3f} mm, ASSD {c['assd_mm']:.3f} mm ({c['surface_a']} and {c['surface_b']} surface voxels)")
+        else:
+            print(f"margin against the cube: {c['a_vox']} and {c['b_vox']} voxels, no surface distances (an empty mask)")
     if a.measure:
         import json
         m = json.loads(res["measure_json"])

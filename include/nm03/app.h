@@ -124,6 +124,12 @@ struct AppConfig {
   int64_t dilate_um = -1;
   double dilate_mm = 0;
   bool measure_volume_thickness = false;
+  // --volume-mask (3d): the dilated mask as <patient>/mask.mhd + mask.raw (MET_UCHAR 0 / 1, the series' spacing).
+  // --compare-to DIR (3d): the dilated mask scored against DIR/<patient>/mask.mhd (non-zero = set; an earlier
+  // output tree, or any tree laid out like one): <patient>/compare.json and <out>/comparisons.csv
+  // (nm03/volume_compare.h). Empty = off.
+  bool volume_mask = false;
+  std::string compare_to;
   bool volume_mesh = false;
   int volume_mesh_placement = kMeshCorner;
   int volume_mesh_format = kMeshPly;

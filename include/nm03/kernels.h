@@ -10,6 +10,7 @@
 #include "nm03/gpu_types.h"
 #include "nm03/measure.h"
 #include "nm03/pixel_math.h"
+#include "nm03/volume_compare.h"
 #include "nm03/volume_distance.h"
 #include "nm03/volume_mesh.h"
 #include "nm03/volume_views.h"
@@ -436,6 +437,31 @@ void launch_volume_thickness(const uint64_t* mask, const VolumeDistanceLayout& L
 // Loads K16's code object on the current device: only a VolumeRunner's first run that asks for a margin in
 // millimetres or the thickness, and the Python ops, load it.
 void preload_volume_distance();
+
+// K17 (k17_volume_compare.hip): the comparison of nm03/volume_compare.h between two bit volumes `a` and `b` of
+// one frame (d planes of h rows of ceil(w / 64) words, bits past the width tolerated). Twenty launches on
+// `stream`: init, the surfaces with the five counts, then per direction K16's launch_volume_distance of the other
+// surface (no cap), the sampling pass, two select / histogram pairs of the 11 + 11 + 10 bit radix select and the
+// launch that writes the directed record to `out` (device, pinned or host-mapped memory) with plain vector
+// stores. No cooperative launch, grid barrier, flag, look-back, spin, host round trip or allocation. `work`:
+// volume_compare_work_bytes of device memory (two surface volumes, 48 KiB of accumulators, 16 KiB of slots, the
+// i64 map and K16's own scratch: 18 bytes per voxel in all), no initialisation needed. `max_blocks`: a lower cap
+// on the workgroups of the sampling and histogram launches (0 = the default 1024); the record does not depend on
+// it. Throws DeviceError before any launch for a null buffer, a spacing below 1 and the extent rule.
+struct VolumeCompareLayout {
+  VolumeDistanceLayout dist;  // K16's layout of the same frame
+  uint32_t blocks = 0;        // 256-word blocks
+  size_t off_surface_a = 0, off_surface_b = 0, off_acc = 0, off_slots = 0, off_map = 0, off_dist = 0;  // byte offsets into `work`
+  size_t bytes = 0;
+};
+// Throws DeviceError for what volume_distance_layout refuses and for a volume of 2^32 voxels or more.
+VolumeCompareLayout volume_compare_layout(int w, int h, int d);
+size_t volume_compare_work_bytes(int w, int h, int d);
+void launch_volume_compare(const uint64_t* a, const uint64_t* b, const VolumeCompareLayout& L, const uint32_t um[3], void* work,
+                           VolumeCompare* out, hipStream_t stream, int max_blocks = 0);
+// Loads K17's code object on the current device: only a VolumeRunner's first run that asks for a comparison, and
+// the Python op, load it. K16's is loaded separately (preload_volume_distance).
+void preload_volume_compare();
 
 // K6: binary threshold lo ≤ x ≤ hi → u8 0/1 (in 16-byte aligned, out 4-byte aligned).
 void launch_threshold(const float* in, uint8_t* out, size_t n, float lo, float hi, hipStream_t stream);

@@ -12,6 +12,7 @@
 #include "nm03/comm.h"
 #include "nm03/engine.h"
 #include "nm03/measure.h"
+#include "nm03/volume_compare.h"
 #include "nm03/volume_distance.h"
 #include "nm03/volume_mesh.h"
 #include "nm03/volume_views.h"
@@ -73,6 +74,19 @@ struct VolumeResult {
   measure::Glcm texture;
   // VolumeParams::measure_thickness: the K16 record of the dilated volume.
   VolumeThickness thickness = {};
+  // VolumeParams::compare: the K17 record of the dilated volume (A) against the reference (B), and the GPU time
+  // of the reference upload and K17's launches (outside kernels_s and measure_s).
+  VolumeCompare compare = {};
+  double compare_s = 0;
+};
+
+// The reference mask of a comparison (VolumeParams::compare), in host memory, valid during run(): either `bits`
+// (d planes of h rows of ceil(w / 64) u64 words, K5's layout, bits past the width tolerated) or `mask` (w · h · d
+// bytes, non-zero = set, which the runner packs); `bits` wins when both are given.
+struct VolumeReference {
+  const uint64_t* bits = nullptr;
+  const uint8_t* mask = nullptr;
+  int w = 0, h = 0, d = 0;
 };
 
 struct VolumeExportStats {
@@ -120,6 +134,9 @@ struct VolumeParams {
   // With measure: also the thickness of the dilated volume (K16, VolumeThickness) at `spacing_um`, after K12's
   // launches, inside measure_s.
   bool measure_thickness = false;
+  // Not null: also compare the dilated volume with this reference mask of the same shape (K17,
+  // nm03/volume_compare.h VolumeCompare) at `spacing_um`, after every measure launch. Needs no `measure`.
+  const VolumeReference* compare = nullptr;
 };
 
 // Runs the 3D pipeline on `device`; copies masks back when `want_masks`. A VolumeRunner keeps
@@ -139,6 +156,11 @@ class VolumeRunner {
   // p.dilate_um ≥ 0 and p.measure_thickness share K16: its code object and its scratch (2 + 8 bytes per
   // voxel) come with the first run that asks for either and are kept and rebuilt with the volume shape. All
   // argument checks, the extent rule of nm03/volume_distance.h included, run before the run's first launch.
+  // p.compare: K17's code object (and K16's, whose map it uses), its work buffer (18 bytes per voxel), the
+  // reference's device words with their pinned staging, the pinned record and two events come with the first
+  // run that asks for it and are kept and rebuilt with the volume shape; its launches follow every measure
+  // launch. A reference without a buffer or of another shape and the extent rule throw std::invalid_argument
+  // before the run's first launch.
   VolumeResult run(const VolumeInput& v, const VolumeParams& p, bool want_masks);
   // After run() on the same volume: the 2·d exported JPEG files of the 3D cohort mode, in plane
   // order (original, processed), rendered and encoded on the GPU (K3/K4) from the volume still on
@@ -171,7 +193,7 @@ class VolumeRunner {
   // export_jpegs(slab, ...) then exports its planes. Masks (when requested) are the slab's.
   // p.measure, p.measure_lesions, p.measure_diameters, p.measure_intensity or p.measure_texture throws std::invalid_argument: components that cross slabs would
   // need a collective. p.dilate_um ≥ 0 and p.measure_thickness throw it too: a margin across slabs needs a
-  // halo of its reach.
+  // halo of its reach. p.compare throws it as well: the surface distances of a slab are not those of the volume.
   VolumeResult run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p, bool want_masks,
                         struct SlabStats* stats = nullptr);
 

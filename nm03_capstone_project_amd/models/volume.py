@@ -40,7 +40,14 @@ physical space (K16, nm03/volume_distance.h: { p : D_region(p) ≤ r² }, r = ll
 quantised to integer micrometres) instead of the cube / ball of `dilation` index steps; everything downstream
 reads that mask. With `measure_thickness=True` (needs `measure`) K16 also reports the largest ball inscribed in
 the dilated volume: the result gains `thickness` (inscribed_um2, inscribed_at, found, inscribed_radius_mm,
-thickness_mm) and `measure_json` carries the thickness keys after the texture keys."""
+thickness_mm) and `measure_json` carries the thickness keys after the texture keys.
+
+With `compare_to=B` (a [D, H, W] array of the volume's shape, non-zero = set) every run also scores its dilated mask
+A against B (K17, nm03/volume_compare.h): overlap counts, both surfaces and, in each direction, the largest, the
+summed and the 95th-percentile surface-to-surface distance in physical space. The result gains `compare` (the
+record's integers, keyed as compare.json), `compare_json` (the text of the CLI's compare.json, from the one native
+writer, with `compare_reference` as its `reference`) and `compare_s`. `run` returns `dilated` as it always does, so
+a caller can save it (native().mhd_write) and compare a later run against it. It needs no `measure`."""
 import numpy as np
 
 from .._native import native
@@ -58,7 +65,7 @@ class VolumePipeline:
                  measure_connectivity: int = 26, measure_lesions: int = 0, measure_intensity: bool = False, measure_texture: bool = False,
                  texture_levels: int = 32, measure_diameters: bool = False, views: bool = False, views_at="mask",
                  mesh: bool = False, mesh_placement: str = "corner", mesh_format: str = "ply", mesh_max_mb: int = 512,
-                 dilate_mm=None, measure_thickness: bool = False):
+                 dilate_mm=None, measure_thickness: bool = False, compare_to=None, compare_reference: str = ""):
         self.config = config or PipelineConfig()
         self.connectivity = connectivity
         self.dilation = dilation
@@ -109,6 +116,12 @@ class VolumePipeline:
             raise ValueError("measure_thickness needs measure=True")
         if (self.dilate_mm is not None or self.measure_thickness) and self.config.host_only:
             raise ValueError("the distance map is computed on the GPU: not available with host_only")
+        self.compare_to = None if compare_to is None else np.ascontiguousarray(np.asarray(compare_to) != 0, dtype=np.uint8)
+        self.compare_reference = str(compare_reference)
+        if self.compare_to is not None and self.compare_to.ndim != 3:
+            raise ValueError("compare_to must be [D, H, W]")
+        if self.compare_to is not None and self.config.host_only:
+            raise ValueError("the comparison runs on the GPU: not available with host_only")
         self._runners = {}  # device -> native VolumeRunner (buffers/stream reused across volumes)
 
     def default_seeds(self, volume):
@@ -130,7 +143,18 @@ class VolumePipeline:
             x, y, z = self.views_at
             if not (0 <= x < w and 0 <= y < h and 0 <= z < d):
                 raise ValueError(f"views_at: the point ({x}, {y}, {z}) lies outside the volume of {w} x {h} x {d}")
-        if not self.measure and meta is None and self.dilate_mm is None:
+        if self.compare_to is not None:
+            if self.compare_to.shape != vol.shape:  # before anything is launched
+                raise ValueError(f"compare_to: shape mismatch: the reference is {self.compare_to.shape}, the volume {vol.shape}")
+            res = runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s, measure=self.measure,
+                             measure_connectivity=self.measure_connectivity, spacing=[float(v) for v in spacing],
+                             spacing_z_source=str(spacing_z_source), measure_lesions=self.measure_lesions,
+                             measure_intensity=self.measure_intensity, measure_texture=self.measure_texture,
+                             texture_levels=self.texture_levels, measure_diameters=self.measure_diameters,
+                             dilate_um=-1 if self.dilate_mm is None else native().dilate_mm_to_um(self.dilate_mm),
+                             measure_thickness=self.measure_thickness, compare_to=self.compare_to,
+                             compare_reference=self.compare_reference, **_meta_args(meta))
+        elif not self.measure and meta is None and self.dilate_mm is None:
             res = runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s)
         elif self.dilate_mm is not None or self.measure_thickness:
             res = runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s, measure=self.measure,
@@ -171,7 +195,7 @@ class VolumePipeline:
         (utils.series_geometry) and the first slice's storage format go with it."""
         from ..utils.dicom import read_series, series_geometry
         vol, slices = read_series(series_dir)
-        if not self.measure and not self.views and not self.mesh and self.dilate_mm is None:
+        if not self.measure and not self.views and not self.mesh and self.dilate_mm is None and self.compare_to is None:
             return self.run(vol, seeds=seeds, device=device)
         g = series_geometry(series_dir)
         return self.run(vol, seeds=seeds, device=device, spacing=(g["spacing_x"], g["spacing_y"], g["spacing_z"]),

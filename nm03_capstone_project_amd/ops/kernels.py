@@ -679,3 +679,31 @@ def volume_thickness(mask, spacing_um=(1000, 1000, 1000)):
     d, h, w, um = _distance_args(mask, spacing_um)
     bits = pack_bits(mask.bool()).contiguous()
     return native().k_volume_distance(bits.data_ptr(), w, h, d, um, "thickness", True, -1, 0, _stream())
+
+
+def compare_volumes(a, b, spacing_um=(1000, 1000, 1000), max_blocks=None):
+    """Overlap and surface distances between two volume masks of one shape (K17, nm03/volume_compare.h) → the dict of
+    integers: a_vox, b_vox, tp_vox, fp_vox, fn_vox, surface_a, surface_b (voxels with an open 6-face, outside the
+    frame counting as open) and per direction n, max_um2, worst [x, y, z], sum_um, p95_um and found, suffixed _ab
+    (from S(a) to S(b)) and _ba. Distances are surface to surface, centre to centre, in physical space:
+    max_um2 is the largest squared distance in um², sum_um and p95_um are over ⌊√D⌋ in whole micrometres, the
+    percentile by nearest rank. A direction is found when both surfaces are non-empty; otherwise its integers are
+    0 and worst is [−1, −1, −1]. native().volume_compare_to_json gives the sidecar text with the derived values.
+
+    `a`, `b`: bool CUDA tensors [D, H, W]; `spacing_um` is (ux, uy, uz) in integer micrometres. Twenty launches,
+    K16's distance map twice among them. `max_blocks` lowers the cap on the workgroups of the sampling launches
+    (the result does not depend on it)."""
+    d, h, w, um = _distance_args(a, spacing_um, "a")
+    if not hasattr(b, "is_cuda") or not b.is_cuda:
+        raise ValueError("b must be a CUDA (HIP) tensor")
+    if tuple(b.shape) != tuple(a.shape):
+        raise ValueError("both masks must be [D, H, W] of one shape")
+    if b.device != a.device:
+        raise ValueError("both masks must be on one device")
+    if w * h * d >= 2 ** 32:
+        raise ValueError("a volume of 2^32 voxels or more cannot be compared")
+    if max_blocks is not None and int(max_blocks) < 1:
+        raise ValueError("max_blocks must be at least 1")
+    wa = pack_bits(a.bool()).contiguous()
+    wb = pack_bits(b.bool()).contiguous()
+    return native().k_volume_compare(wa.data_ptr(), wb.data_ptr(), w, h, d, um, int(max_blocks or 0), _stream())

@@ -846,3 +846,46 @@ def volume_thickness(mask, spacing_um=(1000, 1000, 1000)):
     z, y, x = (int(a) for a in np.unravel_index(int(np.argmax(v)), v.shape))  # argmax: the first in raster order
     r = math.sqrt(float(best)) / 1000.0
     return {"inscribed_um2": best, "inscribed_at": [x, y, z], "found": True, "inscribed_radius_mm": r, "thickness_mm": 2.0 * r}
+
+
+def volume_surface(mask):
+    """S(M) of nm03/volume_compare.h: the voxels of M with an open 6-face, outside the frame counting as open —
+    M ^ binary_erosion(M, generate_binary_structure(3, 1)) → bool array."""
+    from scipy import ndimage
+    m = _distance_set(mask, "foreground")
+    return m ^ ndimage.binary_erosion(m, ndimage.generate_binary_structure(3, 1))
+
+
+def _compare_directed(s_from, s_to, spacing_um, tag, out):
+    import numpy as np
+    found = bool(s_from.any() and s_to.any())
+    out["found" + tag] = found
+    if not found:
+        out.update({"n" + tag: 0, "max_um2" + tag: 0, "worst" + tag: [-1, -1, -1], "sum_um" + tag: 0, "p95_um" + tag: 0})
+        return
+    dist = volume_distance(s_to, spacing_um, "foreground")  # SciPy for indices only; d² recomputed in int64
+    dv = dist[s_from]  # raster order
+    keys = np.sort(np.array([math.isqrt(int(v)) for v in dv], dtype=np.int64))
+    n = int(keys.size)
+    first = int(np.argmax(dv))  # the first in raster order at the maximum
+    z, y, x = (int(c[first]) for c in np.nonzero(s_from))
+    out.update({"n" + tag: n, "max_um2" + tag: int(dv.max()), "worst" + tag: [x, y, z], "sum_um" + tag: int(keys.sum()),
+                "p95_um" + tag: int(keys[(95 * n + 99) // 100 - 1])})
+
+
+def compare_volumes(a, b, spacing_um=(1000, 1000, 1000)):
+    """Reference of ops.compare_volumes / native.golden_compare_volumes on two [D, H, W] masks (arrays or CPU
+    tensors) → the same dict of integers. SciPy's erosion gives the surfaces; distance_transform_edt is used for
+    indices only (volume_distance above recomputes d² in int64, no float of SciPy's is compared); math.isqrt and
+    np.sort do the rest."""
+    import numpy as np
+    ma, mb = _distance_set(a, "foreground"), _distance_set(b, "foreground")
+    if ma.shape != mb.shape:
+        raise ValueError("both masks must be [D, H, W] of one shape")
+    tp = int((ma & mb).sum())
+    out = {"a_vox": int(ma.sum()), "b_vox": int(mb.sum()), "tp_vox": tp, "fp_vox": int(ma.sum()) - tp, "fn_vox": int(mb.sum()) - tp}
+    sa, sb = volume_surface(ma), volume_surface(mb)
+    out["surface_a"], out["surface_b"] = int(sa.sum()), int(sb.sum())
+    _compare_directed(sa, sb, spacing_um, "_ab", out)
+    _compare_directed(sb, sa, spacing_um, "_ba", out)
+    return out

@@ -231,3 +231,36 @@ def read_volume_mesh(path):
     quads = np.concatenate([tri[0::2], tri[1::2, 2:3]], axis=1) if nf else np.zeros((0, 4), dtype=np.int32)
     return {"vertices": verts, "triangles": tri, "quads": quads.astype(np.int32),
             "comments": [ln[len("comment "):] for ln in lines if ln.startswith("comment ")]}
+
+
+def read_volume_comparisons(out_dir):
+    """Rows of <out_dir>/comparisons.csv (written by the 3D CLI with --compare-to) as dicts keyed by the header:
+    one per patient in plan order. `status` is "ok", "no_reference" (the reference tree has no mask for the
+    patient) or "shape_mismatch"; the two latter leave every field None. Integer columns come back as int
+    (arrays flattened: compare_spacing_um_x / _y / _z, worst_ab_x …), `reference` as text, the derived ones
+    (dice … assd_mm) as float."""
+    import csv
+    import os
+    floats = {"dice", "jaccard", "sensitivity", "precision", "volume_a_mm3", "volume_b_mm3", "volume_diff_mm3", "hausdorff_mm",
+              "hd95_mm", "msd_ab_mm", "msd_ba_mm", "assd_mm"}
+    text = {"patient", "status"}
+    rows = []
+    with open(os.path.join(out_dir, "comparisons.csv"), newline="") as f:
+        for r in csv.DictReader(f):
+            rows.append({k: v if k in text else None if v == "" else v if k == "reference" else float(v) if k in floats else int(v)
+                         for k, v in r.items()})
+    return rows
+
+
+def read_volume_mask(path):
+    """The mask.mhd the 3D CLI writes with --volume-mask (`path` is the file or the patient directory that holds
+    it) → (uint8 array [D, H, W] of 0 / 1, (sx, sy, sz) in mm). Non-zero means set, as --compare-to reads it."""
+    import os
+
+    import numpy as np
+    if os.path.isdir(path):
+        path = os.path.join(path, "mask.mhd")
+    arr, spacing = native().mhd_read(path)
+    if arr.ndim == 2:
+        arr = arr[None]
+    return (np.asarray(arr) != 0).astype(np.uint8), tuple(float(v) for v in spacing)

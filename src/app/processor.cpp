@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <filesystem>
 #include <fstream>
 #include <iomanip>
 #include <iostream>
@@ -103,6 +104,12 @@ void usage(const std::string& which) {
             << "  --measure-volume-thickness  3d: --measure-volume plus the radius of the largest ball inscribed in the\n"
             << "                         dilated volume and the thickness, twice that: keys in the sidecar, columns in\n"
             << "                         <out>/volumes.csv (not with --split-volume)\n"
+            << "  --volume-mask          3d: also write each patient's dilated mask as <patient>/mask.mhd and mask.raw\n"
+            << "                         (MET_UCHAR 0 / 1 at the series' spacing; needs --mode 3d; not with --split-volume)\n"
+            << "  --compare-to DIR       3d: score each patient's dilated mask against DIR/<patient>/mask.mhd (an earlier\n"
+            << "                         --volume-mask tree; non-zero = set): Dice, Jaccard, the Hausdorff distance, its 95th\n"
+            << "                         percentile and the mean surface distances in <patient>/compare.json and\n"
+            << "                         <out>/comparisons.csv (needs --mode 3d; not with --split-volume; DIR must not be --out)\n"
             << "  --mode 2d|3d           3d: whole series as a volume (SRG 6-conn + cube dilation)\n"
             << "  --split-volume         3d: each volume split into z-slabs over all ranks (halo exchange)\n"
             << "  --input FILE           test_pipeline: slice to process\n"
@@ -350,6 +357,14 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
     }
     else if (a == "--measure-volume-thickness") c.measure_volume_thickness = true;
     else if (a == "--volume-mesh") c.volume_mesh = true;
+    else if (a == "--volume-mask") c.volume_mask = true;
+    else if (a == "--compare-to") {
+      c.compare_to = val();
+      if (c.compare_to.empty()) {
+        std::cerr << "--compare-to needs a directory" << std::endl;
+        std::exit(2);
+      }
+    }
     else if (a == "--volume-mesh-placement") {
       const std::string v = val();
       if (!mesh::parse_placement(v, &c.volume_mesh_placement)) {
@@ -522,6 +537,38 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
                  "get the mesh, or --volume-mesh to split the volume)"
               << std::endl;
     std::exit(2);
+  }
+  if (c.volume_mask && c.mode != "3d") {
+    std::cerr << "--volume-mask needs --mode 3d" << std::endl;
+    std::exit(2);
+  }
+  if (c.volume_mask && c.split_volume) {
+    std::cerr << "--volume-mask is not available with --split-volume: no rank holds the whole mask (drop --split-volume to "
+                 "get the mask, or --volume-mask to split the volume)"
+              << std::endl;
+    std::exit(2);
+  }
+  if (!c.compare_to.empty() && c.mode != "3d") {
+    std::cerr << "--compare-to needs --mode 3d" << std::endl;
+    std::exit(2);
+  }
+  if (!c.compare_to.empty() && c.split_volume) {
+    std::cerr << "--compare-to is not available with --split-volume: the surface distances of a slab are not those of the "
+                 "volume (drop --split-volume to get the comparison, or --compare-to to split the volume)"
+              << std::endl;
+    std::exit(2);
+  }
+  if (!c.compare_to.empty()) {  // the output directory is wiped before the reference could be read
+    std::error_code ec1, ec2;
+    // "" appended: "o", "o/" and "o/." all end in one separator after the normalisation
+    const std::filesystem::path ref = (std::filesystem::weakly_canonical(c.compare_to, ec1) / "").lexically_normal();
+    const std::filesystem::path out = (std::filesystem::weakly_canonical(c.out_dir, ec2) / "").lexically_normal();
+    if (!ec1 && !ec2 && ref == out) {
+      std::cerr << "--compare-to " << c.compare_to << " is the output directory, which is wiped before the reference could be "
+                   "read: give another --out"
+                << std::endl;
+      std::exit(2);
+    }
   }
   if (c.engine.render.overlay && c.mode == "3d") {
     std::cerr << "--overlay is not available with --mode 3d" << std::endl;

@@ -52,6 +52,7 @@ int main(int argc, char** argv) {
   int64_t dilate_um = -1;          // volume: the margin of --dilate-mm R (K16) in place of the cube / ball, inside kernels_s
   double dilate_mm = 0;
   bool measure_volume_thickness = false;  // volume with --measure-volume: also K16's thickness, inside measure_s
+  bool compare = false;  // volume: also K17 (the dilated volume against the run's own undilated region), outside kernels_s and measure_s
   int mesh_placement = nm03::kMeshCorner;
   uint64_t mesh_max_mb = nm03::mesh::kDefaultMaxMb;
   for (int i = 1; i < argc; ++i) {
@@ -103,6 +104,7 @@ int main(int argc, char** argv) {
       dilate_um = nm03::measure::dilate_mm_to_um(dilate_mm);
     }
     else if (a == "--measure-volume-thickness") measure_volume_thickness = true;
+    else if (a == "--compare") compare = true;
     else if (a == "--volume-views") volume_views = true;
     else if (a == "--volume-mesh") volume_mesh = true;
     else if (a == "--volume-mesh-placement") {
@@ -129,6 +131,10 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (measure_volume_thickness) measure_volume = true;
+  if (compare && (config != "volume" || ec.host_only)) {
+    std::cerr << "--compare needs --config volume and the GPU (not --host-only)" << std::endl;
+    return 2;
+  }
   if (volume_views && (config != "volume" || ec.host_only)) {
     std::cerr << "--volume-views needs --config volume and the GPU (not --host-only)" << std::endl;
     return 2;
@@ -243,8 +249,19 @@ int main(int argc, char** argv) {
       if (dilate_um >= 0 || measure_volume_thickness)
         nm03::measure::volume_spacing_um((double)v.spacing_x, (double)v.spacing_y, v.spacing_z, vp.spacing_um);
       nm03::VolumeRunner runner(ec.device);
+      // --compare: the reference is this run's own undilated region, so no file is needed
+      std::vector<uint8_t> compare_mask;
+      nm03::VolumeReference compare_ref;
+      if (compare) {
+        compare_mask = runner.run(v, vp, true).region;
+        compare_ref.mask = compare_mask.data();
+        compare_ref.w = v.w, compare_ref.h = v.h, compare_ref.d = v.d;
+        nm03::measure::volume_spacing_um((double)v.spacing_x, (double)v.spacing_y, v.spacing_z, vp.spacing_um);
+        vp.compare = &compare_ref;
+      }
       for (int w = 0; w < warmup; ++w) runner.run(v, vp, false);
-      double ks = 0, ms = 0;
+      double ks = 0, ms = 0, cs = 0;
+      nm03::VolumeCompare vc = {};
       int sweeps = 0;
       nm03::VolumeMeasure vm = {};
       size_t lesions = 0;
@@ -257,6 +274,8 @@ int main(int argc, char** argv) {
         auto r = runner.run(v, vp, false);
         ks += r.kernels_s;
         ms += r.measure_s;
+        cs += r.compare_s;
+        vc = r.compare;
         sweeps = r.sweeps;
         vm = r.measure;
         vi = r.intensity;
@@ -267,6 +286,7 @@ int main(int argc, char** argv) {
         lesion0_major_um2 = r.diameters.empty() ? 0 : r.diameters[0].major_um2;
       }
       const double dt = now_s() - t0;
+      vp.compare = nullptr;  // the comparison is timed above alone
       // + the GPU export of every plane (render + JPEG, both images), as the 3D CLI does
       nm03::VolumeExportStats xs;
       for (int w = 0; w < warmup; ++w) runner.export_jpegs(v, vp, ec.render);
@@ -331,6 +351,12 @@ int main(int argc, char** argv) {
       if (measure_texture)
         std::cout << ", \"texture\": true, \"texture_levels\": " << texture_levels << ", \"glcm_pairs\": " << glcm_pairs;
       if (dilate_um >= 0) std::cout << ", \"dilate_mm\": " << dilate_mm << ", \"dilate_um\": " << dilate_um;
+      if (compare) {
+        const nm03::compare::Derived dv = nm03::compare::derive(vc, vp.spacing_um);
+        std::cout << ", \"compare_ms_per_volume\": " << cs * 1e3 / steps << ", \"compare_surface_a\": " << vc.surface_a
+                  << ", \"compare_surface_b\": " << vc.surface_b << ", \"compare_dice\": " << dv.dice
+                  << ", \"compare_hausdorff_mm\": " << dv.hausdorff_mm << ", \"compare_hd95_mm\": " << dv.hd95_mm;
+      }
       if (measure_volume_thickness)
         std::cout << ", \"thickness\": true, \"inscribed_um2\": " << vt.inscribed_um2
                   << ", \"thickness_mm\": " << 2.0 * nm03::measure::inscribed_radius_mm(vt);

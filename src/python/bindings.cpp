@@ -34,6 +34,8 @@
 #include "nm03/synth.h"
 #include "nm03/texture_core.h"
 #include "nm03/volume.h"
+#include "nm03/volume_compare.h"
+#include "nm03/volume_compare_core.h"
 #include "nm03/volume_slabs.h"
 
 namespace py = pybind11;
@@ -532,6 +534,57 @@ void distance_args(const py::array& mask, const std::vector<int64_t>& spacing_um
   spacing_um_from(spacing_um, um);
 }
 
+// The integers of a comparison record (nm03/volume_compare.h VolumeCompare) as a dict, keyed as compare.json.
+py::dict volume_compare_dict(const VolumeCompare& c) {
+  py::dict d;
+  d["a_vox"] = c.a_vox, d["b_vox"] = c.b_vox, d["tp_vox"] = c.tp_vox, d["fp_vox"] = c.fp_vox, d["fn_vox"] = c.fn_vox;
+  d["surface_a"] = c.surface_a, d["surface_b"] = c.surface_b;
+  const VolumeCompareDirected* dirs[2] = {&c.ab, &c.ba};
+  const char* tag[2] = {"_ab", "_ba"};
+  for (int i = 0; i < 2; ++i) {
+    const VolumeCompareDirected& r = *dirs[i];
+    const std::string t = tag[i];
+    py::list at;
+    for (int k = 0; k < 3; ++k) at.append(r.worst[k]);
+    d[py::str("n" + t)] = r.n;
+    d[py::str("max_um2" + t)] = r.max_um2;
+    d[py::str("worst" + t)] = at;
+    d[py::str("sum_um" + t)] = r.sum_um;
+    d[py::str("p95_um" + t)] = r.p95_um;
+    d[py::str("found" + t)] = r.found != 0;
+  }
+  return d;
+}
+
+VolumeCompare volume_compare_from(const py::dict& d) {
+  VolumeCompare c{};
+  c.a_vox = d["a_vox"].cast<uint64_t>(), c.b_vox = d["b_vox"].cast<uint64_t>(), c.tp_vox = d["tp_vox"].cast<uint64_t>();
+  c.fp_vox = d["fp_vox"].cast<uint64_t>(), c.fn_vox = d["fn_vox"].cast<uint64_t>();
+  c.surface_a = d["surface_a"].cast<uint64_t>(), c.surface_b = d["surface_b"].cast<uint64_t>();
+  VolumeCompareDirected* dirs[2] = {&c.ab, &c.ba};
+  const char* tag[2] = {"_ab", "_ba"};
+  for (int i = 0; i < 2; ++i) {
+    VolumeCompareDirected& r = *dirs[i];
+    const std::string t = tag[i];
+    r.n = d[py::str("n" + t)].cast<uint32_t>();
+    r.max_um2 = d[py::str("max_um2" + t)].cast<uint64_t>();
+    const std::vector<int> at = d[py::str("worst" + t)].cast<std::vector<int>>();
+    if (at.size() != 3) throw std::invalid_argument("worst must be [x, y, z]");
+    for (int k = 0; k < 3; ++k) r.worst[k] = at[(size_t)k];
+    r.sum_um = d[py::str("sum_um" + t)].cast<uint64_t>();
+    r.p95_um = d[py::str("p95_um" + t)].cast<uint32_t>();
+    r.found = d[py::str("found" + t)].cast<bool>() ? 1 : 0;
+  }
+  return c;
+}
+
+// The two masks of the comparison bindings: [D, H, W] of one shape.
+void compare_args(const py::array& a, const py::array& b, const std::vector<int64_t>& spacing_um, uint32_t um[3]) {
+  distance_args(a, spacing_um, um);
+  if (b.ndim() != 3 || b.shape(0) != a.shape(0) || b.shape(1) != a.shape(1) || b.shape(2) != a.shape(2))
+    throw std::invalid_argument("both masks must be [D, H, W] of one shape");
+}
+
 void check_max_lesions(int n) {
   if (n < 1 || n > kMaxVolumeLesions)
     throw std::invalid_argument("max_lesions must be 1.." + std::to_string(kMaxVolumeLesions));
@@ -565,7 +618,23 @@ struct VolumeMeta {
   int texture_levels = 32;
   int64_t dilate_um = -1;  // ≥ 0: the margin in micrometres in place of the cube / ball
   bool measure_thickness = false;
+  // VolumeRunner.run(compare_to=…): the reference mask [D, H, W] of a comparison and the name compare_json carries.
+  bool compare = false;
+  std::vector<uint8_t> compare_mask;
+  int compare_shape[3] = {0, 0, 0};  // d, h, w
+  std::string compare_reference;
 };
+
+// compare_to of the runner bindings: None, or a [D, H, W] array (non-zero = set).
+void compare_to_from(const py::object& o, const std::string& reference, VolumeMeta& mt) {
+  if (o.is_none()) return;
+  const auto a = o.cast<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>>();
+  if (a.ndim() != 3) throw std::invalid_argument("compare_to must be [D, H, W]");
+  mt.compare = true;
+  mt.compare_mask.assign(a.data(), a.data() + a.size());
+  for (int k = 0; k < 3; ++k) mt.compare_shape[k] = (int)a.shape(k);
+  mt.compare_reference = reference;
+}
 
 void apply_meta(const VolumeMeta& mt, VolumeInput& v) {
   if (mt.spacing.size() != 3) throw std::invalid_argument("spacing must be (sx, sy, sz)");
@@ -756,8 +825,14 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
     vp.texture_levels = meta->texture_levels;
     vp.dilate_um = meta->dilate_um;
     vp.measure_thickness = meta->measure_thickness;
-    if (vp.dilate_um >= 0 || vp.measure_thickness)
+    if (vp.dilate_um >= 0 || vp.measure_thickness || meta->compare)
       measure::volume_spacing_um((double)v.spacing_x, (double)v.spacing_y, v.spacing_z, vp.spacing_um);
+  }
+  VolumeReference ref;
+  if (meta && meta->compare) {
+    ref.mask = meta->compare_mask.data();
+    ref.d = meta->compare_shape[0], ref.h = meta->compare_shape[1], ref.w = meta->compare_shape[2];
+    vp.compare = &ref;
   }
   VolumeResult r;
   {
@@ -799,6 +874,11 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
                                                         (int)r.diameters.size(), vp.spacing_um);
     }
     d["measure_s"] = r.measure_s;
+  }
+  if (vp.compare) {
+    d["compare"] = volume_compare_dict(r.compare);
+    d["compare_json"] = compare::to_json(r.compare, v.w, v.h, v.d, vp.spacing_um, meta->compare_reference);
+    d["compare_s"] = r.compare_s;
   }
   return d;
 }
@@ -1955,8 +2035,10 @@ PYBIND11_MODULE(_nm03, m) {
              const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_connectivity,
              const std::vector<double>& spacing, const std::string& spacing_z_source, const std::string& type,
              int stored_bits, float slope, float intercept, int measure_lesions, bool measure_intensity, bool measure_texture,
-             int texture_levels, bool measure_diameters, int64_t dilate_um, bool measure_thickness) {
+             int texture_levels, bool measure_diameters, int64_t dilate_um, bool measure_thickness, const py::object& compare_to,
+             const std::string& compare_reference) {
             VolumeMeta mt;
+            compare_to_from(compare_to, compare_reference, mt);
             mt.measure_diameters = measure_diameters;
             mt.dilate_um = dilate_um;
             mt.measure_thickness = measure_thickness;
@@ -1982,7 +2064,7 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f, py::arg("intercept") = 0.f,
           py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false, py::arg("measure_texture") = false,
           py::arg("texture_levels") = 32, py::arg("measure_diameters") = false, py::arg("dilate_um") = -1,
-          py::arg("measure_thickness") = false)
+          py::arg("measure_thickness") = false, py::arg("compare_to") = py::none(), py::arg("compare_reference") = "")
       .def(
           "export_views",
           // After run() on a volume of this shape: the views of nm03/volume_views.h from the volume still on
@@ -2047,9 +2129,10 @@ PYBIND11_MODULE(_nm03, m) {
           [](VolumeRunner& self, Comm& comm, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> slab,
              int z0, int depth, const PipelineParams& p, int connectivity, int dilation,
              const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_lesions, bool measure_intensity,
-             bool measure_texture, bool measure_diameters, int64_t dilate_um, bool measure_thickness) {
+             bool measure_texture, bool measure_diameters, int64_t dilate_um, bool measure_thickness, const py::object& compare_to) {
             SlabStats st;
             VolumeMeta mt;
+            compare_to_from(compare_to, "", mt);  // refused by run_slab
             mt.measure_diameters = measure_diameters;
             mt.dilate_um = dilate_um;  // refused by run_slab, as the measurements are
             mt.measure_thickness = measure_thickness;
@@ -2069,7 +2152,8 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("connectivity") = 6, py::arg("dilation") = 7,
           py::arg("seeds") = std::vector<std::tuple<int, int, int>>{}, py::arg("measure") = false,
           py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false, py::arg("measure_texture") = false,
-          py::arg("measure_diameters") = false, py::arg("dilate_um") = -1, py::arg("measure_thickness") = false);
+          py::arg("measure_diameters") = false, py::arg("dilate_um") = -1, py::arg("measure_thickness") = false,
+          py::arg("compare_to") = py::none());
 
   // One-process rehearsal of the z-slab decomposition: `nranks` threads, each with its own
   // VolumeRunner (stream) on `device`, talking over loopback comms — the device-resident exchange
@@ -3195,6 +3279,121 @@ PYBIND11_MODULE(_nm03, m) {
     return volume_thickness_dict(*h_rec);
   }, py::arg("bits"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_um"), py::arg("mode") = "map",
      py::arg("to_background") = false, py::arg("cap_um") = -1, py::arg("out") = 0, py::arg("stream") = 0);
+
+  // ---- K17: the comparison of nm03/volume_compare.h ------------------------------------------------------
+  // The golden comparison (plain loops, a sort) of two masks ([D, H, W], non-zero = set) → the dict of integers.
+  m.def(
+      "golden_compare_volumes",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> b,
+         const std::vector<int64_t>& spacing_um) {
+        uint32_t um[3];
+        compare_args(a, b, spacing_um, um);
+        const int d = (int)a.shape(0), h = (int)a.shape(1), w = (int)a.shape(2);
+        const std::vector<uint8_t> ma = from_np<uint8_t>(a), mb = from_np<uint8_t>(b);
+        VolumeCompare c;
+        {
+          py::gil_scoped_release nogil;
+          c = golden::compare_volumes(ma, mb, w, h, d, um);
+        }
+        return volume_compare_dict(c);
+      },
+      py::arg("a"), py::arg("b"), py::arg("spacing_um") = std::vector<int64_t>{1000, 1000, 1000});
+  // S(M) of the golden model → uint8 [D, H, W].
+  m.def("golden_volume_surface", [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> mask) {
+    if (mask.ndim() != 3) throw std::invalid_argument("mask must be [D, H, W]");
+    const int d = (int)mask.shape(0), h = (int)mask.shape(1), w = (int)mask.shape(2);
+    return to_np<uint8_t>(golden::volume_surface(from_np<uint8_t>(mask), w, h, d), {d, h, w});
+  });
+  // The comparison from the K17 kernels' functions run on the host (measure::volume_compare_words). `junk`: the
+  // storage bits past the width are set in both inputs. With `surfaces` the result is (dict, S(A), S(B)), the
+  // surfaces as the int64 words [D, H, ceil(W / 64)] the surface launch stores.
+  m.def(
+      "volume_compare_words",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> b,
+         const std::vector<int64_t>& spacing_um, bool junk, bool surfaces) -> py::object {
+        uint32_t um[3];
+        compare_args(a, b, spacing_um, um);
+        const int d = (int)a.shape(0), h = (int)a.shape(1), w = (int)a.shape(2), wpr = (w + 63) / 64;
+        std::vector<uint64_t> wa = pack_volume(a), wb = pack_volume(b);
+        if (junk)
+          for (size_t r = 0; r < (size_t)d * h; ++r) {
+            wa[r * wpr + wpr - 1] |= ~row_word_mask(wpr - 1, w);
+            wb[r * wpr + wpr - 1] |= ~row_word_mask(wpr - 1, w);
+          }
+        std::vector<uint64_t> sa(wa.size()), sb(wb.size());
+        VolumeCompare c;
+        {
+          py::gil_scoped_release nogil;
+          c = measure::volume_compare_words(wa.data(), wb.data(), w, h, d, wpr, um, sa.data(), sb.data());
+        }
+        if (!surfaces) return volume_compare_dict(c);
+        std::vector<int64_t> ia(sa.begin(), sa.end()), ib(sb.begin(), sb.end());
+        return py::make_tuple(volume_compare_dict(c), to_np<int64_t>(ia, {d, h, wpr}), to_np<int64_t>(ib, {d, h, wpr}));
+      },
+      py::arg("a"), py::arg("b"), py::arg("spacing_um") = std::vector<int64_t>{1000, 1000, 1000}, py::arg("junk") = false,
+      py::arg("surfaces") = false);
+  // compare.json of a comparison dict: the one writer (compare::to_json).
+  m.def("volume_compare_to_json", [](const py::dict& c, int w, int h, int d, const std::vector<int64_t>& spacing_um, const std::string& reference) {
+    uint32_t um[3];
+    spacing_um_from(spacing_um, um);
+    return compare::to_json(volume_compare_from(c), w, h, d, um, reference);
+  }, py::arg("compare"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_um"), py::arg("reference") = "");
+  m.def("volume_compare_csv_header", []() { return compare::csv_header(); });
+  m.def("volume_compare_csv_fields", [](const py::dict& c, int w, int h, int d, const std::vector<int64_t>& spacing_um, const std::string& reference) {
+    uint32_t um[3];
+    spacing_um_from(spacing_um, um);
+    return compare::csv_fields(volume_compare_from(c), w, h, d, um, reference);
+  }, py::arg("compare"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_um"), py::arg("reference") = "");
+  // ⌊√v⌋ of the shared core (vcmp::isqrt_um), 0 ≤ v < 2^62.
+  m.def("volume_compare_isqrt", [](int64_t v) {
+    if (v < 0 || v >= (1ll << 62)) throw std::invalid_argument("0 <= v < 2^62");
+    return vcmp::isqrt_um(v);
+  });
+
+  // K17 alone on two device bit volumes [d][h][ceil(w/64)] (int64 words) → the dict of integers. The work buffer
+  // is this op's own; synchronous on `stream`. `max_blocks`: see launch_volume_compare.
+  m.def("k_volume_compare", [](uintptr_t a, uintptr_t b, int w, int h, int d, const std::vector<int64_t>& spacing_um, int max_blocks,
+                               uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    if (w <= 0 || h <= 0 || d <= 0) throw std::invalid_argument("empty volume");
+    if (!a || !b) throw std::invalid_argument("null buffer");
+    if (max_blocks < 0) throw std::invalid_argument("max_blocks must not be negative");
+    uint32_t um[3];
+    spacing_um_from(spacing_um, um);
+    const std::string ext = measure::volume_distance_extent_error(w, h, d, um);
+    if (!ext.empty()) throw std::invalid_argument(ext);
+    {
+      // K16's and K17's code objects, loaded on the current device before this op's first launch there.
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_volume_distance();
+        gpu::preload_volume_compare();
+        preloaded.push_back(dev);
+      }
+    }
+    const gpu::VolumeCompareLayout L = gpu::volume_compare_layout(w, h, d);
+    struct DevMem {
+      void* p = nullptr;
+      ~DevMem() {
+        if (p) (void)hipFree(p);
+      }
+    } work;
+    gpu::check_hip(hipMalloc(&work.p, L.bytes), "hipMalloc compare work");
+    VolumeCompare* h_rec = nullptr;
+    gpu::check_hip(hipHostMalloc((void**)&h_rec, sizeof(VolumeCompare), hipHostMallocDefault), "hipHostMalloc compare");
+    struct Pinned {
+      void* p;
+      ~Pinned() { (void)hipHostFree(p); }
+    } pinned{h_rec};
+    gpu::launch_volume_compare((const uint64_t*)a, (const uint64_t*)b, L, um, work.p, h_rec, st, max_blocks);
+    gpu::check_hip(hipStreamSynchronize(st), "k_volume_compare");
+    return volume_compare_dict(*h_rec);
+  }, py::arg("a"), py::arg("b"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_um"), py::arg("max_blocks") = 0,
+     py::arg("stream") = 0);
 
   // K11 on a batch of masks of ANY sizes in one launch: planes = the masks' bit planes back to back
   // (mask i: hs[i] × ceil(ws[i] / 64) words); raw = the slices' u16 samples back to back; one pixel type

@@ -24,6 +24,7 @@
 #include "nm03/gpu_types.h"
 #include "nm03/jpeg.h"
 #include "nm03/kernels.h"
+#include "nm03/metaimage.h"
 
 namespace nm03 {
 
@@ -182,6 +183,14 @@ struct VolumeDevice {
   VolumeDistanceLayout dist_layout;
   std::unique_ptr<DevBuf> dist_work;
   VolumeThickness* h_thickness = nullptr;
+  // K17 (VolumeParams::compare): the layout, the work buffer, the reference's words on the device with their
+  // pinned staging, the pinned record and the events of its timing, allocated by the first run that asks for a
+  // comparison and kept.
+  VolumeCompareLayout cmp_layout;
+  std::unique_ptr<DevBuf> cmp_work, cmp_ref;
+  uint64_t* h_cmp_ref = nullptr;
+  VolumeCompare* h_compare = nullptr;
+  hipEvent_t cmp_e0 = nullptr, cmp_e1 = nullptr;
   VolumeDevice(const VolumeInput& v)
       : w(v.w), h(v.h), d(v.d), wpr((v.w + 63) / 64), words((size_t)v.h * ((v.w + 63) / 64)),
         ps(((size_t)v.w * v.h + 7) / 8 * 8),
@@ -207,6 +216,10 @@ struct VolumeDevice {
     if (h_intensity) (void)hipHostFree(h_intensity);
     if (h_texture) (void)hipHostFree(h_texture);
     if (h_thickness) (void)hipHostFree(h_thickness);
+    if (h_cmp_ref) (void)hipHostFree(h_cmp_ref);
+    if (h_compare) (void)hipHostFree(h_compare);
+    if (cmp_e0) (void)hipEventDestroy(cmp_e0);
+    if (cmp_e1) (void)hipEventDestroy(cmp_e1);
     if (h_measure) (void)hipHostFree(h_measure);
     if (h_tables) (void)hipHostFree(h_tables);
     if (h_flag) (void)hipHostFree(h_flag);
@@ -424,7 +437,8 @@ struct VolumeRunner::Impl {
   bool diameters_loaded = false;  // K13's code object (first run that asks for diameters)
   bool intensity_loaded = false;  // K11's code object (first run that asks for the intensity statistics)
   bool texture_loaded = false;    // K12's code object (first run that asks for the texture)
-  bool distance_loaded = false;   // K16's code object (first run that asks for a margin in mm or the thickness)
+  bool distance_loaded = false;   // K16's code object (first run that asks for a margin in mm, the thickness or a comparison)
+  bool compare_loaded = false;    // K17's code object (first run that asks for a comparison)
   explicit Impl(int dev) : device(dev) {
     check_hip(hipSetDevice(device), "hipSetDevice");
     preload_kernels();  // every code object, before the first launch (kernels.h)
@@ -489,6 +503,21 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
     if (v.w > 65535) throw std::invalid_argument(std::string(who) + "a row holds at most 65535 voxels");
     const std::string ext = measure::volume_distance_extent_error(v.w, v.h, v.d, p.spacing_um);
     if (!ext.empty()) throw std::invalid_argument(who + ext);
+  }
+  if (p.compare) {
+    const VolumeReference& ref = *p.compare;
+    if (!ref.bits && !ref.mask) throw std::invalid_argument("3D comparison: null buffer (the reference has neither bits nor a mask)");
+    if (ref.w != v.w || ref.h != v.h || ref.d != v.d)
+      throw std::invalid_argument("3D comparison: shape mismatch: the reference is " + std::to_string(ref.w) + " x " +
+                                  std::to_string(ref.h) + " x " + std::to_string(ref.d) + ", the volume " + std::to_string(v.w) +
+                                  " x " + std::to_string(v.h) + " x " + std::to_string(v.d));
+    for (int a = 0; a < 3; ++a)
+      if (p.spacing_um[a] < 1u) throw std::invalid_argument("3D comparison: a spacing must be at least 1 um");
+    if (v.w > 65535) throw std::invalid_argument("3D comparison: a row holds at most 65535 voxels");
+    if ((uint64_t)v.w * (uint64_t)v.h * (uint64_t)v.d >= (1ull << 32))
+      throw std::invalid_argument("3D comparison: a volume of 2^32 voxels or more cannot be compared");
+    const std::string ext = measure::volume_distance_extent_error(v.w, v.h, v.d, p.spacing_um);
+    if (!ext.empty()) throw std::invalid_argument("3D comparison: " + ext);
   }
   if (p.measure) {
     if (p.measure_connectivity != 6 && p.measure_connectivity != 26)
@@ -567,6 +596,49 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
     if (p.measure_thickness && !V.h_thickness)
       check_hip(hipHostMalloc((void**)&V.h_thickness, sizeof(VolumeThickness), hipHostMallocDefault), "hipHostMalloc thickness");
   }
+  if (p.compare) {  // K17 alike, after every check of this run; it launches K16's map
+    if (!I.distance_loaded) {
+      preload_volume_distance();
+      I.distance_loaded = true;
+    }
+    if (!I.compare_loaded) {
+      preload_volume_compare();
+      I.compare_loaded = true;
+    }
+    if (!V.cmp_work) {
+      V.cmp_layout = volume_compare_layout(v.w, v.h, v.d);
+      V.cmp_work = std::make_unique<DevBuf>(V.cmp_layout.bytes);
+      V.cmp_ref = std::make_unique<DevBuf>(V.words * V.d * 8);
+      check_hip(hipHostMalloc((void**)&V.h_cmp_ref, std::max<size_t>(V.words * V.d * 8, 16), hipHostMallocDefault),
+                "hipHostMalloc compare reference");
+      check_hip(hipHostMalloc((void**)&V.h_compare, sizeof(VolumeCompare), hipHostMallocDefault), "hipHostMalloc compare");
+      check_hip(hipEventCreate(&V.cmp_e0), "event");
+      check_hip(hipEventCreate(&V.cmp_e1), "event");
+    }
+    // The reference's words into the pinned staging (the stream is idle: the previous run ended with a sync).
+    const VolumeReference& ref = *p.compare;
+    const size_t nw = V.words * (size_t)V.d;
+    if (ref.bits) {
+      std::memcpy(V.h_cmp_ref, ref.bits, nw * 8);
+    } else {
+      std::memset(V.h_cmp_ref, 0, nw * 8);
+      for (int z = 0; z < v.d; ++z)
+        for (int y = 0; y < v.h; ++y) {
+          const uint8_t* src = ref.mask + ((size_t)z * v.h + y) * v.w;
+          uint64_t* row = V.h_cmp_ref + (size_t)z * V.words + (size_t)y * V.wpr;
+          int x = 0;
+          for (; x + 8 <= v.w; x += 8) {  // eight voxels at a time: most of a mask is empty
+            uint64_t eight;
+            std::memcpy(&eight, src + x, 8);
+            if (!eight) continue;
+            for (int b = 0; b < 8; ++b)
+              if (src[x + b]) row[(x + b) >> 6] |= 1ull << ((x + b) & 63);
+          }
+          for (; x < v.w; ++x)
+            if (src[x]) row[x >> 6] |= 1ull << (x & 63);
+        }
+    }
+  }
   const PipeConsts pc = make_consts(p.pipe, 2);
   check_hip(hipEventRecord(I.e0, V.stream), "event");
   VolumeResult r;
@@ -621,6 +693,18 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
     float mms = 0;
     (void)hipEventElapsedTime(&mms, I.e1, I.e2);
     r.measure_s = mms * 1e-3;
+  }
+  if (p.compare) {  // K17's twenty launches after every measure launch, timed on their own
+    check_hip(hipEventRecord(V.cmp_e0, V.stream), "event");
+    check_hip(hipMemcpyAsync(V.cmp_ref->p, V.h_cmp_ref, V.words * (size_t)V.d * 8, hipMemcpyHostToDevice, V.stream), "H2D reference");
+    launch_volume_compare(V.dil.as<uint64_t>(), V.cmp_ref->as<uint64_t>(), V.cmp_layout, p.spacing_um, V.cmp_work->p, V.h_compare,
+                          V.stream);
+    check_hip(hipEventRecord(V.cmp_e1, V.stream), "event");
+    check_hip(hipEventSynchronize(V.cmp_e1), "sync");
+    r.compare = *V.h_compare;
+    float cms = 0;
+    (void)hipEventElapsedTime(&cms, V.cmp_e0, V.cmp_e1);
+    r.compare_s = cms * 1e-3;
   }
   check_hip(hipEventSynchronize(I.e1), "sync");
   r.sweeps = srg_volume_result(V.h_flag);
@@ -769,6 +853,9 @@ VolumeResult VolumeRunner::run_slab(Comm& comm, const VolumeInput& slab, int z0,
   if (p.dilate_um >= 0 || p.measure_thickness)
     throw std::invalid_argument("run_slab: a margin in millimetres and the thickness are not supported on a volume split "
                                 "into slabs (a margin across slabs needs a halo of its reach)");
+  if (p.compare)
+    throw std::invalid_argument("run_slab: comparing a volume split into slabs with a reference is not supported "
+                                "(the surface distances of a slab are not those of the volume)");
   if (p.measure || p.measure_lesions || p.measure_diameters || p.measure_intensity || p.measure_texture)
     throw std::invalid_argument("run_slab: measuring a volume split into slabs is not supported "
                                 "(components that cross slabs need a collective)");
@@ -1193,7 +1280,37 @@ struct VolOutcome {
   int32_t view_files = 0;     // --volume-views: view files written (12, or 0)
   int32_t mesh_files = 0;     // --volume-mesh: files written (the mesh and mesh.json: 2, or 0)
   int64_t mesh_vertices = 0, mesh_quads = 0;
+  int32_t mask_files = 0;      // --volume-mask: files written (mask.mhd and mask.raw: 2, or 0)
+  std::string compare_status;  // --compare-to: "ok", "no_reference" or "shape_mismatch" (empty: the patient failed)
+  std::string compare_fields;  // --compare-to: the patient's fields of comparisons.csv (compare::csv_fields)
+  int32_t dice_ok = 0, distances_ok = 0;
+  double dice = 0, hausdorff_mm = 0, compare_s = 0;
 };
+
+// --compare-to: the reference mask of a patient, DIR/<patient>/mask.mhd, as 0 / 1 bytes (non-zero = set, whatever
+// the element type). `status`: "ok", "no_reference" (no such file) or "shape_mismatch".
+std::vector<uint8_t> read_reference_mask(const std::string& path, int w, int h, int d, std::string* status) {
+  {
+    std::ifstream probe(path, std::ios::binary);
+    if (!probe) {
+      *status = "no_reference";
+      return {};
+    }
+  }
+  const mhd::Image im = mhd::read(path);
+  if (im.w != w || im.h != h || im.d != d) {
+    *status = "shape_mismatch";
+    return {};
+  }
+  const size_t es = mhd::element_size(im.type), n = (size_t)w * h * d;
+  if (im.bytes.size() != n * es) throw std::runtime_error("--compare-to: " + path + " holds " + std::to_string(im.bytes.size()) +
+                                                           " bytes, expected " + std::to_string(n * es));
+  std::vector<uint8_t> m(n, 0);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t b = 0; b < es; ++b) m[i] |= im.bytes[i * es + b] != 0;
+  *status = "ok";
+  return m;
+}
 
 std::vector<uint8_t> encode(const std::vector<VolPatient>& pl) {
   ByteWriter w;
@@ -1303,7 +1420,9 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
                                                       std::vector<VolumeLesionDiameters>* diameters = nullptr,
                                                       const ViewsAt* views_at = nullptr, VolumeViewsExport* views = nullptr,
                                                       VolumeMesh* mesh_out = nullptr, int mesh_placement = kMeshCorner,
-                                                      VolumeThickness* thickness = nullptr) {
+                                                      VolumeThickness* thickness = nullptr,
+                                                      std::vector<uint8_t>* dilated_out = nullptr,
+                                                      VolumeCompare* compared = nullptr) {
   const GoldenPlanes gp = golden_preprocess(v, vp);
   std::vector<Seed> seeds = vp.seeds;
   if (seeds.empty()) {
@@ -1330,6 +1449,11 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
     views->files = golden::volume_view_jpegs(views->views, (uint8_t)v.type, v.stored_bits, slope, intercept, v.spacing_x,
                                              v.spacing_y, v.spacing_z, rp);
   }
+  if (compared && vp.compare) {  // --compare-to: the golden comparison with the reference's bytes (nm03/volume_compare.h)
+    const std::vector<uint8_t> ref(vp.compare->mask, vp.compare->mask + (size_t)v.w * v.h * v.d);
+    *compared = golden::compare_volumes(dil, ref, v.w, v.h, v.d, vp.spacing_um);
+  }
+  if (dilated_out) *dilated_out = dil;
   if (mesh_out)  // --volume-mesh: the golden mesh of the dilated mask (nm03/volume_mesh.h)
     *mesh_out = golden::volume_mesh(dil.data(), v.w, v.h, v.d, v.spacing_x, v.spacing_y, v.spacing_z, mesh_placement);
   return golden_export(v, gp.vals, dil, rp);
@@ -1514,6 +1638,25 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         if (!ext.empty())
           throw std::runtime_error(std::string(vp.dilate_um >= 0 ? "--dilate-mm: " : "--measure-volume-thickness: ") + ext);
       }
+      // --compare-to: the reference of this patient, read and checked before anything runs; a missing file or another
+      // shape is a status of the table, not a failure of the patient
+      std::vector<uint8_t> ref_mask, dilated;
+      VolumeReference ref;
+      VolumeCompare compared = {};
+      const std::string ref_path = cfg.compare_to.empty() ? std::string() : cohort::with_slash(cfg.compare_to) + pp.id + "/mask.mhd";
+      vp.compare = nullptr;
+      if (!cfg.compare_to.empty()) {
+        ref_mask = read_reference_mask(ref_path, v.w, v.h, v.d, &o.compare_status);
+        if (o.compare_status == "ok") {
+          measure::volume_spacing_um((double)v.spacing_x, (double)v.spacing_y, v.spacing_z, vp.spacing_um);
+          const std::string ext = v.w > 65535 ? std::string("a row holds at most 65535 voxels")
+                                              : measure::volume_distance_extent_error(v.w, v.h, v.d, vp.spacing_um);
+          if (!ext.empty()) throw std::runtime_error("--compare-to: " + ext);
+          ref.mask = ref_mask.data();
+          ref.w = v.w, ref.h = v.h, ref.d = v.d;
+          vp.compare = &ref;
+        }
+      }
       VolumeMesh vmesh;
       const uint64_t mesh_cap = cfg.volume_mesh_max_mb << 20;
       VolumeViewsExport vx;
@@ -1524,16 +1667,19 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       if (cfg.cpu) {
         files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions, &intensity, &texture, &diameters,
                                     cfg.volume_views ? &cfg.volume_views_at : nullptr, &vx, cfg.volume_mesh ? &vmesh : nullptr,
-                                    cfg.volume_mesh_placement, &thickness);
+                                    cfg.volume_mesh_placement, &thickness, cfg.volume_mask ? &dilated : nullptr, &compared);
         if (cfg.volume_mesh) {  // the check export_mesh makes between its two halves
           const std::string err = mesh::size_error(vmesh.vertices(), vmesh.quad_count(), mesh_cap);
           if (!err.empty()) throw std::runtime_error("--volume-mesh: " + err);
         }
       } else {
-        VolumeResult r = runner->run(v, vp, false);
+        VolumeResult r = runner->run(v, vp, cfg.volume_mask);
         o.sweeps = r.sweeps;
         o.gpu_s = r.kernels_s;
         o.measure_s = r.measure_s;
+        o.compare_s = r.compare_s;
+        compared = r.compare;
+        dilated = std::move(r.dilated);
         measured = r.measure;
         lesions = std::move(r.lesions);
         diameters = std::move(r.diameters);
@@ -1566,6 +1712,19 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         o.mesh_files = 2;
         o.mesh_vertices = (int64_t)vmesh.vertices();
         o.mesh_quads = (int64_t)vmesh.quad_count();
+      }
+      if (cfg.volume_mask) {  // the dilated mask as 0 / 1 bytes at the series' spacing
+        mhd::write(pp.out_dir + "/mask", dilated.data(), v.w, v.h, v.d, mhd::MetType::kUChar, v.spacing_x, v.spacing_y,
+                   (float)v.spacing_z);
+        o.mask_files = 2;
+      }
+      if (vp.compare) {  // the sidecar; its table fields travel to rank 0
+        const std::string text = compare::to_json(compared, v.w, v.h, v.d, vp.spacing_um, ref_path);
+        write_bytes(pp.out_dir + "/compare.json", text.data(), text.size());
+        o.compare_fields = compare::csv_fields(compared, v.w, v.h, v.d, vp.spacing_um, ref_path);
+        const compare::Derived dv = compare::derive(compared, vp.spacing_um);
+        o.dice_ok = dv.dice_ok, o.dice = dv.dice;
+        o.distances_ok = dv.distances_ok, o.hausdorff_mm = dv.hausdorff_mm;
       }
       if (vp.measure) {  // the sidecar next to the planes; its text travels to rank 0 for the table
         o.measure_json = vp.measure_texture
@@ -1617,6 +1776,14 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
     w.i32(o.mesh_files);
     w.u64((uint64_t)o.mesh_vertices);
     w.u64((uint64_t)o.mesh_quads);
+    w.i32(o.mask_files);
+    w.str(o.compare_status);
+    w.str(o.compare_fields);
+    w.i32(o.dice_ok);
+    w.i32(o.distances_ok);
+    w.f64(o.dice);
+    w.f64(o.hausdorff_mm);
+    w.f64(o.compare_s);
   }
   auto all = comm.allgather_bytes(w.b);
   double tot = wall_now() - t_start;
@@ -1646,6 +1813,14 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       o.mesh_files = r.i32();
       o.mesh_vertices = (int64_t)r.u64();
       o.mesh_quads = (int64_t)r.u64();
+      o.mask_files = r.i32();
+      o.compare_status = r.str();
+      o.compare_fields = r.str();
+      o.dice_ok = r.i32();
+      o.distances_ok = r.i32();
+      o.dice = r.f64();
+      o.hausdorff_mm = r.f64();
+      o.compare_s = r.f64();
       outs.push_back(std::move(o));
     }
   }
@@ -1706,6 +1881,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
        << ", \"export_s\": " << o.export_s << ", \"wall_s\": " << o.wall_s << ", \"rounds\": " << o.rounds
        << ", \"exchanged_bytes\": " << o.exchanged;
     if (cfg.measure_volume) pj << ", \"measure_s\": " << o.measure_s;
+    if (!cfg.compare_to.empty()) pj << ", \"compare_s\": " << o.compare_s;
     pj << "}";
   }
   std::cout << "\n=== All Processing Completed ===\n" << std::endl;
@@ -1727,6 +1903,21 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       } catch (const std::exception& e) {
         std::cerr << "Error writing lesions.csv: " << e.what() << std::endl;
       }
+    }
+  }
+  if (!cfg.compare_to.empty()) {  // the comparison table, in plan order (an error is reported, not fatal)
+    try {
+      std::string text = compare::csv_header() + "\n";
+      const size_t commas = (size_t)std::count(text.begin(), text.end(), ',') - 1;  // after patient,status
+      for (size_t i = 0; i < plan.size(); ++i) {
+        const VolOutcome& o = outs[i];
+        const bool ok = o.ok && o.compare_status == "ok";
+        text += plan[i].id + "," + (o.ok ? o.compare_status : std::string("failed")) + "," +
+                (ok ? o.compare_fields : std::string(commas - 1, ',')) + "\n";
+      }
+      write_bytes(cohort::with_slash(cfg.out_dir) + "comparisons.csv", text.data(), text.size());
+    } catch (const std::exception& e) {
+      std::cerr << "Error writing comparisons.csv: " << e.what() << std::endl;
     }
   }
   if (!cfg.json.empty()) {
@@ -1753,6 +1944,27 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       f << ", \"volume_mesh\": {\"patients\": " << mp_n << ", \"vertices\": " << mv_n << ", \"quads\": " << mq_n
         << ", \"placement\": \"" << mesh::placement_name(cfg.volume_mesh_placement) << "\", \"format\": \""
         << mesh::format_name(cfg.volume_mesh_format) << "\"}";
+    }
+    if (cfg.volume_mask) {
+      int64_t mk_n = 0;
+      for (const auto& o : outs) mk_n += o.ok && o.mask_files > 0;
+      f << ", \"volume_mask\": {\"patients\": " << mk_n << "}";
+    }
+    if (!cfg.compare_to.empty()) {
+      int64_t cn = 0, dn = 0;
+      double dice_sum = 0, hd_max = 0;
+      bool any_hd = false;
+      for (const auto& o : outs) {
+        if (!o.ok || o.compare_status != "ok") continue;
+        ++cn;
+        if (o.dice_ok) ++dn, dice_sum += o.dice;
+        if (o.distances_ok) any_hd = true, hd_max = std::max(hd_max, o.hausdorff_mm);
+      }
+      char buf[160];
+      std::string dm = "null", hm = "null";
+      if (dn) std::snprintf(buf, sizeof buf, "%.9g", dice_sum / (double)dn), dm = buf;
+      if (any_hd) std::snprintf(buf, sizeof buf, "%.9g", hd_max), hm = buf;
+      f << ", \"compare\": {\"volumes\": " << cn << ", \"dice_mean\": " << dm << ", \"hausdorff_mm_max\": " << hm << "}";
     }
     f << "}\n";
   }
