@@ -1,7 +1,7 @@
 """One DICOM series as a 3D volume on the MI355X: per-slice preprocessing, 6-connected 3D region
 growing and a 7×7×7 dilation (BASELINE config 5), checked against the golden 3D model.
 
-    python examples/volume_3d.py --series path/to/series_dir [--ball] [--measure] [--views DIR] [--mesh DIR] [--dilate-mm R [--compare-to-cube]]
+    python examples/volume_3d.py --series path/to/series_dir [--ball] [--measure] [--views DIR] [--mesh DIR] [--dilate-mm R [--compare-to-cube [--compare-lesions N]]]
 """
 import argparse
 import os
@@ -32,17 +32,24 @@ def main(argv=None):
     ap.add_argument("--compare-to-cube", action="store_true",
                     help="with --dilate-mm: also score the margin's mask against the default 7x7x7 cube's (K17) and print "
                          "Dice and the surface distances")
+    ap.add_argument("--compare-lesions", type=int, default=0, metavar="N",
+                    help="with --compare-to-cube: also compare the two masks lesion by lesion (K18, N reported lesions per side) "
+                         "and print the totals")
     a = ap.parse_args(argv)
     margin = a.dilate_mm is not None
     if a.compare_to_cube and not margin:
         ap.error("--compare-to-cube needs --dilate-mm R")
+    if a.compare_lesions and not a.compare_to_cube:
+        ap.error("--compare-lesions needs --compare-to-cube")
+    if not 0 <= a.compare_lesions <= 64:
+        ap.error("--compare-lesions must be 1..64")
     cube_mask = None
     if a.compare_to_cube:  # the reference: a run with the default cube; `run` returns `dilated`, so it could be saved as well
         cube_mask = nm.VolumePipeline(nm.PipelineConfig(se_shape=int(a.ball)), connectivity=6, dilation=7).run_series(a.series)["dilated"]
     vp = nm.VolumePipeline(nm.PipelineConfig(se_shape=int(a.ball)), connectivity=6, dilation=7, measure=a.measure or margin,
                            measure_lesions=int(a.measure), measure_diameters=a.measure, views=bool(a.views),
                            mesh=bool(a.mesh), dilate_mm=a.dilate_mm, measure_thickness=margin, compare_to=cube_mask,
-                           compare_reference="cube")
+                           compare_reference="cube", compare_lesions=a.compare_lesions)
     res = vp.run_series(a.series)
     band = res["band"]
     g = nm.utils.series_geometry(a.series)
@@ -68,6 +75,10 @@ def main(argv=None):
                   f"HD95 {c['hd95_mm']:.3f} mm, ASSD {c['assd_mm']:.3f} mm ({c['surface_a']} and {c['surface_b']} surface voxels)")
         else:
             print(f"margin against the cube: {c['a_vox']} and {c['b_vox']} voxels, no surface distances (an empty mask)")
+        if a.compare_lesions:
+            f1 = "none" if c["lesion_f1"] is None else f"{c['lesion_f1']:.4f}"
+            print(f"lesions (connectivity {c['lesions_connectivity']}): margin {c['lesions_a']} ({c['hit_a']} hit, {c['multi_a']} merging), "
+                  f"cube {c['lesions_b']} ({c['hit_b']} hit, {c['multi_b']} split), F1 {f1}")
     if a.measure:
         import json
         m = json.loads(res["measure_json"])

@@ -130,6 +130,10 @@ struct AppConfig {
   // (nm03/volume_compare.h). Empty = off.
   bool volume_mask = false;
   std::string compare_to;
+  // --compare-lesions N (3d, with --compare-to): also the lesion-wise comparison (nm03/volume_compare_lesions.h) with
+  // N reported lesions per side at measure_volume_connectivity: more keys in compare.json, nine more columns in
+  // comparisons.csv and <out>/compare_lesions.csv. 0 = off.
+  int compare_lesions = 0;
   bool volume_mesh = false;
   int volume_mesh_placement = kMeshCorner;
   int volume_mesh_format = kMeshPly;

@@ -463,6 +463,25 @@ void launch_volume_compare(const uint64_t* a, const uint64_t* b, const VolumeCom
 // the Python op, load it. K16's is loaded separately (preload_volume_distance).
 void preload_volume_compare();
 
+// K18 (k18_volume_compare_lesions.hip): the lesion-wise comparison of nm03/volume_compare_lesions.h between two bit
+// volumes `a` and `b` of one frame (d planes of h rows of ceil(w / 64) words, bits past the width tolerated). Ten
+// launches on `stream`: init, then for both masks in one grid each K8's runs, unions, runs pointed at their roots
+// (with the side data of the roots set), areas and K10's candidates, the selection (a workgroup per side), the
+// join of the two labellings, the count of lesions / hit / multi and the launch that writes the record to `out`
+// (volume_compare_lesions_record_bytes(max_lesions) of device, pinned or host-mapped memory) with plain vector
+// stores. No cooperative launch, grid barrier, flag, look-back, spin, host round trip or allocation. `work`:
+// volume_compare_lesions_work_bytes of device memory (16 bytes per slot of K8's layout, a 35 KiB control block and
+// the candidate lists), no initialisation needed; 0 for arguments the launcher refuses. `max_blocks`: a lower cap on
+// the workgroups of the join (0 = the default 1024); the record does not depend on it. Throws DeviceError before any
+// launch for a null buffer, max_lesions outside 1 … kMaxVolumeLesions, a connectivity other than 6 / 26 and a volume
+// whose (w + 1)·h·d + 1 slots do not fit 32 bits.
+size_t volume_compare_lesions_work_bytes(int w, int h, int d, int max_lesions);
+void launch_volume_compare_lesions(const uint64_t* a, const uint64_t* b, int w, int h, int d, int max_lesions, int connectivity, void* work,
+                                   void* out, hipStream_t stream, int max_blocks = 0);
+// Loads K18's code object on the current device: only a VolumeRunner's first run that asks for the lesion-wise
+// comparison, and the Python op, load it.
+void preload_volume_compare_lesions();
+
 // K6: binary threshold lo ≤ x ≤ hi → u8 0/1 (in 16-byte aligned, out 4-byte aligned).
 void launch_threshold(const float* in, uint8_t* out, size_t n, float lo, float hi, hipStream_t stream);
 

@@ -13,6 +13,7 @@
 #include "nm03/engine.h"
 #include "nm03/measure.h"
 #include "nm03/volume_compare.h"
+#include "nm03/volume_compare_lesions.h"
 #include "nm03/volume_distance.h"
 #include "nm03/volume_mesh.h"
 #include "nm03/volume_views.h"
@@ -78,6 +79,10 @@ struct VolumeResult {
   // of the reference upload and K17's launches (outside kernels_s and measure_s).
   VolumeCompare compare = {};
   double compare_s = 0;
+  // VolumeParams::compare_lesions: the K18 record of the same two masks, and the GPU time of K18's launches
+  // (outside compare_s).
+  VolumeCompareLesions compare_lesions;
+  double compare_lesions_s = 0;
 };
 
 // The reference mask of a comparison (VolumeParams::compare), in host memory, valid during run(): either `bits`
@@ -137,6 +142,10 @@ struct VolumeParams {
   // Not null: also compare the dilated volume with this reference mask of the same shape (K17,
   // nm03/volume_compare.h VolumeCompare) at `spacing_um`, after every measure launch. Needs no `measure`.
   const VolumeReference* compare = nullptr;
+  // N > 0 (needs `compare`): also the lesion-wise comparison of the same two masks (K18,
+  // nm03/volume_compare_lesions.h) with N reported lesions per side, at `measure_connectivity`, after K17's
+  // launches on the same stream. 0 = off.
+  int compare_lesions = 0;
 };
 
 // Runs the 3D pipeline on `device`; copies masks back when `want_masks`. A VolumeRunner keeps
@@ -161,6 +170,11 @@ class VolumeRunner {
   // run that asks for it and are kept and rebuilt with the volume shape; its launches follow every measure
   // launch. A reference without a buffer or of another shape and the extent rule throw std::invalid_argument
   // before the run's first launch.
+  // p.compare_lesions: K18's code object, its work buffer (16 bytes per slot of K8's layout), the pinned record and
+  // two events come with the first run that asks for it and are kept and rebuilt with the volume shape; its ten
+  // launches follow K17's on the masks K17 already has on the device. Without `compare`, outside 1 … 64, with a
+  // connectivity other than 6 / 26 or on a volume K8 could not label it throws std::invalid_argument before the
+  // run's first launch.
   VolumeResult run(const VolumeInput& v, const VolumeParams& p, bool want_masks);
   // After run() on the same volume: the 2·d exported JPEG files of the 3D cohort mode, in plane
   // order (original, processed), rendered and encoded on the GPU (K3/K4) from the volume still on
@@ -193,7 +207,8 @@ class VolumeRunner {
   // export_jpegs(slab, ...) then exports its planes. Masks (when requested) are the slab's.
   // p.measure, p.measure_lesions, p.measure_diameters, p.measure_intensity or p.measure_texture throws std::invalid_argument: components that cross slabs would
   // need a collective. p.dilate_um ≥ 0 and p.measure_thickness throw it too: a margin across slabs needs a
-  // halo of its reach. p.compare throws it as well: the surface distances of a slab are not those of the volume.
+  // halo of its reach. p.compare throws it as well: the surface distances of a slab are not those of the volume;
+  // so does p.compare_lesions (lesions that cross slabs).
   VolumeResult run_slab(Comm& comm, const VolumeInput& slab, int z0, int depth, const VolumeParams& p, bool want_masks,
                         struct SlabStats* stats = nullptr);
 

@@ -50,6 +50,8 @@
 
 namespace nm03 {
 
+struct VolumeCompareLesions;  // nm03/volume_compare_lesions.h (K18, --compare-lesions)
+
 struct VolumeCompareDirected {
   uint64_t max_um2;  // 0 when !found
   uint64_t sum_um;   // Σ ⌊√D⌋
@@ -94,12 +96,16 @@ Derived derive(const VolumeCompare& c, const uint32_t um[3]);
 // The one writer of compare.json (GPU path, --cpu and Python): one object on one line, keys in fixed order —
 // width, height, depth, compare_spacing_um, reference; a_vox, b_vox, tp_vox, fp_vox, fn_vox, surface_a, surface_b;
 // n_ab, max_um2_ab, worst_ab [x, y, z], sum_um_ab, p95_um_ab, found_ab and the same for ba; then the derived
-// values in the order of Derived. Ends with "}\n".
-std::string to_json(const VolumeCompare& c, int w, int h, int d, const uint32_t um[3], const std::string& reference);
+// values in the order of Derived. Ends with "}\n". With `lesions` (K18, --compare-lesions) the lesion keys of
+// nm03/volume_compare_lesions.h (compare::lesions_json_keys) follow assd_mm; removing them gives the text without.
+std::string to_json(const VolumeCompare& c, int w, int h, int d, const uint32_t um[3], const std::string& reference,
+                    const VolumeCompareLesions* lesions = nullptr);
 // comparisons.csv: the header line (no newline) and one patient's fields after "patient,status," (arrays
-// flattened; the same values as to_json, null written as an empty field).
-std::string csv_header();
-std::string csv_fields(const VolumeCompare& c, int w, int h, int d, const uint32_t um[3], const std::string& reference);
+// flattened; the same values as to_json, null written as an empty field). With `lesions` the nine per-volume
+// lesion columns (the six totals, then lesion_sensitivity, lesion_precision, lesion_f1) follow all the others.
+std::string csv_header(bool lesions = false);
+std::string csv_fields(const VolumeCompare& c, int w, int h, int d, const uint32_t um[3], const std::string& reference,
+                       const VolumeCompareLesions* lesions = nullptr);
 
 }  // namespace compare
 

@@ -47,7 +47,12 @@ A against B (K17, nm03/volume_compare.h): overlap counts, both surfaces and, in 
 summed and the 95th-percentile surface-to-surface distance in physical space. The result gains `compare` (the
 record's integers, keyed as compare.json), `compare_json` (the text of the CLI's compare.json, from the one native
 writer, with `compare_reference` as its `reference`) and `compare_s`. `run` returns `dilated` as it always does, so
-a caller can save it (native().mhd_write) and compare a later run against it. It needs no `measure`."""
+a caller can save it (native().mhd_write) and compare a later run against it. It needs no `measure`.
+
+With `compare_lesions=N` (1..64, needs `compare_to`) the two masks are also compared lesion by lesion (K18,
+nm03/volume_compare_lesions.h) at `measure_connectivity`: the result gains `compare_lesions` (the dict of
+ops.compare_volume_lesions, `table` as an int64 array) and `compare_lesions_s`, and `compare_json` is the longer text
+with the lesion keys after assd_mm."""
 import numpy as np
 
 from .._native import native
@@ -65,7 +70,8 @@ class VolumePipeline:
                  measure_connectivity: int = 26, measure_lesions: int = 0, measure_intensity: bool = False, measure_texture: bool = False,
                  texture_levels: int = 32, measure_diameters: bool = False, views: bool = False, views_at="mask",
                  mesh: bool = False, mesh_placement: str = "corner", mesh_format: str = "ply", mesh_max_mb: int = 512,
-                 dilate_mm=None, measure_thickness: bool = False, compare_to=None, compare_reference: str = ""):
+                 dilate_mm=None, measure_thickness: bool = False, compare_to=None, compare_reference: str = "",
+                 compare_lesions: int = 0):
         self.config = config or PipelineConfig()
         self.connectivity = connectivity
         self.dilation = dilation
@@ -122,6 +128,11 @@ class VolumePipeline:
             raise ValueError("compare_to must be [D, H, W]")
         if self.compare_to is not None and self.config.host_only:
             raise ValueError("the comparison runs on the GPU: not available with host_only")
+        self.compare_lesions = int(compare_lesions)
+        if not 0 <= self.compare_lesions <= 64:
+            raise ValueError(f"compare_lesions must be 0 (off) or 1..64 (got {compare_lesions})")
+        if self.compare_lesions and self.compare_to is None:
+            raise ValueError("compare_lesions needs compare_to")
         self._runners = {}  # device -> native VolumeRunner (buffers/stream reused across volumes)
 
     def default_seeds(self, volume):
@@ -153,7 +164,7 @@ class VolumePipeline:
                              texture_levels=self.texture_levels, measure_diameters=self.measure_diameters,
                              dilate_um=-1 if self.dilate_mm is None else native().dilate_mm_to_um(self.dilate_mm),
                              measure_thickness=self.measure_thickness, compare_to=self.compare_to,
-                             compare_reference=self.compare_reference, **_meta_args(meta))
+                             compare_reference=self.compare_reference, compare_lesions=self.compare_lesions, **_meta_args(meta))
         elif not self.measure and meta is None and self.dilate_mm is None:
             res = runner.run(vol, self.config.pipeline_params(), self.connectivity, self.dilation, s)
         elif self.dilate_mm is not None or self.measure_thickness:

@@ -707,3 +707,57 @@ def compare_volumes(a, b, spacing_um=(1000, 1000, 1000), max_blocks=None):
     wa = pack_bits(a.bool()).contiguous()
     wb = pack_bits(b.bool()).contiguous()
     return native().k_volume_compare(wa.data_ptr(), wb.data_ptr(), w, h, d, um, int(max_blocks or 0), _stream())
+
+
+def compare_volume_lesions(a, b, max_lesions, connectivity=26, max_blocks=None):
+    """Lesion-wise detection scores for two volume masks of one shape (K18, nm03/volume_compare_lesions.h) → a dict:
+    connectivity, max_lesions, the totals over ALL connected components (lesions_a, hit_a, multi_a, lesions_b, hit_b,
+    multi_b: a lesion is hit when it overlaps the other mask, multi when it meets at least two of its components),
+    a_lesions and b_lesions (the `max_lesions` largest of each side, largest first, ties to the earlier first voxel:
+    dicts of voxels, first [x, y, z], overlap_vox, partners_reported, overlap_other_vox, multi, best,
+    best_overlap_vox) and table, an int64 tensor [N + 1, N + 1] of |A_i ∩ B_j| whose index N collects the unreported
+    components of a side. native().volume_compare_to_json(..., lesions=…) gives the sidecar text with the derived values.
+
+    `a`, `b`: bool CUDA tensors [D, H, W] (compare_volume_lesions_words takes their bit words). Ten launches. `max_blocks` lowers the cap on the workgroups of the
+    join launch (the result does not depend on it)."""
+    if not hasattr(a, "is_cuda") or not a.is_cuda:
+        raise ValueError("a must be a CUDA (HIP) tensor")
+    if not hasattr(b, "is_cuda") or not b.is_cuda:
+        raise ValueError("b must be a CUDA (HIP) tensor")
+    if a.dim() != 3 or tuple(b.shape) != tuple(a.shape):
+        raise ValueError("both masks must be [D, H, W] of one shape")
+    if b.device != a.device:
+        raise ValueError("both masks must be on one device")
+    d, h, w = (int(v) for v in a.shape)
+    if min(d, h, w) < 1:
+        raise ValueError("empty volume")
+    wa = pack_bits(a.bool()).contiguous()
+    wb = pack_bits(b.bool()).contiguous()
+    return compare_volume_lesions_words(wa, wb, w, max_lesions, connectivity, max_blocks)
+
+
+def compare_volume_lesions_words(wa, wb, width, max_lesions, connectivity=26, max_blocks=None):
+    """compare_volume_lesions on the masks' bit words: int64 CUDA tensors [D, H, ceil(width / 64)], LSB = left-most
+    voxel; bits past the width are tolerated."""
+    for name, t in (("a", wa), ("b", wb)):
+        if not hasattr(t, "is_cuda") or not t.is_cuda or t.dtype != torch.int64 or t.dim() != 3:
+            raise ValueError(f"{name} must be an int64 CUDA (HIP) tensor [D, H, ceil(width / 64)]")
+    if tuple(wa.shape) != tuple(wb.shape) or wa.device != wb.device:
+        raise ValueError("both word volumes must have one shape and one device")
+    d, h, n = (int(v) for v in wa.shape)
+    w = int(width)
+    if min(d, h, w) < 1 or n != (w + 63) // 64:
+        raise ValueError("the words must be [D, H, ceil(width / 64)]")
+    if not 1 <= int(max_lesions) <= 64:
+        raise ValueError("max_lesions must be 1..64")
+    if int(connectivity) not in (6, 26):
+        raise ValueError("connectivity must be 6 or 26")
+    if (w + 1) * h * d + 1 >= 2 ** 32:
+        raise ValueError("volume too large to measure: (w + 1) * h * d + 1 must stay below 2^32")
+    if max_blocks is not None and int(max_blocks) < 1:
+        raise ValueError("max_blocks must be at least 1")
+    wa, wb = wa.contiguous(), wb.contiguous()
+    res = native().k_volume_compare_lesions(wa.data_ptr(), wb.data_ptr(), w, h, d, int(max_lesions), int(connectivity),
+                                            int(max_blocks or 0), _stream())
+    res["table"] = torch.from_numpy(res["table"])
+    return res

@@ -889,3 +889,66 @@ def compare_volumes(a, b, spacing_um=(1000, 1000, 1000)):
     _compare_directed(sa, sb, spacing_um, "_ab", out)
     _compare_directed(sb, sa, spacing_um, "_ba", out)
     return out
+
+
+def _lesion_records(lab, n_lab, other_lab, order, other_order, table, is_a, n_max):
+    import numpy as np
+    out = []
+    others = len(other_order)
+    for i, l in enumerate(order):
+        where = lab == l
+        first = int(np.flatnonzero(where.ravel())[0])  # raster (z, y, x) order
+        d, h, w = lab.shape
+        line = table[i, :] if is_a else table[:, i]
+        partners = np.unique(other_lab[where & (other_lab > 0)])
+        best, best_o = -1, 0
+        for j in range(others):
+            if int(line[j]) > best_o:  # a tie keeps the smaller index
+                best, best_o = j, int(line[j])
+        out.append({"voxels": int(where.sum()), "first": [first % w, first // w % h, first // (w * h)], "overlap_vox": int(line.sum()),
+                    "partners_reported": int((line[:others] > 0).sum()), "overlap_other_vox": int(line[n_max]),
+                    "multi": int(partners.size >= 2), "best": best, "best_overlap_vox": best_o})
+    return out
+
+
+def compare_volume_lesions(a, b, max_lesions, connectivity=26):
+    """Reference of ops.compare_volume_lesions / native.golden_compare_volume_lesions on two [D, H, W] masks (arrays
+    or CPU tensors) → the same dict, `table` as an int64 array. scipy.ndimage.label with generate_binary_structure(3, 1)
+    or (3, 3) gives the components (its labels are in the order of the first voxels), np.add.at on the label pairs of
+    A ∩ B the table, np.unique of the pairs the partners."""
+    import numpy as np
+    from scipy import ndimage
+    ma, mb = _distance_set(a, "foreground"), _distance_set(b, "foreground")
+    if ma.shape != mb.shape:
+        raise ValueError("both masks must be [D, H, W] of one shape")
+    n = int(max_lesions)
+    if not 1 <= n <= 64:
+        raise ValueError("max_lesions must be 1..64")
+    if connectivity not in (6, 26):
+        raise ValueError("connectivity must be 6 or 26")
+    st = ndimage.generate_binary_structure(3, 1 if connectivity == 6 else 3)
+    la, na = ndimage.label(ma, structure=st)
+    lb, nb = ndimage.label(mb, structure=st)
+    both = ma & mb
+    pairs = np.unique(np.stack([la[both], lb[both]], axis=1), axis=0) if both.any() else np.zeros((0, 2), dtype=np.int64)
+    out = {"connectivity": int(connectivity), "max_lesions": n, "lesions_a": int(na), "lesions_b": int(nb)}
+    for tag, col in (("a", 0), ("b", 1)):
+        ids, cnt = np.unique(pairs[:, col], return_counts=True)
+        out["hit_" + tag] = int(ids.size)
+        out["multi_" + tag] = int((cnt >= 2).sum())
+
+    def order(lab, count):  # labels: more voxels first, then the earlier first voxel (= the smaller label)
+        sizes = np.bincount(lab.ravel(), minlength=count + 1)[1:]
+        return [int(i) + 1 for i in np.lexsort((np.arange(count), -sizes))][:n]
+
+    oa, ob = order(la, na), order(lb, nb)
+    rank_a = np.full(na + 1, n, dtype=np.int64)
+    rank_b = np.full(nb + 1, n, dtype=np.int64)
+    rank_a[oa] = np.arange(len(oa))
+    rank_b[ob] = np.arange(len(ob))
+    table = np.zeros((n + 1, n + 1), dtype=np.int64)
+    np.add.at(table, (rank_a[la[both]], rank_b[lb[both]]), 1)
+    out["a_lesions"] = _lesion_records(la, na, lb, oa, ob, table, True, n)
+    out["b_lesions"] = _lesion_records(lb, nb, la, ob, oa, table, False, n)
+    out["table"] = table
+    return out

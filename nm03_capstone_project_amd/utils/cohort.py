@@ -238,11 +238,12 @@ def read_volume_comparisons(out_dir):
     one per patient in plan order. `status` is "ok", "no_reference" (the reference tree has no mask for the
     patient) or "shape_mismatch"; the two latter leave every field None. Integer columns come back as int
     (arrays flattened: compare_spacing_um_x / _y / _z, worst_ab_x …), `reference` as text, the derived ones
-    (dice … assd_mm) as float."""
+    (dice … assd_mm) as float. With --compare-lesions the table has nine more columns: lesions_a … multi_b as int,
+    lesion_sensitivity, lesion_precision and lesion_f1 as float."""
     import csv
     import os
     floats = {"dice", "jaccard", "sensitivity", "precision", "volume_a_mm3", "volume_b_mm3", "volume_diff_mm3", "hausdorff_mm",
-              "hd95_mm", "msd_ab_mm", "msd_ba_mm", "assd_mm"}
+              "hd95_mm", "msd_ab_mm", "msd_ba_mm", "assd_mm", "lesion_sensitivity", "lesion_precision", "lesion_f1"}
     text = {"patient", "status"}
     rows = []
     with open(os.path.join(out_dir, "comparisons.csv"), newline="") as f:
@@ -250,6 +251,17 @@ def read_volume_comparisons(out_dir):
             rows.append({k: v if k in text else None if v == "" else v if k == "reference" else float(v) if k in floats else int(v)
                          for k, v in r.items()})
     return rows
+
+
+def read_volume_lesion_comparisons(out_dir):
+    """Rows of <out_dir>/compare_lesions.csv (written by the 3D CLI with --compare-to and --compare-lesions) as dicts
+    keyed by the header: one per reported lesion, side "a" before "b", patients in plan order. `patient` and `side`
+    are text, every other column an int (first flattened to first_x / _y / _z; best is -1 for no partner)."""
+    import csv
+    import os
+    text = {"patient", "side"}
+    with open(os.path.join(out_dir, "compare_lesions.csv"), newline="") as f:
+        return [{k: v if k in text else int(v) for k, v in r.items()} for r in csv.DictReader(f)]
 
 
 def read_volume_mask(path):

@@ -110,6 +110,10 @@ void usage(const std::string& which) {
             << "                         --volume-mask tree; non-zero = set): Dice, Jaccard, the Hausdorff distance, its 95th\n"
             << "                         percentile and the mean surface distances in <patient>/compare.json and\n"
             << "                         <out>/comparisons.csv (needs --mode 3d; not with --split-volume; DIR must not be --out)\n"
+            << "  --compare-lesions N    3d, with --compare-to: also lesion-wise detection scores (1..64 reported lesions per side,\n"
+            << "                         components at --measure-volume-connectivity): hit / missed / spurious / merged / split\n"
+            << "                         lesions, sensitivity, precision and F1 in compare.json and comparisons.csv, one row per\n"
+            << "                         reported lesion in <out>/compare_lesions.csv (not with --split-volume)\n"
             << "  --mode 2d|3d           3d: whole series as a volume (SRG 6-conn + cube dilation)\n"
             << "  --split-volume         3d: each volume split into z-slabs over all ranks (halo exchange)\n"
             << "  --input FILE           test_pipeline: slice to process\n"
@@ -365,6 +369,16 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
         std::exit(2);
       }
     }
+    else if (a == "--compare-lesions") {
+      const std::string v = val();
+      char* end = nullptr;
+      const long n = std::strtol(v.c_str(), &end, 10);
+      if (v.empty() || *end != 0 || n < 1 || n > kMaxVolumeLesions) {
+        std::cerr << "--compare-lesions must be an integer from 1 to " << kMaxVolumeLesions << " (got " << v << ")" << std::endl;
+        std::exit(2);
+      }
+      c.compare_lesions = (int)n;
+    }
     else if (a == "--volume-mesh-placement") {
       const std::string v = val();
       if (!mesh::parse_placement(v, &c.volume_mesh_placement)) {
@@ -546,6 +560,20 @@ AppConfig parse_args(int argc, char** argv, const std::string& which) {
     std::cerr << "--volume-mask is not available with --split-volume: no rank holds the whole mask (drop --split-volume to "
                  "get the mask, or --volume-mask to split the volume)"
               << std::endl;
+    std::exit(2);
+  }
+  if (c.compare_lesions && c.mode != "3d") {
+    std::cerr << "--compare-lesions needs --mode 3d" << std::endl;
+    std::exit(2);
+  }
+  if (c.compare_lesions && c.split_volume) {
+    std::cerr << "--compare-lesions is not available with --split-volume: lesions that cross slabs need a collective (drop "
+                 "--split-volume to get the lesion scores, or --compare-lesions to split the volume)"
+              << std::endl;
+    std::exit(2);
+  }
+  if (c.compare_lesions && c.compare_to.empty()) {
+    std::cerr << "--compare-lesions needs --compare-to DIR: the reference masks whose lesions are matched" << std::endl;
     std::exit(2);
   }
   if (!c.compare_to.empty() && c.mode != "3d") {

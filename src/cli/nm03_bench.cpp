@@ -52,6 +52,7 @@ int main(int argc, char** argv) {
   int64_t dilate_um = -1;          // volume: the margin of --dilate-mm R (K16) in place of the cube / ball, inside kernels_s
   double dilate_mm = 0;
   bool measure_volume_thickness = false;  // volume with --measure-volume: also K16's thickness, inside measure_s
+  int compare_lesions = 0;  // volume with --compare: also K18 with N reported lesions per side, outside compare_ms_per_volume
   bool compare = false;  // volume: also K17 (the dilated volume against the run's own undilated region), outside kernels_s and measure_s
   int mesh_placement = nm03::kMeshCorner;
   uint64_t mesh_max_mb = nm03::mesh::kDefaultMaxMb;
@@ -105,6 +106,7 @@ int main(int argc, char** argv) {
     }
     else if (a == "--measure-volume-thickness") measure_volume_thickness = true;
     else if (a == "--compare") compare = true;
+    else if (a == "--compare-lesions") compare_lesions = std::stoi(v());
     else if (a == "--volume-views") volume_views = true;
     else if (a == "--volume-mesh") volume_mesh = true;
     else if (a == "--volume-mesh-placement") {
@@ -133,6 +135,14 @@ int main(int argc, char** argv) {
   if (measure_volume_thickness) measure_volume = true;
   if (compare && (config != "volume" || ec.host_only)) {
     std::cerr << "--compare needs --config volume and the GPU (not --host-only)" << std::endl;
+    return 2;
+  }
+  if (compare_lesions != 0 && !compare) {
+    std::cerr << "--compare-lesions needs --compare" << std::endl;
+    return 2;
+  }
+  if (compare_lesions < 0 || compare_lesions > nm03::kMaxVolumeLesions) {
+    std::cerr << "--compare-lesions must be 1.." << nm03::kMaxVolumeLesions << std::endl;
     return 2;
   }
   if (volume_views && (config != "volume" || ec.host_only)) {
@@ -258,10 +268,12 @@ int main(int argc, char** argv) {
         compare_ref.w = v.w, compare_ref.h = v.h, compare_ref.d = v.d;
         nm03::measure::volume_spacing_um((double)v.spacing_x, (double)v.spacing_y, v.spacing_z, vp.spacing_um);
         vp.compare = &compare_ref;
+        vp.compare_lesions = compare_lesions;
       }
       for (int w = 0; w < warmup; ++w) runner.run(v, vp, false);
-      double ks = 0, ms = 0, cs = 0;
+      double ks = 0, ms = 0, cs = 0, ls = 0;
       nm03::VolumeCompare vc = {};
+      nm03::VolumeCompareLesions vl;
       int sweeps = 0;
       nm03::VolumeMeasure vm = {};
       size_t lesions = 0;
@@ -276,6 +288,8 @@ int main(int argc, char** argv) {
         ms += r.measure_s;
         cs += r.compare_s;
         vc = r.compare;
+        ls += r.compare_lesions_s;
+        if (compare_lesions) vl = std::move(r.compare_lesions);
         sweeps = r.sweeps;
         vm = r.measure;
         vi = r.intensity;
@@ -287,6 +301,7 @@ int main(int argc, char** argv) {
       }
       const double dt = now_s() - t0;
       vp.compare = nullptr;  // the comparison is timed above alone
+      vp.compare_lesions = 0;
       // + the GPU export of every plane (render + JPEG, both images), as the 3D CLI does
       nm03::VolumeExportStats xs;
       for (int w = 0; w < warmup; ++w) runner.export_jpegs(v, vp, ec.render);
@@ -356,6 +371,10 @@ int main(int argc, char** argv) {
         std::cout << ", \"compare_ms_per_volume\": " << cs * 1e3 / steps << ", \"compare_surface_a\": " << vc.surface_a
                   << ", \"compare_surface_b\": " << vc.surface_b << ", \"compare_dice\": " << dv.dice
                   << ", \"compare_hausdorff_mm\": " << dv.hausdorff_mm << ", \"compare_hd95_mm\": " << dv.hd95_mm;
+        if (compare_lesions)
+          std::cout << ", \"compare_lesions\": " << compare_lesions << ", \"compare_lesions_ms_per_volume\": " << ls * 1e3 / steps
+                    << ", \"compare_lesions_a\": " << vl.head.lesions_a << ", \"compare_lesions_b\": " << vl.head.lesions_b
+                    << ", \"compare_hit_b\": " << vl.head.hit_b << ", \"compare_multi_a\": " << vl.head.multi_a;
       }
       if (measure_volume_thickness)
         std::cout << ", \"thickness\": true, \"inscribed_um2\": " << vt.inscribed_um2

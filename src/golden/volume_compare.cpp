@@ -10,6 +10,7 @@
 #include "nm03/intensity_core.h"
 #include "nm03/volume_compare.h"
 #include "nm03/volume_compare_core.h"
+#include "nm03/volume_compare_lesions.h"
 #include "nm03/volume_distance.h"
 #include "nm03/volume_distance_core.h"
 
@@ -215,7 +216,8 @@ Derived derive(const VolumeCompare& c, const uint32_t um[3]) {
   return v;
 }
 
-std::string to_json(const VolumeCompare& c, int w, int h, int d, const uint32_t um[3], const std::string& reference) {
+std::string to_json(const VolumeCompare& c, int w, int h, int d, const uint32_t um[3], const std::string& reference,
+                    const VolumeCompareLesions* lesions) {
   std::string s = "{";
   bool first = true;
   for (const Field& f : fields(c, w, h, d, um, reference)) {
@@ -226,10 +228,11 @@ std::string to_json(const VolumeCompare& c, int w, int h, int d, const uint32_t 
     s += "\":";
     s += f.json;
   }
+  if (lesions) s += lesions_json_keys(*lesions);
   return s + "}\n";
 }
 
-std::string csv_header() {
+std::string csv_header(bool lesions) {
   static const char* axes[3] = {"_x", "_y", "_z"};
   const uint32_t um[3] = {1, 1, 1};
   std::string s = "patient,status";
@@ -238,10 +241,12 @@ std::string csv_header() {
     else
       for (const char* ax : axes) s += std::string(",") + f.key + ax;
   }
+  if (lesions) s += lesions_csv_header_fields();
   return s;
 }
 
-std::string csv_fields(const VolumeCompare& c, int w, int h, int d, const uint32_t um[3], const std::string& reference) {
+std::string csv_fields(const VolumeCompare& c, int w, int h, int d, const uint32_t um[3], const std::string& reference,
+                       const VolumeCompareLesions* lesions) {
   std::string s;
   bool first = true;
   for (const Field& f : fields(c, w, h, d, um, reference)) {
@@ -249,6 +254,7 @@ std::string csv_fields(const VolumeCompare& c, int w, int h, int d, const uint32
     first = false;
     s += f.csv;
   }
+  if (lesions) s += lesions_csv_fields(*lesions);
   return s;
 }
 

@@ -36,6 +36,7 @@
 #include "nm03/volume.h"
 #include "nm03/volume_compare.h"
 #include "nm03/volume_compare_core.h"
+#include "nm03/volume_compare_lesions.h"
 #include "nm03/volume_slabs.h"
 
 namespace py = pybind11;
@@ -578,6 +579,80 @@ VolumeCompare volume_compare_from(const py::dict& d) {
   return c;
 }
 
+// A lesion-wise comparison record (nm03/volume_compare_lesions.h) as a dict: connectivity, max_lesions, the six
+// totals, a_lesions / b_lesions (lists of dicts of the record's integers) and table (int64 [N + 1, N + 1]).
+py::list volume_compare_lesion_list(const std::vector<VolumeCompareLesion>& v) {
+  py::list out;
+  for (const VolumeCompareLesion& r : v) {
+    py::dict d;
+    py::list at;
+    for (int k = 0; k < 3; ++k) at.append(r.first[k]);
+    d["voxels"] = r.voxels, d["first"] = at, d["overlap_vox"] = r.overlap_vox, d["partners_reported"] = r.partners_reported;
+    d["overlap_other_vox"] = r.overlap_other_vox, d["multi"] = r.multi, d["best"] = r.best, d["best_overlap_vox"] = r.best_overlap_vox;
+    out.append(d);
+  }
+  return out;
+}
+
+py::dict volume_compare_lesions_dict(const VolumeCompareLesions& l) {
+  py::dict d;
+  const VolumeCompareLesionsHead& hd = l.head;
+  d["connectivity"] = hd.connectivity, d["max_lesions"] = hd.max_lesions;
+  d["lesions_a"] = hd.lesions_a, d["hit_a"] = hd.hit_a, d["multi_a"] = hd.multi_a;
+  d["lesions_b"] = hd.lesions_b, d["hit_b"] = hd.hit_b, d["multi_b"] = hd.multi_b;
+  d["a_lesions"] = volume_compare_lesion_list(l.a);
+  d["b_lesions"] = volume_compare_lesion_list(l.b);
+  const int n1 = (int)hd.max_lesions + 1;
+  std::vector<int64_t> t(l.table.begin(), l.table.end());
+  d["table"] = to_np<int64_t>(t, {n1, n1});
+  return d;
+}
+
+std::vector<VolumeCompareLesion> volume_compare_lesion_vector(const py::list& v) {
+  std::vector<VolumeCompareLesion> out;
+  for (const py::handle& hnd : v) {
+    const py::dict d = py::reinterpret_borrow<py::dict>(hnd);
+    VolumeCompareLesion r{};
+    r.voxels = d["voxels"].cast<uint64_t>(), r.overlap_vox = d["overlap_vox"].cast<uint64_t>();
+    r.overlap_other_vox = d["overlap_other_vox"].cast<uint64_t>(), r.best_overlap_vox = d["best_overlap_vox"].cast<uint64_t>();
+    const std::vector<int> at = d["first"].cast<std::vector<int>>();
+    if (at.size() != 3) throw std::invalid_argument("first must be [x, y, z]");
+    for (int k = 0; k < 3; ++k) r.first[k] = at[(size_t)k];
+    r.partners_reported = d["partners_reported"].cast<uint32_t>();
+    r.multi = d["multi"].cast<int32_t>(), r.best = d["best"].cast<int32_t>();
+    out.push_back(r);
+  }
+  return out;
+}
+
+VolumeCompareLesions volume_compare_lesions_from(const py::dict& d) {
+  VolumeCompareLesions l;
+  VolumeCompareLesionsHead& hd = l.head;
+  hd.connectivity = d["connectivity"].cast<uint32_t>(), hd.max_lesions = d["max_lesions"].cast<uint32_t>();
+  if (hd.max_lesions < 1 || hd.max_lesions > (uint32_t)kMaxVolumeLesions)
+    throw std::invalid_argument("max_lesions must be 1.." + std::to_string(kMaxVolumeLesions));
+  hd.lesions_a = d["lesions_a"].cast<uint32_t>(), hd.hit_a = d["hit_a"].cast<uint32_t>(), hd.multi_a = d["multi_a"].cast<uint32_t>();
+  hd.lesions_b = d["lesions_b"].cast<uint32_t>(), hd.hit_b = d["hit_b"].cast<uint32_t>(), hd.multi_b = d["multi_b"].cast<uint32_t>();
+  l.a = volume_compare_lesion_vector(d["a_lesions"].cast<py::list>());
+  l.b = volume_compare_lesion_vector(d["b_lesions"].cast<py::list>());
+  hd.reported_a = (uint32_t)l.a.size(), hd.reported_b = (uint32_t)l.b.size();
+  const auto t = d["table"].cast<py::array_t<int64_t, py::array::c_style | py::array::forcecast>>();
+  const size_t cells = (size_t)(hd.max_lesions + 1) * (hd.max_lesions + 1);
+  if ((size_t)t.size() != cells) throw std::invalid_argument("table must be [max_lesions + 1, max_lesions + 1]");
+  l.table.assign(t.data(), t.data() + cells);
+  return l;
+}
+
+// The optional `lesions` argument of the writer bindings: None, or a lesion-wise comparison dict.
+struct OptionalLesions {
+  VolumeCompareLesions l;
+  bool have = false;
+  explicit OptionalLesions(const py::object& o) {
+    if (!o.is_none()) l = volume_compare_lesions_from(o.cast<py::dict>()), have = true;
+  }
+  const VolumeCompareLesions* get() const { return have ? &l : nullptr; }
+};
+
 // The two masks of the comparison bindings: [D, H, W] of one shape.
 void compare_args(const py::array& a, const py::array& b, const std::vector<int64_t>& spacing_um, uint32_t um[3]) {
   distance_args(a, spacing_um, um);
@@ -623,6 +698,7 @@ struct VolumeMeta {
   std::vector<uint8_t> compare_mask;
   int compare_shape[3] = {0, 0, 0};  // d, h, w
   std::string compare_reference;
+  int compare_lesions = 0;  // VolumeRunner.run(compare_lesions=N): also the lesion-wise comparison (K18)
 };
 
 // compare_to of the runner bindings: None, or a [D, H, W] array (non-zero = set).
@@ -834,6 +910,7 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
     ref.d = meta->compare_shape[0], ref.h = meta->compare_shape[1], ref.w = meta->compare_shape[2];
     vp.compare = &ref;
   }
+  if (meta) vp.compare_lesions = meta->compare_lesions;  // checked by the runner (needs compare_to, 1 … 64)
   VolumeResult r;
   {
     py::gil_scoped_release nogil;
@@ -877,8 +954,13 @@ py::dict volume_call(py::array_t<uint16_t, py::array::c_style | py::array::force
   }
   if (vp.compare) {
     d["compare"] = volume_compare_dict(r.compare);
-    d["compare_json"] = compare::to_json(r.compare, v.w, v.h, v.d, vp.spacing_um, meta->compare_reference);
+    d["compare_json"] = compare::to_json(r.compare, v.w, v.h, v.d, vp.spacing_um, meta->compare_reference,
+                                         vp.compare_lesions ? &r.compare_lesions : nullptr);
     d["compare_s"] = r.compare_s;
+    if (vp.compare_lesions) {
+      d["compare_lesions"] = volume_compare_lesions_dict(r.compare_lesions);
+      d["compare_lesions_s"] = r.compare_lesions_s;
+    }
   }
   return d;
 }
@@ -2036,9 +2118,10 @@ PYBIND11_MODULE(_nm03, m) {
              const std::vector<double>& spacing, const std::string& spacing_z_source, const std::string& type,
              int stored_bits, float slope, float intercept, int measure_lesions, bool measure_intensity, bool measure_texture,
              int texture_levels, bool measure_diameters, int64_t dilate_um, bool measure_thickness, const py::object& compare_to,
-             const std::string& compare_reference) {
+             const std::string& compare_reference, int compare_lesions) {
             VolumeMeta mt;
             compare_to_from(compare_to, compare_reference, mt);
+            mt.compare_lesions = compare_lesions;
             mt.measure_diameters = measure_diameters;
             mt.dilate_um = dilate_um;
             mt.measure_thickness = measure_thickness;
@@ -2064,7 +2147,8 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("type") = "u16", py::arg("stored_bits") = 16, py::arg("slope") = 1.f, py::arg("intercept") = 0.f,
           py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false, py::arg("measure_texture") = false,
           py::arg("texture_levels") = 32, py::arg("measure_diameters") = false, py::arg("dilate_um") = -1,
-          py::arg("measure_thickness") = false, py::arg("compare_to") = py::none(), py::arg("compare_reference") = "")
+          py::arg("measure_thickness") = false, py::arg("compare_to") = py::none(), py::arg("compare_reference") = "",
+          py::arg("compare_lesions") = 0)
       .def(
           "export_views",
           // After run() on a volume of this shape: the views of nm03/volume_views.h from the volume still on
@@ -2129,10 +2213,12 @@ PYBIND11_MODULE(_nm03, m) {
           [](VolumeRunner& self, Comm& comm, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> slab,
              int z0, int depth, const PipelineParams& p, int connectivity, int dilation,
              const std::vector<std::tuple<int, int, int>>& seeds, bool measure, int measure_lesions, bool measure_intensity,
-             bool measure_texture, bool measure_diameters, int64_t dilate_um, bool measure_thickness, const py::object& compare_to) {
+             bool measure_texture, bool measure_diameters, int64_t dilate_um, bool measure_thickness, const py::object& compare_to,
+             int compare_lesions) {
             SlabStats st;
             VolumeMeta mt;
             compare_to_from(compare_to, "", mt);  // refused by run_slab
+            mt.compare_lesions = compare_lesions;  // alike
             mt.measure_diameters = measure_diameters;
             mt.dilate_um = dilate_um;  // refused by run_slab, as the measurements are
             mt.measure_thickness = measure_thickness;
@@ -2153,7 +2239,7 @@ PYBIND11_MODULE(_nm03, m) {
           py::arg("seeds") = std::vector<std::tuple<int, int, int>>{}, py::arg("measure") = false,
           py::arg("measure_lesions") = 0, py::arg("measure_intensity") = false, py::arg("measure_texture") = false,
           py::arg("measure_diameters") = false, py::arg("dilate_um") = -1, py::arg("measure_thickness") = false,
-          py::arg("compare_to") = py::none());
+          py::arg("compare_to") = py::none(), py::arg("compare_lesions") = 0);
 
   // One-process rehearsal of the z-slab decomposition: `nranks` threads, each with its own
   // VolumeRunner (stream) on `device`, talking over loopback comms — the device-resident exchange
@@ -3333,22 +3419,122 @@ PYBIND11_MODULE(_nm03, m) {
       py::arg("a"), py::arg("b"), py::arg("spacing_um") = std::vector<int64_t>{1000, 1000, 1000}, py::arg("junk") = false,
       py::arg("surfaces") = false);
   // compare.json of a comparison dict: the one writer (compare::to_json).
-  m.def("volume_compare_to_json", [](const py::dict& c, int w, int h, int d, const std::vector<int64_t>& spacing_um, const std::string& reference) {
+  // `lesions`: None, or a lesion-wise comparison dict (golden_compare_volume_lesions), whose keys follow assd_mm.
+  m.def("volume_compare_to_json", [](const py::dict& c, int w, int h, int d, const std::vector<int64_t>& spacing_um, const std::string& reference,
+                                     const py::object& lesions) {
     uint32_t um[3];
     spacing_um_from(spacing_um, um);
-    return compare::to_json(volume_compare_from(c), w, h, d, um, reference);
-  }, py::arg("compare"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_um"), py::arg("reference") = "");
-  m.def("volume_compare_csv_header", []() { return compare::csv_header(); });
-  m.def("volume_compare_csv_fields", [](const py::dict& c, int w, int h, int d, const std::vector<int64_t>& spacing_um, const std::string& reference) {
+    const OptionalLesions ol(lesions);
+    return compare::to_json(volume_compare_from(c), w, h, d, um, reference, ol.get());
+  }, py::arg("compare"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_um"), py::arg("reference") = "",
+     py::arg("lesions") = py::none());
+  m.def("volume_compare_csv_header", [](bool lesions) { return compare::csv_header(lesions); }, py::arg("lesions") = false);
+  m.def("volume_compare_csv_fields", [](const py::dict& c, int w, int h, int d, const std::vector<int64_t>& spacing_um, const std::string& reference,
+                                        const py::object& lesions) {
     uint32_t um[3];
     spacing_um_from(spacing_um, um);
-    return compare::csv_fields(volume_compare_from(c), w, h, d, um, reference);
-  }, py::arg("compare"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_um"), py::arg("reference") = "");
+    const OptionalLesions ol(lesions);
+    return compare::csv_fields(volume_compare_from(c), w, h, d, um, reference, ol.get());
+  }, py::arg("compare"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("spacing_um"), py::arg("reference") = "",
+     py::arg("lesions") = py::none());
+  // compare_lesions.csv: the header line and one patient's rows (compare::lesions_table_rows).
+  m.def("volume_compare_lesions_table_header", []() { return compare::lesions_table_header(); });
+  m.def("volume_compare_lesions_table_rows", [](const std::string& patient, const py::dict& lesions) {
+    return compare::lesions_table_rows(patient, volume_compare_lesions_from(lesions));
+  }, py::arg("patient"), py::arg("lesions"));
   // ⌊√v⌋ of the shared core (vcmp::isqrt_um), 0 ≤ v < 2^62.
   m.def("volume_compare_isqrt", [](int64_t v) {
     if (v < 0 || v >= (1ll << 62)) throw std::invalid_argument("0 <= v < 2^62");
     return vcmp::isqrt_um(v);
   });
+
+  // ---- K18: the lesion-wise comparison of nm03/volume_compare_lesions.h ---------------------------------------
+  // The golden model (flood fills, plain loops, a sort) on two masks ([D, H, W], non-zero = set) → the dict.
+  m.def(
+      "golden_compare_volume_lesions",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> b,
+         int max_lesions, int connectivity) {
+        if (a.ndim() != 3) throw std::invalid_argument("mask must be [D, H, W]");
+        if (b.ndim() != 3 || b.shape(0) != a.shape(0) || b.shape(1) != a.shape(1) || b.shape(2) != a.shape(2))
+          throw std::invalid_argument("both masks must be [D, H, W] of one shape");
+        const int d = (int)a.shape(0), h = (int)a.shape(1), w = (int)a.shape(2);
+        const std::vector<uint8_t> ma = from_np<uint8_t>(a), mb = from_np<uint8_t>(b);
+        VolumeCompareLesions l;
+        {
+          py::gil_scoped_release nogil;
+          l = golden::compare_volume_lesions(ma, mb, w, h, d, max_lesions, connectivity);
+        }
+        return volume_compare_lesions_dict(l);
+      },
+      py::arg("a"), py::arg("b"), py::arg("max_lesions"), py::arg("connectivity") = 26);
+  // The same from the K18 kernels' functions run on the host (measure::volume_compare_lesions_words). `junk`: the
+  // storage bits past the width are set in both inputs.
+  m.def(
+      "volume_compare_lesions_words",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> b,
+         int max_lesions, int connectivity, bool junk) {
+        if (a.ndim() != 3) throw std::invalid_argument("mask must be [D, H, W]");
+        if (b.ndim() != 3 || b.shape(0) != a.shape(0) || b.shape(1) != a.shape(1) || b.shape(2) != a.shape(2))
+          throw std::invalid_argument("both masks must be [D, H, W] of one shape");
+        const int d = (int)a.shape(0), h = (int)a.shape(1), w = (int)a.shape(2), wpr = (w + 63) / 64;
+        std::vector<uint64_t> wa = pack_volume(a), wb = pack_volume(b);
+        if (junk)
+          for (size_t r = 0; r < (size_t)d * h; ++r) {
+            wa[r * wpr + wpr - 1] |= ~row_word_mask(wpr - 1, w);
+            wb[r * wpr + wpr - 1] |= ~row_word_mask(wpr - 1, w);
+          }
+        VolumeCompareLesions l;
+        {
+          py::gil_scoped_release nogil;
+          l = measure::volume_compare_lesions_words(wa.data(), wb.data(), w, h, d, wpr, max_lesions, connectivity);
+        }
+        return volume_compare_lesions_dict(l);
+      },
+      py::arg("a"), py::arg("b"), py::arg("max_lesions"), py::arg("connectivity") = 26, py::arg("junk") = false);
+
+  // K18 alone on two device bit volumes [d][h][ceil(w/64)] (int64 words, bits past the width tolerated) → the dict.
+  // The work buffer is this op's own; synchronous on `stream`. `max_blocks`: see launch_volume_compare_lesions.
+  m.def("k_volume_compare_lesions", [](uintptr_t a, uintptr_t b, int w, int h, int d, int max_lesions, int connectivity, int max_blocks,
+                                       uintptr_t stream) {
+    hipStream_t st = as_stream(stream);
+    if (w <= 0 || h <= 0 || d <= 0) throw std::invalid_argument("empty volume");
+    if (!a || !b) throw std::invalid_argument("null buffer");
+    check_max_lesions(max_lesions);
+    if (connectivity != 6 && connectivity != 26) throw std::invalid_argument("connectivity must be 6 or 26");
+    if (max_blocks < 0) throw std::invalid_argument("max_blocks must not be negative");
+    if (gpu::volume_measure_scratch_words(w, h, d) == 0)
+      throw std::invalid_argument("volume too large to measure: (w + 1) * h * d + 1 must stay below 2^32");
+    {
+      // K18's code object, loaded on the current device before this op's first launch there.
+      static std::mutex preload_m;
+      static std::vector<int> preloaded;
+      int dev = 0;
+      gpu::check_hip(hipGetDevice(&dev), "hipGetDevice");
+      std::lock_guard<std::mutex> g(preload_m);
+      if (std::find(preloaded.begin(), preloaded.end(), dev) == preloaded.end()) {
+        gpu::preload_volume_compare_lesions();
+        preloaded.push_back(dev);
+      }
+    }
+    struct DevMem {
+      void* p = nullptr;
+      ~DevMem() {
+        if (p) (void)hipFree(p);
+      }
+    } work;
+    gpu::check_hip(hipMalloc(&work.p, gpu::volume_compare_lesions_work_bytes(w, h, d, max_lesions)), "hipMalloc lesion comparison work");
+    void* h_rec = nullptr;
+    gpu::check_hip(hipHostMalloc(&h_rec, volume_compare_lesions_record_bytes(max_lesions), hipHostMallocDefault),
+                   "hipHostMalloc lesion comparison");
+    struct Pinned {
+      void* p;
+      ~Pinned() { (void)hipHostFree(p); }
+    } pinned{h_rec};
+    gpu::launch_volume_compare_lesions((const uint64_t*)a, (const uint64_t*)b, w, h, d, max_lesions, connectivity, work.p, h_rec, st, max_blocks);
+    gpu::check_hip(hipStreamSynchronize(st), "k_volume_compare_lesions");
+    return volume_compare_lesions_dict(measure::unpack_compare_lesions(h_rec, max_lesions));
+  }, py::arg("a"), py::arg("b"), py::arg("w"), py::arg("h"), py::arg("d"), py::arg("max_lesions"), py::arg("connectivity") = 26,
+     py::arg("max_blocks") = 0, py::arg("stream") = 0);
 
   // K17 alone on two device bit volumes [d][h][ceil(w/64)] (int64 words) → the dict of integers. The work buffer
   // is this op's own; synchronous on `stream`. `max_blocks`: see launch_volume_compare.

@@ -191,6 +191,11 @@ struct VolumeDevice {
   uint64_t* h_cmp_ref = nullptr;
   VolumeCompare* h_compare = nullptr;
   hipEvent_t cmp_e0 = nullptr, cmp_e1 = nullptr;
+  // K18 (VolumeParams::compare_lesions): the work buffer, the pinned record (sized for 64 lesions) and the events
+  // of its timing, allocated by the first run that asks for the lesion-wise comparison and kept.
+  std::unique_ptr<DevBuf> cl_work;
+  uint8_t* h_cl_record = nullptr;
+  hipEvent_t cl_e0 = nullptr, cl_e1 = nullptr;
   VolumeDevice(const VolumeInput& v)
       : w(v.w), h(v.h), d(v.d), wpr((v.w + 63) / 64), words((size_t)v.h * ((v.w + 63) / 64)),
         ps(((size_t)v.w * v.h + 7) / 8 * 8),
@@ -220,6 +225,9 @@ struct VolumeDevice {
     if (h_compare) (void)hipHostFree(h_compare);
     if (cmp_e0) (void)hipEventDestroy(cmp_e0);
     if (cmp_e1) (void)hipEventDestroy(cmp_e1);
+    if (h_cl_record) (void)hipHostFree(h_cl_record);
+    if (cl_e0) (void)hipEventDestroy(cl_e0);
+    if (cl_e1) (void)hipEventDestroy(cl_e1);
     if (h_measure) (void)hipHostFree(h_measure);
     if (h_tables) (void)hipHostFree(h_tables);
     if (h_flag) (void)hipHostFree(h_flag);
@@ -439,6 +447,7 @@ struct VolumeRunner::Impl {
   bool texture_loaded = false;    // K12's code object (first run that asks for the texture)
   bool distance_loaded = false;   // K16's code object (first run that asks for a margin in mm, the thickness or a comparison)
   bool compare_loaded = false;    // K17's code object (first run that asks for a comparison)
+  bool compare_lesions_loaded = false;  // K18's code object (first run that asks for the lesion-wise comparison)
   explicit Impl(int dev) : device(dev) {
     check_hip(hipSetDevice(device), "hipSetDevice");
     preload_kernels();  // every code object, before the first launch (kernels.h)
@@ -518,6 +527,17 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
       throw std::invalid_argument("3D comparison: a volume of 2^32 voxels or more cannot be compared");
     const std::string ext = measure::volume_distance_extent_error(v.w, v.h, v.d, p.spacing_um);
     if (!ext.empty()) throw std::invalid_argument("3D comparison: " + ext);
+  }
+  if (p.compare_lesions != 0) {
+    if (!p.compare) throw std::invalid_argument("3D lesion comparison: compare_lesions needs a reference (compare)");
+    if (p.compare_lesions < 1 || p.compare_lesions > kMaxVolumeLesions)
+      throw std::invalid_argument("3D lesion comparison: compare_lesions must be 1.." + std::to_string(kMaxVolumeLesions) + " (got " +
+                                  std::to_string(p.compare_lesions) + ")");
+    if (p.measure_connectivity != 6 && p.measure_connectivity != 26)
+      throw std::invalid_argument("3D lesion comparison: connectivity must be 6 or 26 (got " + std::to_string(p.measure_connectivity) + ")");
+    if (volume_measure_scratch_words(v.w, v.h, v.d) == 0)
+      throw std::invalid_argument("3D lesion comparison: volume too large to label: (w + 1) * h * d + 1 must stay below 2^32 (got " +
+                                  std::to_string(v.w) + " x " + std::to_string(v.h) + " x " + std::to_string(v.d) + ")");
   }
   if (p.measure) {
     if (p.measure_connectivity != 6 && p.measure_connectivity != 26)
@@ -639,6 +659,19 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
         }
     }
   }
+  if (p.compare_lesions) {  // K18 alike; the record is sized for the largest N, the work buffer does not depend on N
+    if (!I.compare_lesions_loaded) {
+      preload_volume_compare_lesions();
+      I.compare_lesions_loaded = true;
+    }
+    if (!V.cl_work) {
+      V.cl_work = std::make_unique<DevBuf>(volume_compare_lesions_work_bytes(v.w, v.h, v.d, kMaxVolumeLesions));
+      check_hip(hipHostMalloc((void**)&V.h_cl_record, kVolumeCompareLesionsMaxRecordBytes, hipHostMallocDefault),
+                "hipHostMalloc lesion comparison");
+      check_hip(hipEventCreate(&V.cl_e0), "event");
+      check_hip(hipEventCreate(&V.cl_e1), "event");
+    }
+  }
   const PipeConsts pc = make_consts(p.pipe, 2);
   check_hip(hipEventRecord(I.e0, V.stream), "event");
   VolumeResult r;
@@ -705,6 +738,17 @@ VolumeResult VolumeRunner::run(const VolumeInput& v, const VolumeParams& p, bool
     float cms = 0;
     (void)hipEventElapsedTime(&cms, V.cmp_e0, V.cmp_e1);
     r.compare_s = cms * 1e-3;
+  }
+  if (p.compare_lesions) {  // K18's ten launches after K17's, on the masks K17 has on the device, timed on their own
+    check_hip(hipEventRecord(V.cl_e0, V.stream), "event");
+    launch_volume_compare_lesions(V.dil.as<uint64_t>(), V.cmp_ref->as<uint64_t>(), v.w, v.h, v.d, p.compare_lesions, p.measure_connectivity,
+                                  V.cl_work->p, V.h_cl_record, V.stream);
+    check_hip(hipEventRecord(V.cl_e1, V.stream), "event");
+    check_hip(hipEventSynchronize(V.cl_e1), "sync");
+    r.compare_lesions = measure::unpack_compare_lesions(V.h_cl_record, p.compare_lesions);
+    float lms = 0;
+    (void)hipEventElapsedTime(&lms, V.cl_e0, V.cl_e1);
+    r.compare_lesions_s = lms * 1e-3;
   }
   check_hip(hipEventSynchronize(I.e1), "sync");
   r.sweeps = srg_volume_result(V.h_flag);
@@ -856,6 +900,9 @@ VolumeResult VolumeRunner::run_slab(Comm& comm, const VolumeInput& slab, int z0,
   if (p.compare)
     throw std::invalid_argument("run_slab: comparing a volume split into slabs with a reference is not supported "
                                 "(the surface distances of a slab are not those of the volume)");
+  if (p.compare_lesions)
+    throw std::invalid_argument("run_slab: the lesion-wise comparison of a volume split into slabs is not supported "
+                                "(lesions that cross slabs need a collective)");
   if (p.measure || p.measure_lesions || p.measure_diameters || p.measure_intensity || p.measure_texture)
     throw std::invalid_argument("run_slab: measuring a volume split into slabs is not supported "
                                 "(components that cross slabs need a collective)");
@@ -1285,6 +1332,9 @@ struct VolOutcome {
   std::string compare_fields;  // --compare-to: the patient's fields of comparisons.csv (compare::csv_fields)
   int32_t dice_ok = 0, distances_ok = 0;
   double dice = 0, hausdorff_mm = 0, compare_s = 0;
+  std::string lesion_rows;  // --compare-lesions: the patient's rows of compare_lesions.csv (compare::lesions_table_rows)
+  int32_t lesion_f1_ok = 0;
+  double lesion_f1 = 0, compare_lesions_s = 0;
 };
 
 // --compare-to: the reference mask of a patient, DIR/<patient>/mask.mhd, as 0 / 1 bytes (non-zero = set, whatever
@@ -1422,7 +1472,8 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
                                                       VolumeMesh* mesh_out = nullptr, int mesh_placement = kMeshCorner,
                                                       VolumeThickness* thickness = nullptr,
                                                       std::vector<uint8_t>* dilated_out = nullptr,
-                                                      VolumeCompare* compared = nullptr) {
+                                                      VolumeCompare* compared = nullptr,
+                                                      VolumeCompareLesions* compared_lesions = nullptr) {
   const GoldenPlanes gp = golden_preprocess(v, vp);
   std::vector<Seed> seeds = vp.seeds;
   if (seeds.empty()) {
@@ -1452,6 +1503,8 @@ std::vector<std::vector<uint8_t>> golden_volume_jpegs(const VolumeInput& v, cons
   if (compared && vp.compare) {  // --compare-to: the golden comparison with the reference's bytes (nm03/volume_compare.h)
     const std::vector<uint8_t> ref(vp.compare->mask, vp.compare->mask + (size_t)v.w * v.h * v.d);
     *compared = golden::compare_volumes(dil, ref, v.w, v.h, v.d, vp.spacing_um);
+    if (compared_lesions && vp.compare_lesions)  // --compare-lesions: the golden lesion-wise comparison of the same masks
+      *compared_lesions = golden::compare_volume_lesions(dil, ref, v.w, v.h, v.d, vp.compare_lesions, vp.measure_connectivity);
   }
   if (dilated_out) *dilated_out = dil;
   if (mesh_out)  // --volume-mesh: the golden mesh of the dilated mask (nm03/volume_mesh.h)
@@ -1643,8 +1696,10 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       std::vector<uint8_t> ref_mask, dilated;
       VolumeReference ref;
       VolumeCompare compared = {};
+      VolumeCompareLesions compared_lesions;
       const std::string ref_path = cfg.compare_to.empty() ? std::string() : cohort::with_slash(cfg.compare_to) + pp.id + "/mask.mhd";
       vp.compare = nullptr;
+      vp.compare_lesions = 0;
       if (!cfg.compare_to.empty()) {
         ref_mask = read_reference_mask(ref_path, v.w, v.h, v.d, &o.compare_status);
         if (o.compare_status == "ok") {
@@ -1655,6 +1710,12 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
           ref.mask = ref_mask.data();
           ref.w = v.w, ref.h = v.h, ref.d = v.d;
           vp.compare = &ref;
+          if (cfg.compare_lesions) {  // --compare-lesions: K8's limit on the slots, before anything runs
+            if (volume_measure_scratch_words(v.w, v.h, v.d) == 0)
+              throw std::runtime_error("--compare-lesions: volume too large to label: (w + 1) * h * d + 1 must stay below 2^32");
+            vp.compare_lesions = cfg.compare_lesions;
+            vp.measure_connectivity = cfg.measure_volume_connectivity;
+          }
         }
       }
       VolumeMesh vmesh;
@@ -1667,7 +1728,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       if (cfg.cpu) {
         files = golden_volume_jpegs(v, vp, rp, vp.measure ? &measured : nullptr, &lesions, &intensity, &texture, &diameters,
                                     cfg.volume_views ? &cfg.volume_views_at : nullptr, &vx, cfg.volume_mesh ? &vmesh : nullptr,
-                                    cfg.volume_mesh_placement, &thickness, cfg.volume_mask ? &dilated : nullptr, &compared);
+                                    cfg.volume_mesh_placement, &thickness, cfg.volume_mask ? &dilated : nullptr, &compared, &compared_lesions);
         if (cfg.volume_mesh) {  // the check export_mesh makes between its two halves
           const std::string err = mesh::size_error(vmesh.vertices(), vmesh.quad_count(), mesh_cap);
           if (!err.empty()) throw std::runtime_error("--volume-mesh: " + err);
@@ -1679,6 +1740,8 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         o.measure_s = r.measure_s;
         o.compare_s = r.compare_s;
         compared = r.compare;
+        o.compare_lesions_s = r.compare_lesions_s;
+        compared_lesions = std::move(r.compare_lesions);
         dilated = std::move(r.dilated);
         measured = r.measure;
         lesions = std::move(r.lesions);
@@ -1719,9 +1782,15 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
         o.mask_files = 2;
       }
       if (vp.compare) {  // the sidecar; its table fields travel to rank 0
-        const std::string text = compare::to_json(compared, v.w, v.h, v.d, vp.spacing_um, ref_path);
+        const VolumeCompareLesions* cl = vp.compare_lesions ? &compared_lesions : nullptr;
+        const std::string text = compare::to_json(compared, v.w, v.h, v.d, vp.spacing_um, ref_path, cl);
         write_bytes(pp.out_dir + "/compare.json", text.data(), text.size());
-        o.compare_fields = compare::csv_fields(compared, v.w, v.h, v.d, vp.spacing_um, ref_path);
+        o.compare_fields = compare::csv_fields(compared, v.w, v.h, v.d, vp.spacing_um, ref_path, cl);
+        if (cl) {
+          o.lesion_rows = compare::lesions_table_rows(pp.id, compared_lesions);
+          const compare::LesionsDerived lv = compare::derive_lesions(compared_lesions);
+          o.lesion_f1_ok = lv.f1_ok, o.lesion_f1 = lv.f1;
+        }
         const compare::Derived dv = compare::derive(compared, vp.spacing_um);
         o.dice_ok = dv.dice_ok, o.dice = dv.dice;
         o.distances_ok = dv.distances_ok, o.hausdorff_mm = dv.hausdorff_mm;
@@ -1784,6 +1853,10 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
     w.f64(o.dice);
     w.f64(o.hausdorff_mm);
     w.f64(o.compare_s);
+    w.str(o.lesion_rows);
+    w.i32(o.lesion_f1_ok);
+    w.f64(o.lesion_f1);
+    w.f64(o.compare_lesions_s);
   }
   auto all = comm.allgather_bytes(w.b);
   double tot = wall_now() - t_start;
@@ -1821,6 +1894,10 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       o.dice = r.f64();
       o.hausdorff_mm = r.f64();
       o.compare_s = r.f64();
+      o.lesion_rows = r.str();
+      o.lesion_f1_ok = r.i32();
+      o.lesion_f1 = r.f64();
+      o.compare_lesions_s = r.f64();
       outs.push_back(std::move(o));
     }
   }
@@ -1882,6 +1959,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
        << ", \"exchanged_bytes\": " << o.exchanged;
     if (cfg.measure_volume) pj << ", \"measure_s\": " << o.measure_s;
     if (!cfg.compare_to.empty()) pj << ", \"compare_s\": " << o.compare_s;
+    if (cfg.compare_lesions) pj << ", \"compare_lesions_s\": " << o.compare_lesions_s;
     pj << "}";
   }
   std::cout << "\n=== All Processing Completed ===\n" << std::endl;
@@ -1907,7 +1985,7 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
   }
   if (!cfg.compare_to.empty()) {  // the comparison table, in plan order (an error is reported, not fatal)
     try {
-      std::string text = compare::csv_header() + "\n";
+      std::string text = compare::csv_header(cfg.compare_lesions != 0) + "\n";
       const size_t commas = (size_t)std::count(text.begin(), text.end(), ',') - 1;  // after patient,status
       for (size_t i = 0; i < plan.size(); ++i) {
         const VolOutcome& o = outs[i];
@@ -1916,6 +1994,12 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
                 (ok ? o.compare_fields : std::string(commas - 1, ',')) + "\n";
       }
       write_bytes(cohort::with_slash(cfg.out_dir) + "comparisons.csv", text.data(), text.size());
+      if (cfg.compare_lesions) {  // one row per reported lesion, side a before b, patients in plan order
+        std::string rows = compare::lesions_table_header() + "\n";
+        for (size_t i = 0; i < plan.size(); ++i)
+          if (outs[i].ok && outs[i].compare_status == "ok") rows += outs[i].lesion_rows;
+        write_bytes(cohort::with_slash(cfg.out_dir) + "compare_lesions.csv", rows.data(), rows.size());
+      }
     } catch (const std::exception& e) {
       std::cerr << "Error writing comparisons.csv: " << e.what() << std::endl;
     }
@@ -1964,7 +2048,17 @@ int volume_rank(const AppConfig& cfg, int rank, int size, Comm& comm, int device
       std::string dm = "null", hm = "null";
       if (dn) std::snprintf(buf, sizeof buf, "%.9g", dice_sum / (double)dn), dm = buf;
       if (any_hd) std::snprintf(buf, sizeof buf, "%.9g", hd_max), hm = buf;
-      f << ", \"compare\": {\"volumes\": " << cn << ", \"dice_mean\": " << dm << ", \"hausdorff_mm_max\": " << hm << "}";
+      f << ", \"compare\": {\"volumes\": " << cn << ", \"dice_mean\": " << dm << ", \"hausdorff_mm_max\": " << hm;
+      if (cfg.compare_lesions) {
+        int64_t fn = 0;
+        double f1_sum = 0;
+        for (const auto& o : outs)
+          if (o.ok && o.compare_status == "ok" && o.lesion_f1_ok) ++fn, f1_sum += o.lesion_f1;
+        std::string fm = "null";
+        if (fn) std::snprintf(buf, sizeof buf, "%.9g", f1_sum / (double)fn), fm = buf;
+        f << ", \"lesions\": true, \"lesion_f1_mean\": " << fm;
+      }
+      f << "}";
     }
     f << "}\n";
   }

@@ -8,7 +8,8 @@
 // and no Python. Build it with the host sources it calls and run it:
 //
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude \
-//       tools/volume_compare_sanitize.cpp src/golden/volume_compare.cpp src/golden/volume_distance.cpp \
+//       tools/volume_compare_sanitize.cpp src/golden/volume_compare.cpp src/golden/volume_compare_lesions.cpp \
+//       src/golden/volume_distance.cpp \
 //       -o volume_compare_sanitize && ./volume_compare_sanitize
 //
 // It prints one line per case and exits 0 when everything agrees.
